@@ -20,7 +20,7 @@ episode-metrics vector (accumulated on the device by the frame kernel) after the
 65,536 envs IN TOTAL at every N ("scaling": "strong"; 8,192 per GPU at N = 8 = config C of SURVEY.md 8(d)); workload E is defined
 per GPU (32,768 each, "weak").  --scaling / --total-envs / --envs-per-gpu override.
 
-Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W] [--workload B|D|E|F]
+Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W] [--workload B|D|E|F] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
 Prints ONE JSON line on rank 0.
@@ -43,6 +43,11 @@ HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # joined inside the timed region (PipelinedVecGame; --parts 1: one batch on one stream).  Measured on one MI355X (profiles/r03_z_parts_sweep.txt):
 # 2 parts give +14 % on workload B at 65,536 envs, +7-9 % at 8,192-32,768, +6-12 % on D, E, F, C, L, T; 3 give no more; 4 side streams collapse.
 DEFAULT_PARTS = 2
+# --dump-outputs: what step() hands its caller, in env order.  Above DUMP_BUDGET bytes a fixed, seeded sample of env rows is written instead
+# (the same rows for the same arguments), with the sampled env indices as env_index.npy.
+DUMP_NAMES = ("obs_num", "lasers", "target", "reward", "done", "status")
+DUMP_BUDGET = 64 << 20
+DUMP_SAMPLE_SEED = 20240601
 
 
 def bytes_per_env_step(cfg, G, Cn):
@@ -118,6 +123,25 @@ def cpu_baseline(cfg, pool, n_envs, steps, age, seed, label):
                        "loop inside the timed region, %.1f s wall" % (n_envs, label, steps, cores, visible, age, n_resets, dt))
 
 
+def dump_outputs(out_dir, outs):
+    """Write the host copies ``outs`` (name -> tensor with one row per env) as out_dir/<name>.npy: float64 stays float64, every other
+    dtype becomes float32 (u8 done / status codes are exact in it)."""
+    arrays = {}
+    for name, t in outs.items():
+        a = t.numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    n = len(arrays["reward"])
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    if row_bytes * n > DUMP_BUDGET - 4096:                 # (4 KB kept for the .npy headers)
+        k = (DUMP_BUDGET - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["env_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def build_workload(name, base, seed, device):
     """(cfg, pool, workload text, bytes per env-step, kernel names) of a workload; base = global index of this rank's first env
     (env_id_base: the keys of the per-env random streams of row a12 stay distinct across ranks)."""
@@ -191,10 +215,17 @@ def main():
                     help="B: the configuration the metric is quoted on.  D, E: the other BASELINE configs.  F: the shipped training config.  "
                          "C, L, T (information only): config B's world with the row-f3 sensors -- compas ray sensors / lidars + leader-track "
                          "detectors / the v1 tracker -- which add ftl_aux_kernel (and ftl_tracker1_kernel) to every step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step returned (obs_num, lasers, target, reward, done, status of "
+                         "every env, in env order) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (above that a fixed, seeded "
+                         "sample of envs, their indices in env_index.npy); ranks > 0 of a multi-GPU run write to DIR/rank<r>/.  Without --ring "
+                         "the same arguments give the same inputs, so two builds can be compared output for output")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the metrics all-reduce: nccl (= RCCL over xGMI, one GPU per rank) or gloo -- a rehearsal "
                          "of the N > 1 path on a box with fewer GPUs than ranks (every rank then uses GPU rank %% n_visible)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -279,6 +310,8 @@ def main():
     dt = time.perf_counter() - t0
     k0 += a.steps
     step_ms = ev0.elapsed_time(ev1) / a.steps          # HIP events on the launch stream: avg launch-to-launch duration
+    # the outputs of the last timed step, copied before the kernel-timing pass below steps the same population on
+    outs = {name: getattr(env, name).cpu() for name in DUMP_NAMES} if a.dump_outputs else None
 
     # episode metrics: the 8 x f64 vector the frame kernel accumulated on the device (before auto-reset wipes the counters);
     # its all-reduce is the only collective of the path, off the timed region
@@ -342,6 +375,8 @@ def main():
     if ring is not None:
         supply = dict(supply or {}, ring_half=a.ring, window_moves_in_timed_region=ring.swaps - swaps0, scenarios_generated=ring.generated)
         ring.close()
+    if outs is not None:
+        dump_outputs(a.dump_outputs if rank == 0 else os.path.join(a.dump_outputs, "rank%d" % rank), outs)
     if rank == 0:
         m = metrics.tolist()
         if ktimes:
