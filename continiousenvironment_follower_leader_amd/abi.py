@@ -143,6 +143,7 @@ class ScenParams(C.Structure):
 
 
 SCEN_FOUND, SCEN_DONE_AT_RESET, SCEN_ROUTE_OVERFLOW, SCEN_TRAJ_OVERFLOW, SCEN_REF_RAISES = 1, 2, 4, 8, 16
+SCEN_GEN_LIMIT = 32              # ftl_generate_scenarios_device only: a rejection sampler hit its cap of 2^20 draws
 
 
 class Outputs(C.Structure):

@@ -606,6 +606,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 }  // extern "C"
 
 #include "ftl_gazebo.hpp"      // follower-relative tracker / ray sensors (include/ftl_gazebo.h), same translation unit
+#include "ftl_scenario_dev.hpp"  // the scenario generator on the GPU (ftl_generate_scenarios_device), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

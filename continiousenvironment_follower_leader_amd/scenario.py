@@ -226,3 +226,224 @@ class ScenarioRing:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------------------------- the generator on the GPU
+SCEN_KEYS = ("static_rects", "robot_pos", "robot_dir", "robot_rect", "route", "route_len", "init_traj", "init_traj_len")
+DEVICE_USABLE_MASK = USABLE_MASK | abi.SCEN_GEN_LIMIT
+
+
+def _device_params(cfg: GameConfig):
+    sp = scen_params(cfg)
+    if sp.planner == 1:
+        raise NotImplementedError("path_finding_algorythm='astar' has no device generator (CPython heapq order is sequential): "
+                                  "use generate_scenarios / ScenarioRing")
+    return sp
+
+
+class _DeviceGenerator:
+    """Output arrays + workspace of ``ftl_generate_scenarios_device`` for up to ``capacity`` seeds per launch (allocated once)."""
+
+    def __init__(self, cfg: GameConfig, capacity, device):
+        self.lib = _lib.load()
+        self.cfg, self.capacity, self.device = cfg, int(capacity), torch.device(device)
+        self.sp = _device_params(cfg)
+        c, R, n = cfg.c, cfg.n_robots, self.capacity
+        ws = C.c_size_t(0)
+        _lib.check(self.lib.ftl_generate_scenarios_device_workspace(C.byref(c), C.byref(self.sp), n, C.byref(ws)), self.lib)
+        shapes = dict(static_rects=((n, c.n_static, 4), torch.int32), robot_pos=((n, R, 2), torch.float32),
+                      robot_dir=((n, R), torch.float64), robot_rect=((n, R, 4), torch.int32),
+                      route=((n, c.route_cap, 2), torch.float64), route_len=((n,), torch.int32),
+                      init_traj=((n, c.init_traj_cap, 2), torch.float32), init_traj_len=((n,), torch.int32))
+        self.out = {k: torch.empty(sh, dtype=dt, device=self.device) for k, (sh, dt) in shapes.items()}
+        self.status = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.ws = torch.empty(max(int(ws.value), 1), dtype=torch.uint8, device=self.device)
+        self.s = abi.Scenarios()
+        self.s.n_scenarios = n
+        for k, v in self.out.items():
+            setattr(self.s, k, v.data_ptr())
+
+    def run(self, seeds, stream=None):
+        """Launch on ``stream`` (default: the current stream) for the int64 device tensor ``seeds``; returns views of the first len(seeds)
+        entries (valid once the stream has passed the launch; overwritten by the next run)."""
+        n = int(seeds.numel())
+        if n > self.capacity:
+            raise ValueError("%d seeds > capacity %d" % (n, self.capacity))
+        stream = stream if stream is not None else torch.cuda.current_stream(self.device)
+        seeds = seeds.contiguous()
+        _lib.check(self.lib.ftl_generate_scenarios_device(C.byref(self.cfg.c), C.byref(self.sp), seeds.data_ptr(), n, C.byref(self.s),
+                                                          self.status.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                                          C.c_void_p(stream.cuda_stream)), self.lib)
+        out = {k: v[:n] for k, v in self.out.items()}
+        status = self.status[:n]
+        out["status"] = status
+        out["usable"] = ((status & abi.SCEN_FOUND) != 0) & ((status & DEVICE_USABLE_MASK) == 0)
+        return out
+
+
+def generate_scenarios_device(cfg: GameConfig, seeds, device):
+    """``generate_scenarios`` on the GPU (``ftl_generate_scenarios_device``): device tensors in the same layout, ``status`` and ``usable``
+    (status bit ``abi.SCEN_GEN_LIMIT`` also makes a scenario unusable), ``seed`` as an int64 device tensor.  Planner ``astar`` raises
+    NotImplementedError before the device is touched.  Bit for bit the host generator's output (atan / cos / sin are evaluated correctly
+    rounded, which is what glibc returns on every generator input measured; include/ftl.h).  Each call allocates its own outputs and
+    workspace -- for config B and 2,048 or more seeds about 760 MB of workspace (2,048 wavefronts x 372 KB); a caller that generates
+    again and again (DeviceScenarioRing) keeps one ``_DeviceGenerator`` instead."""
+    _device_params(cfg)
+    dev = torch.device(device)
+    seeds = torch.as_tensor(np.asarray(seeds, np.int64) if not isinstance(seeds, torch.Tensor) else seeds).to(torch.int64).reshape(-1)
+    seeds = seeds.to(dev)
+    g = _DeviceGenerator(cfg, max(len(seeds), 1), dev)
+    out = g.run(seeds)
+    out = {k: v.clone() if k in SCEN_KEYS or k == "status" else v for k, v in out.items()}
+    out["usable"] = ((out["status"] & abi.SCEN_FOUND) != 0) & ((out["status"] & DEVICE_USABLE_MASK) == 0)
+    out["seed"] = seeds
+    return out
+
+
+class DeviceScenarioRing:
+    """``ScenarioRing`` with the producer on the GPU: ``K`` segments of ``S`` pool entries; the envs' auto-reset draws from one segment
+    (``ftl_set_reset_window``) while ``ftl_generate_scenarios_device`` fills the oldest free one on a side stream of its own, from python
+    seeds ``seed_base, seed_base + 1, ...`` (no host iterator, no host copy).  The first ``S`` usable scenarios of the next seeds are
+    compacted into the segment on the device; a segment that comes out short is topped up by a further launch.  ``poll`` reads the filled
+    count through an event (it never blocks) and moves the window to a segment as soon as it is complete.
+
+    A segment is only rewritten ``horizon`` = max_steps / frames_per_step + 2 steps after the window left it (every episode that started on
+    it has ended by then).  Sizing rule: with a window move every ``t_fill`` steps the supply is at most ``(K - 1) * S / horizon`` worlds per
+    step, whatever the kernel's speed -- K - 1 segments wait out the horizon while one is live.  One world per reset needs
+    ``(K - 1) * S >= horizon * resets per step``; K = 2 is the shape of the host ring (two halves).  E.g. config B (horizon 502) at 65,536
+    envs: measured 339 resets per step (1,017,218 episodes ended in 3,000 steps, profiles/r04_scenario_supply.json), so (K - 1) * S of
+    about 170 k, K * S of 200-300 k worlds (~3 KB each at route_cap 128).
+
+    ``history`` (``record=True``): ``(step, segment, (seed_lo, seed_hi), arrays)`` for every segment that went live, ``arrays`` a device copy
+    of its entries; ``[seed_lo, seed_hi)`` is the seed range its usable scenarios came from, in order."""
+
+    def __init__(self, cfg: GameConfig, segment, device, segments=2, seed_base=0, chunk=None, record=False):
+        from .vec_game import ScenarioPool
+        if int(segments) < 2 or int(segment) < 1:
+            raise ValueError("a DeviceScenarioRing needs segments >= 2 and segment >= 1")
+        _device_params(cfg)
+        self.cfg, self.S, self.K, self.device = cfg, int(segment), int(segments), torch.device(device)
+        # one spare row past the K * S entries: the compaction's destination of everything that is not kept
+        self.pool = ScenarioPool.empty(cfg, self.K * self.S + 1, self.device)
+        self.pool.n = self.K * self.S
+        self.pool._bind()
+        self._chunk = int(chunk or max(256, int(self.S * 1.2) + 64))
+        self._gen = _DeviceGenerator(cfg, self._chunk, self.device)
+        c = cfg.c
+        fps = c.rand_fps_lo if c.rand_fps_hi > 0 else c.frames_per_step
+        self.horizon = c.max_steps // max(fps, 1) + 2
+        self._stream = torch.cuda.Stream(device=self.device)
+        self._have = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._host = torch.zeros(2, dtype=torch.int64).pin_memory()
+        self._next_seed = int(seed_base)
+        self._fill = None             # segment being filled: dict(seg, lo, launch_lo, event)
+        self.active = 0
+        self._left_at = [None] + [-10 ** 9] * (self.K - 1)
+        self.generated = 0            # usable scenarios written into segments that went live
+        self.seeds_used = 0           # seeds consumed by those segments
+        self.launches = 0
+        self.swaps = 0
+        self.history = [] if record else None
+        # the first segment, synchronously; the side stream first waits for everything queued so far (the pool's own zero fill included)
+        self._stream.wait_stream(torch.cuda.current_stream(self.device))
+        self._start(0)
+        for _ in range(1 << 16):
+            self._fill["event"].synchronize()
+            if self._advance():
+                break
+        else:
+            raise RuntimeError("no usable scenario among %d seeds" % (self._chunk << 16))
+        f = self._fill
+        self._fill = None
+        self._went_live(0, f)
+
+    def _launch(self, f):
+        S, seg = self.S, f["seg"]
+        with torch.cuda.stream(self._stream):
+            seeds = torch.arange(f["launch_lo"], f["launch_lo"] + self._chunk, dtype=torch.int64, device=self.device)
+            g = self._gen.run(seeds, self._stream)
+            cnt = torch.cumsum(g["usable"].to(torch.int64), 0)
+            have = self._have
+            pos = have + cnt - 1
+            keep = g["usable"] & (pos < S)
+            dest = torch.where(keep, pos + seg * S, torch.full_like(pos, self.K * S))
+            for k in SCEN_KEYS:
+                self.pool.t[k].index_copy_(0, dest, g[k])
+            need = S - have
+            total = cnt[-1:]
+            consumed = torch.where(have + total >= S, torch.searchsorted(cnt, need) + 1, torch.full_like(have, self._chunk))
+            have.copy_(torch.minimum(have + total, torch.full_like(have, S)))
+            self._host[0:1].copy_(have, non_blocking=True)
+            self._host[1:2].copy_(consumed, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._stream)
+        f["event"] = ev
+        self.launches += 1
+
+    def _start(self, seg):
+        with torch.cuda.stream(self._stream):
+            self._have.zero_()
+        self._fill = dict(seg=seg, lo=self._next_seed, launch_lo=self._next_seed)
+        self._launch(self._fill)
+
+    def _advance(self):
+        """The fill's last launch has landed: top it up (False) or close the segment's seed range (True)."""
+        f = self._fill
+        have, consumed = (int(x) for x in self._host.tolist())
+        if have < self.S:
+            f["launch_lo"] += self._chunk
+            self._launch(f)
+            return False
+        f["hi"] = f["launch_lo"] + consumed
+        self._next_seed = f["hi"]
+        return True
+
+    def _went_live(self, step, f):
+        seg = f["seg"]
+        self.generated += self.S
+        self.seeds_used += f["hi"] - f["lo"]
+        if self.history is not None:
+            arrays = {k: v[seg * self.S:(seg + 1) * self.S].clone() for k, v in self.pool.t.items()}
+            self.history.append((step, seg, (f["lo"], f["hi"]), arrays))
+
+    def _stride(self, env):
+        import math
+        s = max(env.n % self.S, 1)
+        while math.gcd(s, self.S) != 1:
+            s += 1
+        return s
+
+    def attach(self, env):
+        """Load the ring's pool into ``env`` with the reset window on the first segment."""
+        env.load_scenarios(self.pool)
+        env.set_reset_window(0, self.S, self._stride(env))
+
+    def poll(self, env, step):
+        """Call between steps with the number of steps taken so far.  Moves the reset window to a segment whose fill has landed, tops up a
+        short one, and starts filling the oldest free segment.  Never blocks.  Returns True when the window moved."""
+        moved = False
+        f = self._fill
+        if f is not None and f["event"].query() and self._advance():
+            self._fill = None
+            seg = f["seg"]
+            self._left_at[self.active] = step
+            self.active = seg
+            self._left_at[seg] = None
+            env.set_reset_window(seg * self.S, self.S, self._stride(env))
+            self.swaps += 1
+            self._went_live(step, f)
+            moved = True
+        if self._fill is None:
+            free = [j for j in range(self.K) if self._left_at[j] is not None and step - self._left_at[j] >= self.horizon]
+            if free:
+                seg = min(free, key=lambda j: self._left_at[j])
+                # `step` counts the steps the HOST has queued: the side stream waits for all of them (and for every part's stream)
+                self._stream.wait_stream(torch.cuda.current_stream(self.device))
+                for st in getattr(env, "streams", ()):
+                    self._stream.wait_stream(st)
+                self._start(seg)
+        return moved
+
+    def close(self):
+        """Wait for the side stream (nothing runs in the background on the host)."""
+        self._stream.synchronize()

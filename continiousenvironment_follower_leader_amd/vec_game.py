@@ -107,6 +107,22 @@ class ScenarioPool:
         return pool
 
     @classmethod
+    def generate_on_device(cls, cfg, seeds, device):
+        """``generate`` with the generator on the GPU (scenario.generate_scenarios_device): the usable scenarios in seed order, compacted on
+        the device."""
+        from .scenario import SCEN_KEYS, generate_scenarios_device
+        g = generate_scenarios_device(cfg, seeds, device)
+        keep = torch.nonzero(g["usable"]).reshape(-1)
+        if keep.numel() == 0:
+            raise ValueError("no usable scenario among the given seeds")
+        pool = cls.__new__(cls)
+        pool.n = int(keep.numel())
+        pool.t = {k: g[k].index_select(0, keep).contiguous() for k in SCEN_KEYS}
+        pool._bind()
+        pool.seeds = g["seed"].index_select(0, keep)
+        return pool
+
+    @classmethod
     def from_npz(cls, cfg, path, device, limit=None):
         z = np.load(path)
         n = len(z["seed"]) if limit is None else min(limit, len(z["seed"]))

@@ -250,11 +250,34 @@ typedef struct ftl_scen_params {
 #define FTL_SCEN_ROUTE_OVERFLOW 4u /* route longer than cfg->route_cap: truncated, do not use */
 #define FTL_SCEN_TRAJ_OVERFLOW 8u  /* initial trajectory longer than cfg->init_traj_cap: truncated, do not use */
 #define FTL_SCEN_REF_RAISES  16u   /* the reference's reset() would raise here (one-point route, ENV:513) */
+#define FTL_SCEN_GEN_LIMIT   32u   /* device generator only: a rejection sampler (rocks ENV:651-668, finish point ENV:1614-1630) or
+                                      randbelow drew 2^20 times without success -- the reference would go on drawing; unusable.  The
+                                      host generator never sets it (no real seed gets there) */
 
 /* Fill `out` (HOST arrays shaped like ftl_scenarios with P = n; cfg gives n_static, R, route_cap, init_traj_cap) with the
  * scenarios of python seeds seeds[0..n); status[i] gets the FTL_SCEN_* bits of scenario i.  n_threads <= 0: all cores. */
 int ftl_generate_scenarios(const ftl_config* cfg, const ftl_scen_params* sp, const int64_t* seeds, int32_t n,
                            int32_t n_threads, const ftl_scenarios* out, uint8_t* status);
+
+/* ---- the same generator on the GPU (ftl_scenario_dev.hpp): scenarios straight into device memory --------------------------------
+ * Scenario i of ftl_generate_scenarios_device equals scenario i of ftl_generate_scenarios for the same seed, array for array, including
+ * the zero padding and the status byte -- robots (ENV:545-611), bridge walls + rocks (ENV:613-677), finish point(s) (ENV:1614-1630, the
+ * three legs of multiple_end_points ENV:470-481), the D* route (ENV:1493-1612 on utils/dstar.py:84-210, with its max_iterat cap), bears
+ * (ENV:687-720, 761-770), the initial leader trajectory (ENV:533-539) -- except that
+ *   - the start directions (atan, f64) and the follower's placements (cos / sin) are evaluated correctly rounded (double-double, rounded
+ *     once); glibc's atan / sin / cos round the same way on every generator input measured (seeds 0..4095 of every golden dstar /
+ *     trajectory config), but not on every double -- a seed where glibc is off by an ulp would give a start direction an ulp apart;
+ *   - a rejection sampler that draws 2^20 times without success stops with FTL_SCEN_GEN_LIMIT (the host would go on drawing).
+ * Limits: the D* grid, (width / step_grid + 2) x (height / step_grid + 2) cells, at most 65,536 cells, and at most 1,022 rocks
+ * (n_static <= 1,024); beyond either, both entry points return FTL_E_UNSUPPORTED.
+ * planner 0 (dstar) and 2 (fixed_route, a HOST pointer, copied into the workspace on `stream`) only; planner 1 (astar: CPython heapq order,
+ * inherently sequential) returns FTL_E_UNSUPPORTED before any device work.  dev_seeds [n], the arrays of dev_out (P = n) and dev_status [n]
+ * are DEVICE pointers; `workspace` is a device buffer of at least ftl_generate_scenarios_device_workspace(cfg, sp, n) bytes owned by the
+ * caller (nothing is allocated here).  Asynchronous on `stream` (NULL: the null stream); the caller keeps every buffer alive until the
+ * stream has passed the call. */
+int ftl_generate_scenarios_device_workspace(const ftl_config* cfg, const ftl_scen_params* sp, int32_t n, size_t* workspace_bytes);
+int ftl_generate_scenarios_device(const ftl_config* cfg, const ftl_scen_params* sp, const int64_t* dev_seeds, int32_t n,
+                                  const ftl_scenarios* dev_out, uint8_t* dev_status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* struct sizes as this library was compiled (binding self-check) */
 size_t ftl_sizeof_config(void);

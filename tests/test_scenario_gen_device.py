@@ -1,0 +1,251 @@
+"""Scenario generator on the GPU (ftl_generate_scenarios_device, scenario.generate_scenarios_device / DeviceScenarioRing).
+
+CPU: the entry points, the workspace query and the argument checks.  GPU: scenario for scenario against the host generator
+(ftl_generate_scenarios) on every golden config whose planner is dstar or a caller-supplied trajectory, against what the reference's reset()
+built (the criteria of test_scenario_gen.py), and a DeviceScenarioRing replayed synchronously into a plain batch."""
+import ctypes as C
+import json
+
+import numpy as np
+import pytest
+
+from continiousenvironment_follower_leader_amd import _lib, abi
+from continiousenvironment_follower_leader_amd.scenario import generate_scenarios, generate_scenarios_device, scen_params
+from golden_util import GOLDEN, config_for, episode_names, load_episode, scenario_arrays
+
+# every output array, bit for bit: atan / cos / sin are evaluated correctly rounded on the device (csrc/ftl_crmath.hpp), which is what
+# glibc returns on every input these seeds produce
+KEYS_EXACT = ("static_rects", "robot_pos", "robot_dir", "robot_rect", "route", "route_len", "init_traj", "init_traj_len")
+HOST_CONFIGS = ("B_s1_chase", "B3_s8_chase", "B6_s2_chase", "D_s2_chase", "E_s3_chase", "F_s1_chase", "Bmep_s2_chase", "Btraj_s3_chase")
+SEEDS = np.concatenate([np.arange(4096), [-1, -2, -7, -4097, -(1 << 40) - 3, 1 << 32, (1 << 32) + 5, (1 << 40) + 11, (1 << 62) + 1]])
+
+
+def _pool_cfg(**over):
+    z = np.load(GOLDEN + "/pool_B.npz")
+    meta = json.loads(str(z["meta"]))
+    return config_for(dict(kwargs=dict(meta["kwargs"], **over), post=None), scen_route_len=256), z, meta
+
+
+def _episode_cfg(name):
+    z, meta = load_episode(name)
+    return config_for(meta, scen_route_len=256)
+
+
+def _route_cost(r, sg=10):
+    d = np.diff(np.asarray(r, np.float64), axis=0) / sg
+    return float(np.sqrt((d ** 2).sum(1)).sum())
+
+
+def _call(lib, cfg, sp, n, out=None, status=None, ws=None, ws_bytes=0, seeds=None):
+    return lib.ftl_generate_scenarios_device(C.byref(cfg.c) if cfg is not None else None, C.byref(sp) if sp is not None else None,
+                                             seeds, n, C.byref(out) if out is not None else None, status, ws, ws_bytes, None)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- CPU
+def test_device_entry_points_resolve():
+    lib = _lib.load()
+    for name in ("ftl_generate_scenarios_device", "ftl_generate_scenarios_device_workspace"):
+        assert hasattr(lib, name) and name in _lib.EXPORTS
+    assert any(s.endswith("ftl_scenario_dev.hpp") for s in _lib.SOURCES)
+
+
+def test_workspace_query_config_b():
+    lib = _lib.load()
+    cfg, _, _ = _pool_cfg()
+    sp = scen_params(cfg)
+    ws = C.c_size_t(0)
+    assert lib.ftl_generate_scenarios_device_workspace(C.byref(cfg.c), C.byref(sp), 16384, C.byref(ws)) == abi.FTL_OK
+    grid = (sp.width // sp.step_grid + 2) * (sp.height // sp.step_grid + 2)
+    assert ws.value >= grid * 8           # at least the f64 D* costs of one wavefront
+    small = C.c_size_t(0)
+    assert lib.ftl_generate_scenarios_device_workspace(C.byref(cfg.c), C.byref(sp), 4, C.byref(small)) == abi.FTL_OK
+    assert 0 < small.value <= ws.value    # persistent wavefronts: the scratch does not grow past their number
+
+
+def test_astar_rejected_before_the_device():
+    lib = _lib.load()
+    cfg = _episode_cfg("Bastar_s1_chase")
+    sp = scen_params(cfg)
+    assert sp.planner == 1
+    with pytest.raises(NotImplementedError):
+        generate_scenarios_device(cfg, [0, 1, 2], "cuda:0")
+    ws = C.c_size_t(0)
+    assert lib.ftl_generate_scenarios_device_workspace(C.byref(cfg.c), C.byref(sp), 8, C.byref(ws)) == abi.FTL_E_UNSUPPORTED
+    assert _call(lib, cfg, sp, 8) == abi.FTL_E_UNSUPPORTED
+
+
+def test_invalid_arguments():
+    lib = _lib.load()
+    cfg, _, _ = _pool_cfg()
+    sp = scen_params(cfg)
+    ws = C.c_size_t(0)
+    assert lib.ftl_generate_scenarios_device_workspace(None, C.byref(sp), 8, C.byref(ws)) == abi.FTL_E_INVALID
+    assert lib.ftl_generate_scenarios_device_workspace(C.byref(cfg.c), C.byref(sp), 8, None) == abi.FTL_E_INVALID
+    assert lib.ftl_generate_scenarios_device_workspace(C.byref(cfg.c), C.byref(sp), -1, C.byref(ws)) == abi.FTL_E_INVALID
+    assert _call(lib, None, sp, 8) == abi.FTL_E_INVALID
+    assert _call(lib, cfg, sp, -1) == abi.FTL_E_INVALID
+    out = abi.Scenarios()
+    assert _call(lib, cfg, sp, 8, out=out) == abi.FTL_E_INVALID                     # null seeds / arrays / workspace
+    fake = C.c_void_p(16)                                                          # never dereferenced: the checks come first
+    for k, _ in abi.Scenarios._fields_[2:]:
+        setattr(out, k, 16)
+    assert _call(lib, cfg, sp, 8, out=out, status=fake, ws=fake, ws_bytes=64, seeds=fake) == abi.FTL_E_INVALID   # workspace too small
+    bad = scen_params(cfg)
+    bad.step_grid = 0
+    assert _call(lib, cfg, bad, 8, out=out, status=fake, ws=fake, ws_bytes=1 << 40, seeds=fake) == abi.FTL_E_INVALID
+    bad = scen_params(cfg)
+    bad.obstacle_number += 1                                                       # n_static no longer matches
+    assert _call(lib, cfg, bad, 8, out=out, status=fake, ws=fake, ws_bytes=1 << 40, seeds=fake) == abi.FTL_E_INVALID
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- GPU
+def _compare_with_host(cfg, seeds):
+    d = generate_scenarios_device(cfg, seeds, "cuda:0")
+    d = {k: v.cpu().numpy() for k, v in d.items()}
+    h = generate_scenarios(cfg, seeds, n_threads=16)
+    assert np.array_equal(d["status"], h["status"]), np.nonzero(d["status"] != h["status"])[0][:10]
+    assert np.array_equal(d["usable"], h["usable"])
+    for k in KEYS_EXACT:
+        assert np.array_equal(d[k], h[k]), (k, np.nonzero((d[k] != h[k]).reshape(len(seeds), -1).any(1))[0][:10])
+    u = np.nonzero(h["usable"])[0]
+    print("usable %d / %d, every array bit-equal to the host generator's" % (len(u), len(seeds)))
+    return d, h
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", HOST_CONFIGS)
+def test_device_matches_host_generator(name):
+    cfg = _episode_cfg(name)
+    d, h = _compare_with_host(cfg, SEEDS)
+    assert h["usable"].sum() > 0.3 * len(SEEDS)
+
+
+@pytest.mark.gpu
+def test_device_matches_host_generator_synthetic_grid():
+    """A size no golden episode uses (1200 x 800, step_grid 8): against the host generator only."""
+    cfg, _, _ = _pool_cfg(game_width=1200, game_height=800, step_grid=8)
+    d, h = _compare_with_host(cfg, SEEDS)
+    assert h["usable"].sum() > 100
+
+
+@pytest.mark.gpu
+def test_device_matches_reference_pool():
+    cfg, z, meta = _pool_cfg()
+    cfg = config_for(dict(kwargs=meta["kwargs"], post=None), scen_route_len=int(z["route_len"].max()))
+    g = {k: v.cpu().numpy() for k, v in generate_scenarios_device(cfg, np.arange(meta["n_seeds"]), "cuda:0").items()}
+    assert sorted(np.nonzero(g["usable"])[0].tolist()) == sorted(z["seed"].tolist())
+    same_route = 0
+    R = cfg.n_robots
+    for i, s in enumerate(z["seed"]):
+        assert np.array_equal(g["static_rects"][s], z["static_rects"][i]), ("walls/rocks", s)
+        rl = z["route_len"][i]
+        r_ref, r_got = z["route"][i, :rl].astype(np.float64), g["route"][s, :g["route_len"][s]]
+        assert np.array_equal(r_ref[0], r_got[0]) and np.abs(r_ref[-1] - r_got[-1]).max() <= 10, ("route ends", s)
+        assert abs(_route_cost(r_ref) - _route_cost(r_got)) < 1e-6, ("route cost", s)
+        assert np.array_equal(g["robot_pos"][s][[0] + list(range(2, R))], z["robot_pos"][i][[0] + list(range(2, R))])
+        if len(r_ref) == len(r_got) and np.array_equal(r_ref, r_got):
+            same_route += 1
+            assert np.array_equal(g["robot_pos"][s], z["robot_pos"][i]), ("robots", s)
+            assert np.array_equal(g["robot_dir"][s], z["robot_dir"][i]), ("directions", s)
+            assert np.array_equal(g["robot_rect"][s], z["robot_rect"][i].astype(np.int32)), ("hitboxes", s)
+            n = z["init_traj_len"][i]
+            assert g["init_traj_len"][s] == n and np.array_equal(g["init_traj"][s, :n], z["init_traj"][i, :n]), ("trajectory", s)
+    assert same_route >= 0.99 * len(z["seed"]), same_route
+
+
+@pytest.mark.gpu
+def test_device_matches_reference_episode_resets():
+    checked = 0
+    for name in episode_names():
+        z, meta = load_episode(name)
+        kw = meta["kwargs"]
+        if kw.get("path_finding_algorythm") == "astar":
+            continue
+        cfg = config_for(meta, scen_route_len=len(z["scen:route"]))
+        g = {k: v.cpu().numpy() for k, v in generate_scenarios_device(cfg, [meta["seed"]], "cuda:0").items()}
+        ref = scenario_arrays(z)
+        assert np.array_equal(g["static_rects"][0], ref["static_rects"]), name
+        if kw.get("trajectory") is not None:
+            assert g["usable"][0]
+            assert np.array_equal(g["route"][0, :g["route_len"][0]], ref["route"]), name
+            assert np.array_equal(g["robot_pos"][0], ref["robot_pos"]) and np.array_equal(g["robot_dir"][0], ref["robot_dir"]), name
+            assert np.array_equal(g["robot_rect"][0], ref["robot_rect"]), name
+            n = len(ref["init_traj"])
+            assert g["init_traj_len"][0] == n and np.array_equal(g["init_traj"][0, :n], ref["init_traj"]), name
+            checked += 1
+            continue
+        assert bool(g["status"][0] & abi.SCEN_FOUND) == bool(z["scen:found_target_point"]), name
+        if not bool(z["scen:found_target_point"]):
+            continue
+        assert g["usable"][0], name
+        r_got = g["route"][0, :g["route_len"][0]]
+        assert abs(_route_cost(ref["route"]) - _route_cost(r_got)) < 1e-6, name
+        if len(r_got) == len(ref["route"]) and np.array_equal(r_got, ref["route"]):
+            assert np.array_equal(g["robot_pos"][0], ref["robot_pos"]), name
+            assert np.array_equal(g["robot_dir"][0], ref["robot_dir"]), name
+            assert np.array_equal(g["robot_rect"][0], ref["robot_rect"]), name
+            n = len(ref["init_traj"])
+            assert g["init_traj_len"][0] == n and np.array_equal(g["init_traj"][0, :n], ref["init_traj"]), name
+        checked += 1
+    assert checked >= 30, checked
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("parts,K", [(1, 2), (2, 2), (1, 3), (2, 3)])
+def test_device_ring_refills_while_stepping(parts, K):
+    """DeviceScenarioRing: segments generated on the side stream while the batch steps, the window moved at step boundaries.  A plain batch
+    that gets the SAME segments written synchronously at the SAME steps produces identical outputs at every step, and every recorded
+    segment is the compacted device generator output of its recorded seed range."""
+    import torch
+    from continiousenvironment_follower_leader_amd.scenario import DeviceScenarioRing
+    from continiousenvironment_follower_leader_amd.vec_game import PipelinedVecGame, ScenarioPool, VecGame
+    cfg, _, _ = _pool_cfg(max_steps=120, warm_start=10)
+    n, S, T = 512, 96, 90
+    ms, mr = cfg.c.follower.max_speed, cfg.c.follower.max_rotation_speed
+    gen = torch.Generator(device="cpu"); gen.manual_seed(7)
+    acts = [torch.stack([(0.5 + 0.5 * torch.rand(n, generator=gen, dtype=torch.float64)) * ms,
+                         torch.clamp(torch.randn(n, generator=gen, dtype=torch.float64) * 0.2 * mr, -mr, mr)], 1).to("cuda:0") for _ in range(T)]
+    ring = DeviceScenarioRing(cfg, S, "cuda:0", segments=K, seed_base=30000 + 1000 * K, record=True)
+    assert ring.horizon == 120 // 10 + 2
+    a = VecGame(n, device="cuda:0", config=cfg) if parts == 1 else PipelinedVecGame(n, parts=parts, device="cuda:0", config=cfg)
+    ring.attach(a)
+    idx = (torch.arange(n) % S).to(torch.int32)
+    a.reset(idx)
+    outs = []
+    for t in range(T):
+        ring.poll(a, t)
+        a.step(acts[t], auto_reset=True)
+        if parts > 1:
+            a.join()
+        outs.append((a.obs_num.clone(), a.lasers.clone(), a.reward.clone(), a.done.clone(), a.status.clone()))
+        if t % 10 == 9:
+            torch.cuda.synchronize()
+    ring.close()
+    assert ring.swaps >= 3, ring.swaps
+    assert a.error_report() == (0, 0)
+    hist = list(ring.history)
+    lo = hist[0][2][0]
+    for (_, _, (l, h), arrays) in hist:                   # consecutive seed ranges, each = the usable scenarios of its range in order
+        assert l == lo and h > l
+        lo = h
+        p = ScenarioPool.generate_on_device(cfg, np.arange(l, h), "cuda:0")
+        assert p.n == S
+        for k, v in arrays.items():
+            assert torch.equal(v, p.t[k]), k
+
+    b = VecGame(n, device="cuda:0", config=cfg)
+    pool = ScenarioPool.empty(cfg, K * S, "cuda:0")
+    pool.write(0, hist[0][3]); torch.cuda.synchronize()
+    b.load_scenarios(pool); b.set_reset_window(0, S, ring._stride(b))
+    b.reset(idx)
+    for t in range(T):
+        for (st, seg, _, arrays) in hist[1:]:
+            if st == t:
+                pool.write(seg * S, arrays); torch.cuda.synchronize()
+                b.set_reset_window(seg * S, S, ring._stride(b))
+        b.step(acts[t], auto_reset=True)
+        for x, y in zip(outs[t], (b.obs_num, b.lasers, b.reward, b.done, b.status)):
+            assert torch.equal(x, y), t
+    assert torch.equal(a.state_field("env_int")[:, abi.EI_SCEN], b.state_field("env_int")[:, abi.EI_SCEN])
+    assert b.error_report() == (0, 0)
+    a.close(); b.close()
