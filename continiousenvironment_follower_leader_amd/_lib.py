@@ -72,6 +72,7 @@ def load():
     lib.ftl_reset.argtypes = [vp, vp, vp, C.POINTER(abi.Outputs), vp]
     lib.ftl_step.argtypes = [vp, vp, C.POINTER(abi.Outputs), u32, vp]
     lib.ftl_step_encoded.argtypes = [vp, vp, i32, C.POINTER(abi.Outputs), u32, vp]
+    lib.ftl_step_final.argtypes = [vp, vp, i32, C.POINTER(abi.Outputs), C.POINTER(abi.FinalOutputs), u32, vp]
     lib.ftl_kernel_timing.argtypes = [vp, i32]
     lib.ftl_kernel_times.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(i32)]
     lib.ftl_episode_metrics.argtypes = [vp, vp, vp, u32, vp]
@@ -97,14 +98,14 @@ def load():
     lib.ftl_gz_reset.argtypes = [vp, vp, vp]
     lib.ftl_gz_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ftl_gz_state_field.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(i32)]
-    for n in ("ftl_sizeof_config", "ftl_sizeof_scenarios", "ftl_sizeof_outputs"):
+    for n in ("ftl_sizeof_config", "ftl_sizeof_scenarios", "ftl_sizeof_outputs", "ftl_sizeof_final_outputs"):
         getattr(lib, n).restype = C.c_size_t
     _LIB = lib
     return lib
 
 
 EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl_state_bytes", "ftl_bind_state",
-           "ftl_state_field", "ftl_load_scenarios", "ftl_set_reset_window", "ftl_tune", "ftl_reset", "ftl_step", "ftl_step_encoded", "ftl_last_error", "ftl_generate_scenarios",
+           "ftl_state_field", "ftl_load_scenarios", "ftl_set_reset_window", "ftl_tune", "ftl_reset", "ftl_step", "ftl_step_encoded", "ftl_step_final", "ftl_last_error", "ftl_generate_scenarios",
            "ftl_generate_scenarios_device_workspace", "ftl_generate_scenarios_device",
            "ftl_episode_metrics", "ftl_kernel_timing", "ftl_kernel_times",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",

@@ -24,6 +24,7 @@ FTL_ERR_LIDAR_OVERFLOW = 32
 FTL_ERR_BAD_ACTION = 64
 FTL_ACTION_BOX2, FTL_ACTION_DISCRETE, FTL_ACTION_TURN = 0, 1, 2
 FTL_STEP_AUTO_RESET = 1
+FTL_STEP_NEXT_RESET = 4
 FTL_N_METRICS = 8
 FTL_METRICS_CLEAR = 1
 (M_EPISODES, M_RETURN_SUM, M_FRAMES_SUM, M_SUCCESS, M_CRASH, M_LOW_REWARD, M_TOO_FAR, M_TIMEOUT) = range(8)
@@ -152,3 +153,9 @@ class Outputs(C.Structure):
 
 # ftl_tune keys (include/ftl.h)
 FTL_TUNE_COSCHEDULED_ENVS, FTL_TUNE_REGROUP_EVERY, FTL_TUNE_TWO_STREAMS = 0, 1, 2
+
+
+class FinalOutputs(C.Structure):
+    """ftl_final_outputs: the terminal rows and the ended / restarted masks of ftl_step_final."""
+    _fields_ = [("obs_num", C.c_void_p), ("lasers", C.c_void_p), ("target", C.c_void_p), ("policy_obs", C.c_void_p),
+                ("ended", C.c_void_p), ("restarted", C.c_void_p)]

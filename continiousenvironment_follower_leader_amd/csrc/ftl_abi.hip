@@ -117,6 +117,7 @@ size_t ftl_sizeof_config(void) { return sizeof(ftl_config); }
 size_t ftl_sizeof_scenarios(void) { return sizeof(ftl_scenarios); }
 size_t ftl_sizeof_outputs(void) { return sizeof(ftl_outputs); }
 size_t ftl_sizeof_scen_params(void) { return sizeof(ftl_scen_params); }
+size_t ftl_sizeof_final_outputs(void) { return sizeof(ftl_final_outputs); }
 
 // Lanes per env of the frame kernel (4 or 8) and everything that follows from the envs per wavefront: the LDS layout of the kernel and the
 // slot count of the cost sort's rule.  Configs with more than 2 dynamic obstacles need 8 lanes.  The others take 8 as well -- 8 envs per
@@ -447,6 +448,7 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
         while (h->tev.size() < h->tev_used + 5) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) return fail(FTL_E_DEVICE, "hipEventCreate"); h->tev.push_back(ev); }
         tev = h->tev.data() + h->tev_used; h->tev_used += 5;
     }
+    const bool xr = (call.flags & (FTL_STEP_NEXT_RESET | FTL_CALL_DEFER_RESET | FTL_CALL_FINISH)) != 0 || call.ended || call.restarted;
     auto launch_range = [&](int part, int parts, hipStream_t s) {
         const int epw0 = FTL_WAVE / h->G;
         const int n_groups = (h->P.n_envs + epw0 - 1) / epw0;
@@ -458,7 +460,15 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
         size_t lds = (size_t)h->P.fr_lds + h->lds_pad;
         const dim3 grid((count + epw - 1) / epw), block(FTL_WAVE);
         if (tev) (void)hipEventRecord(tev[0], s);
-        if (h->G == 4) {
+        if (xr) {           // next-step restarts, the deferred reset of ftl_step_final and its masks: the instantiations that carry them
+            if (h->G == 4) {
+                if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<4, true, true>), grid, block, lds, s, h->dP, c2);
+                else hipLaunchKernelGGL((ftl_frames_group_kernel<4, false, true>), grid, block, lds, s, h->dP, c2);
+            } else {
+                if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<8, true, true>), grid, block, lds, s, h->dP, c2);
+                else hipLaunchKernelGGL((ftl_frames_group_kernel<8, false, true>), grid, block, lds, s, h->dP, c2);
+            }
+        } else if (h->G == 4) {
             if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<4, true>), grid, block, lds, s, h->dP, c2);
             else hipLaunchKernelGGL((ftl_frames_group_kernel<4, false>), grid, block, lds, s, h->dP, c2);
         } else {
@@ -508,8 +518,9 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
     }
     if (tev) (void)hipEventRecord(tev[3], (hipStream_t)stream);
     // the frame kernel left every env's cost class for its next step: rebuild the slot -> env map.  The classes are stable
-    // from step to step unless the frame count is random, so every second launch is enough then.
-    if (h->regroup && (h->P.cfg.rand_fps_hi > 0 || call.mode == 1 || (h->rg_launches++ % h->rg_every) == 0)) {
+    // from step to step unless the frame count is random, so every second launch is enough then.  (The reset pass of ftl_step_final
+    // follows a step that has just rebuilt or kept the map: the few envs it re-initialises move with the next rebuild.)
+    if (h->regroup && !(call.flags & FTL_CALL_FINISH) && (h->P.cfg.rand_fps_hi > 0 || call.mode == 1 || (h->rg_launches++ % h->rg_every) == 0)) {
         const unsigned nb = (unsigned)((h->P.n_envs + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK);
         int* tot = h->rg_tot + (h->rg_parity & 1u) * FTL_NKEYS, *tot_next = h->rg_tot + ((h->rg_parity + 1u) & 1u) * FTL_NKEYS;
         h->rg_parity++;
@@ -536,6 +547,7 @@ int ftl_reset(ftl_handle* h, const int32_t* scen_idx, const uint8_t* mask, const
     if (rc) return rc;
     if (out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
     FtlCall call; call.mode = 1; call.scen_idx = scen_idx; call.mask = mask; call.out = *out; call.action = nullptr; call.flags = 0; call.action_kind = FTL_ACTION_BOX2; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
+    call.ended = nullptr; call.restarted = nullptr;
     return launch(h, call, stream);
 }
 
@@ -544,15 +556,41 @@ int ftl_step(ftl_handle* h, const double* action, const ftl_outputs* out, uint32
 }
 
 int ftl_step_encoded(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, uint32_t flags, void* stream) {
+    return ftl_step_final(h, action, encoding, out, nullptr, flags, stream);
+}
+
+int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, const ftl_final_outputs* fin,
+                   uint32_t flags, void* stream) {
     if (!h || !action) return fail(FTL_E_INVALID, "null argument");
+    flags &= FTL_STEP_AUTO_RESET | FTL_STEP_NEXT_RESET;       // (other bits were always ignored; the kernel's internal ones stay internal)
+    if ((flags & FTL_STEP_AUTO_RESET) && (flags & FTL_STEP_NEXT_RESET)) return fail(FTL_E_INVALID, "FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET exclude each other");
     if (encoding < FTL_ACTION_BOX2 || encoding > FTL_ACTION_TURN) return fail(FTL_E_INVALID, "unknown action encoding");
     if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
     if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
     int rc = check_out(h, out);
     if (rc) return rc;
     if (out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
+    const bool same_step = fin && (flags & FTL_STEP_AUTO_RESET);
+    if (fin && (!fin->ended || !fin->restarted)) return fail(FTL_E_INVALID, "ftl_final_outputs: ended / restarted missing");
+    if (same_step && (!fin->obs_num || !fin->target || (h->P.lasers_len > 0 && !fin->lasers)))
+        return fail(FTL_E_INVALID, "ftl_final_outputs: obs_num / lasers / target missing (needed under FTL_STEP_AUTO_RESET)");
+    if (same_step && fin->policy_obs && !out->policy_obs) return fail(FTL_E_INVALID, "ftl_final_outputs.policy_obs needs ftl_outputs.policy_obs");
     FtlCall call; call.mode = 0; call.action = (const double*)action; call.action_kind = encoding; call.out = *out; call.flags = flags; call.scen_idx = nullptr; call.mask = nullptr; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
-    return launch(h, call, stream);
+    call.ended = fin ? fin->ended : nullptr; call.restarted = fin ? fin->restarted : nullptr;
+    if (!same_step) return launch(h, call, stream);
+    // same-step: the step defers the reset of the envs that finish (their terminal state gets the usual sensor scans), their terminal rows
+    // go to `fin`, then a reset pass over fin->ended re-initialises them as the in-kernel auto-reset would have -- all on `stream`, after
+    // the step's join when the handle runs two streams
+    call.flags = (flags & ~(uint32_t)FTL_STEP_AUTO_RESET) | FTL_CALL_DEFER_RESET;
+    rc = launch(h, call, stream);
+    if (rc) return rc;
+    const int n = h->P.n_envs, epb = FTL_FC_THREADS;                  // envs per workgroup (64 per wavefront)
+    const int pol_len = (fin->policy_obs && out->policy_obs) ? h->P.pol_h * h->P.pol_width : 0;
+    hipLaunchKernelGGL(ftl::ftl_final_copy_kernel, dim3((unsigned)((n + epb - 1) / epb)), dim3(FTL_FC_THREADS), 0, (hipStream_t)stream,
+                       *out, *fin, n, h->P.lasers_len, pol_len);
+    FtlCall rcall = call;
+    rcall.mode = 1; rcall.flags = FTL_CALL_FINISH; rcall.mask = fin->ended; rcall.action = nullptr; rcall.ended = nullptr; rcall.restarted = nullptr;
+    return launch(h, rcall, stream);
 }
 
 int ftl_kernel_timing(ftl_handle* h, int32_t enable) {

@@ -88,7 +88,12 @@ struct FtlCall {
     int32_t win_base, win_count, win_stride;   // pool entries the auto-reset draws from and the step of its walk (ftl_set_reset_window)
     int32_t part, parts, epw;          // this launch covers the slot groups (epw consecutive slots = one frame-kernel wavefront)
                                        // part, part + parts, part + 2*parts, ... of the slot -> env permutation
+    uint8_t* ended; uint8_t* restarted;   // ftl_step_final: per-env masks written by the frame kernel (NULL: not asked for)
 };
+// internal bits of FtlCall::flags next to the public FTL_STEP_* (include/ftl.h); only the frame kernel's XR instantiations read them
+#define FTL_CALL_DEFER_RESET (1u << 30)   // step: an env that finishes records its episode as under FTL_STEP_AUTO_RESET but is not re-initialised
+#define FTL_CALL_FINISH (1u << 29)        // reset pass after a deferring step: scenario from the reset window's walk, auto-reset bookkeeping,
+                                          // reward / done / status left as the step wrote them
 
 // field `f0` (its address inside record 0) of env `env`
 template <typename T>

@@ -155,9 +155,14 @@ class VecGame:
     ``reset(scen_idx, mask)`` / ``step(action, auto_reset)`` return views of persistent device tensors:
     ``obs_num`` f32[N,10] (numerical_features, ENV:1793-1802), ``lasers`` f32[N, sum_k H_k*N_k] (one
     ``[H_k, N_k]`` block per ray sensor, ``laser_view(name)``), ``target`` f64[N,2], ``reward`` f64[N],
-    ``done`` u8[N], ``status`` u8[N,3] (mission/agent/leader codes of ``abi.MISSION/AGENT/LEADER``)."""
+    ``done`` u8[N], ``status`` u8[N,3] (mission/agent/leader codes of ``abi.MISSION/AGENT/LEADER``).
 
-    def __init__(self, n_envs, device="cuda:0", config: GameConfig = None, policy_obs=False, _outputs=None, **game_kwargs):
+    ``final_obs=True`` adds the persistent tensors of ``ftl_step_final``, passed on every step except ``auto_reset=True``:
+    ``final_obs_num``, ``final_lasers``, ``final_target`` (+ ``final_policy_obs`` with ``policy_obs``) hold the terminal observation
+    of the envs whose episode ended in the last ``auto_reset="same_step"`` step (other rows keep older values); ``ended`` u8[N] marks
+    the envs whose episode ended in the last step, ``restarted`` u8[N] the envs it re-initialised (``terminated_truncated()``)."""
+
+    def __init__(self, n_envs, device="cuda:0", config: GameConfig = None, policy_obs=False, _outputs=None, final_obs=False, **game_kwargs):
         self.cfg = config if config is not None else make_config(**game_kwargs)
         self.n = int(n_envs)
         self.device = torch.device(device)
@@ -204,6 +209,22 @@ class VecGame:
                 raise ValueError("policy_obs needs the same max_prev_obs on every sensor it concatenates (wrappers.py:207, 217 assert it)")
             self.policy_obs = out("policy_obs", hs.pop(), sum(l.width for l in sel), dtype=torch.float32)
             o.policy_obs = self.policy_obs.data_ptr()
+        self.final_obs = bool(final_obs)
+        self._fin = None
+        if self.final_obs:                     # ftl_final_outputs: terminal rows + ended / restarted masks
+            self.final_obs_num = out("final_obs_num", abi.FTL_OBS_NUM, dtype=torch.float32)
+            self.final_lasers = out("final_lasers", L, dtype=torch.float32)
+            self.final_target = out("final_target", 2, dtype=torch.float64)
+            self.final_policy_obs = None
+            if self.policy_obs is not None:
+                self.final_policy_obs = out("final_policy_obs", *self.policy_obs.shape[1:], dtype=torch.float32)
+            self.ended = out("ended", dtype=torch.uint8)
+            self.restarted = out("restarted", dtype=torch.uint8)
+            f = abi.FinalOutputs()
+            f.obs_num, f.lasers, f.target = self.final_obs_num.data_ptr(), self.final_lasers.data_ptr(), self.final_target.data_ptr()
+            f.policy_obs = self.final_policy_obs.data_ptr() if self.final_policy_obs is not None else None
+            f.ended, f.restarted = self.ended.data_ptr(), self.restarted.data_ptr()
+            self._fin = f
         self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, **z)
         self._errors = torch.zeros(2, dtype=torch.int32, **z)
         self._out = o
@@ -266,14 +287,42 @@ class VecGame:
         """action: f64[N,2] device tensor = (speed px/frame, signed rotation deg/frame) (ENV:927-933).  With
         ``discrete_action_space=True`` an integer tensor [N] (or [N,1]) of Discrete(5) indices, with ``constant_follower_speed=True`` a
         float tensor [N] (or [N,1]) of rotations: both are decoded on the device as ENV:909-925 does (``ftl_step_encoded``).
+        ``auto_reset``: False -- finished envs stay done; True -- they are re-initialised inside this step, the outputs keep the terminal
+        reward / done / status and the new episode's observation (FTL_STEP_AUTO_RESET); ``"same_step"`` -- True plus the terminal
+        observations in the final buffers (needs ``final_obs=True``); ``"next_step"`` -- this step returns the terminal observation, an env
+        that is done on entry is re-initialised instead of stepped (its action ignored; reward 0, done 0, status 0: FTL_STEP_NEXT_RESET).
         ``check_errors=True`` synchronises and raises what the reference would have raised in any env (``raise_on_errors``);
         the default leaves the per-env sticky error words for ``error_report()`` so that the step stays asynchronous."""
         action, enc = self._encode_action(action, self.n)
-        flags = abi.FTL_STEP_AUTO_RESET if auto_reset else 0
-        _lib.check(self.lib.ftl_step_encoded(self.h, action.data_ptr(), enc, C.byref(self._out), flags, self._stream()), self.lib)
+        flags, fin = self._step_mode(auto_reset)
+        _lib.check(self.lib.ftl_step_final(self.h, action.data_ptr(), enc, C.byref(self._out), fin, flags, self._stream()), self.lib)
         if check_errors:
             self.raise_on_errors(live_errors)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
+
+    def _step_mode(self, auto_reset):
+        """(FTL_STEP_* flags, ftl_final_outputs pointer or None) of a ``step(auto_reset=...)`` value."""
+        fin = C.byref(self._fin) if self._fin is not None else None
+        if not isinstance(auto_reset, str):
+            if auto_reset:                     # today's meaning exactly: no final buffers
+                return abi.FTL_STEP_AUTO_RESET, None
+            return 0, fin
+        if auto_reset == "same_step":
+            if fin is None:
+                raise ValueError('auto_reset="same_step" needs the final buffers: VecGame(..., final_obs=True)')
+            return abi.FTL_STEP_AUTO_RESET, fin
+        if auto_reset == "next_step":
+            return abi.FTL_STEP_NEXT_RESET, fin
+        raise ValueError('auto_reset must be False, True, "same_step" or "next_step" (got %r)' % (auto_reset,))
+
+    def terminated_truncated(self):
+        """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
+        truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap
+        continues from the terminal observation), terminated = ended and not truncated.  The statuses are the reference's own: it tests
+        the step limit after the crash tests of the frame, so a crash in the frame that reaches max_steps reads as a time-out."""
+        if not self.final_obs:
+            raise ValueError("terminated_truncated() needs VecGame(..., final_obs=True)")
+        return _terminated_truncated(self.ended, self.status)
 
     def _encode_action(self, action, n):
         """(tensor to hand to ftl_step_encoded, FTL_ACTION_* encoding) for an action of ``n`` envs of this config (ENV:909-925)."""
@@ -403,6 +452,12 @@ class VecGame:
         return hist, corr
 
 
+def _terminated_truncated(ended, status):
+    ended = ended.bool()
+    truncated = ended & (status[:, 0] == abi.MISSION.index("finished_by_time"))
+    return ended & ~truncated, truncated
+
+
 class PipelinedVecGame:
     """A batch of N envs stepped as ``parts`` independent sub-batches, each on its own HIP stream of this process.
 
@@ -419,7 +474,7 @@ class PipelinedVecGame:
     and gets ``VecGame``'s throughput back; a training loop keeps them apart by consuming part k's rows (``rows(k)``) on ``stream(k)``
     and feeding ``step_part(k, action_k)`` -- the double-buffered sampling loop of asynchronous RL frameworks."""
 
-    def __init__(self, n_envs, parts=2, device="cuda:0", config: GameConfig = None, policy_obs=False, **game_kwargs):
+    def __init__(self, n_envs, parts=2, device="cuda:0", config: GameConfig = None, policy_obs=False, final_obs=False, **game_kwargs):
         import dataclasses
         from .shard import shard_range
         cfg = config if config is not None else make_config(**game_kwargs)
@@ -437,12 +492,20 @@ class PipelinedVecGame:
             if len(hs) != 1:
                 raise ValueError("policy_obs needs the same max_prev_obs on every sensor it concatenates (wrappers.py:207, 217 assert it)")
             outs["policy_obs"] = torch.zeros(self.n, hs.pop(), sum(l.width for l in sel), dtype=torch.float32, **z)
+        self.final_obs = bool(final_obs)
+        if self.final_obs:                     # the final buffers of VecGame(final_obs=True), rows of shared tensors like the outputs
+            outs.update(final_obs_num=torch.zeros_like(outs["obs_num"]), final_lasers=torch.zeros_like(outs["lasers"]),
+                        final_target=torch.zeros_like(outs["target"]), ended=torch.zeros_like(outs["done"]),
+                        restarted=torch.zeros_like(outs["done"]))
+            if "policy_obs" in outs:
+                outs["final_policy_obs"] = torch.zeros_like(outs["policy_obs"])
         self.shards = [shard_range(self.n, k, parts) for k in range(parts)]
         self.games, self.streams = [], []
         for sh in self.shards:
             ck = dataclasses.replace(cfg, c=abi.Config.from_buffer_copy(cfg.c))
             ck.c.env_id_base = cfg.c.env_id_base + sh.lo          # per-env random streams are keyed by the global env index
-            g = VecGame(sh.n, device=self.device, config=ck, policy_obs=policy_obs, _outputs={k: v[sh.lo:sh.hi] for k, v in outs.items()})
+            g = VecGame(sh.n, device=self.device, config=ck, policy_obs=policy_obs, _outputs={k: v[sh.lo:sh.hi] for k, v in outs.items()},
+                        final_obs=final_obs)
             if parts > 1:
                 # the parts take the role of the handle's own two-stream mode (random_frames_per_step), without its join; the envs are sorted
                 # by cost when the WHOLE batch oversubscribes the device, on a staler order than a lone handle's (259 against 255 M env-steps/s)
@@ -453,6 +516,8 @@ class PipelinedVecGame:
             setattr(self, k, v)
         if "policy_obs" not in outs:
             self.policy_obs = None
+        if self.final_obs and "final_policy_obs" not in outs:
+            self.final_policy_obs = None
         self.pool = None
         self._serial = False
         self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, **z)
@@ -519,7 +584,8 @@ class PipelinedVecGame:
         return self.obs_num, self.lasers
 
     def step_part(self, k, action, auto_reset=False):
-        """One step of part k on its stream; ``action`` = the rows of part k (any layout ``VecGame.step`` takes)."""
+        """One step of part k on its stream; ``action`` = the rows of part k (any layout ``VecGame.step`` takes); ``auto_reset`` as
+        ``VecGame.step`` (the final buffers' rows of part k are valid on ``stream(k)``)."""
         with self._on(k):
             self.games[k].step(action, auto_reset=auto_reset)
             if not self._serial:
@@ -531,19 +597,26 @@ class PipelinedVecGame:
         g0 = self.games[0]
         action, enc = g0._encode_action(action, self.n)            # checked / decoded once for the whole batch, then handed over by row range
         self._keep_action = action
-        flags = abi.FTL_STEP_AUTO_RESET if auto_reset else 0
+        modes = [g._step_mode(auto_reset) for g in self.games]      # (validated before anything is enqueued)
         cur = torch.cuda.current_stream(self.device)
         base, row = action.data_ptr(), action.element_size() * (2 if enc == abi.FTL_ACTION_BOX2 else 1)
         if not self._serial:
             self._ev.record(cur)
-        for g, sh, stream, sptr in zip(self.games, self.shards, self.streams, self._stream_ptrs):
+        for g, sh, stream, sptr, (flags, fin) in zip(self.games, self.shards, self.streams, self._stream_ptrs, modes):
             if self._serial:
                 sptr = C.c_void_p(cur.cuda_stream)
             else:
                 stream.wait_event(self._ev)
                 action.record_stream(stream)       # (the caller may drop the tensor right away: its memory must outlive the part's read)
-            _lib.check(g.lib.ftl_step_encoded(g.h, base + sh.lo * row, enc, C.byref(g._out), flags, sptr), g.lib)
+            _lib.check(g.lib.ftl_step_final(g.h, base + sh.lo * row, enc, C.byref(g._out), fin, flags, sptr), g.lib)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
+
+    def terminated_truncated(self):
+        """``VecGame.terminated_truncated`` over all rows: computed on the current stream, so ``join()`` first (or take part k's rows
+        of ``ended`` / ``status`` on ``stream(k)``)."""
+        if not self.final_obs:
+            raise ValueError("terminated_truncated() needs PipelinedVecGame(..., final_obs=True)")
+        return _terminated_truncated(self.ended, self.status)
 
     def episode_metrics(self, clear=False):
         self.join()

@@ -284,6 +284,7 @@ size_t ftl_sizeof_config(void);
 size_t ftl_sizeof_scenarios(void);
 size_t ftl_sizeof_outputs(void);
 size_t ftl_sizeof_scen_params(void);
+size_t ftl_sizeof_final_outputs(void);
 
 
 /* step()/reset() outputs = (obs, reward, done, info) of ENV:945 for n envs, device arrays */
@@ -305,7 +306,28 @@ typedef struct ftl_handle ftl_handle;
 
 /* flags of ftl_step */
 #define FTL_STEP_AUTO_RESET 1u  /* envs that finish are re-initialised from scenario (scen_idx+n_envs) % P inside the
-                                   same launch; outputs keep the terminal reward/done/status, obs are the new episode's */
+                                   same launch; outputs keep the terminal reward/done/status, obs are the new episode's
+                                   (ftl_step_final adds the terminal observations: "same-step" mode, below) */
+#define FTL_STEP_NEXT_RESET 4u  /* "next-step" auto-reset (gymnasium 1.x, EnvPool): the call in which an episode ends returns its terminal
+                                   observation like a step without auto-reset.  An env whose done word is set on ENTRY (whichever call set it)
+                                   is re-initialised instead of stepped -- its action is ignored -- from the reset window's walk
+                                   (ftl_set_reset_window) with the bookkeeping of FTL_STEP_AUTO_RESET: FTL_EI_EPISODES + 1, the episode's error
+                                   bits OR-ed into the sticky word, FTL_EI_RESETS advanced (the same per-env random streams), ep_stats not
+                                   recorded again (the step that set done did).  Its outputs are ftl_reset's for that env: the new episode's first
+                                   observation (initial tracker and ray scans, ENV:541), reward 0, done = the new world's done-at-reset bit, status
+                                   0/0/0.  Every other env steps as without the flag.  Combined with FTL_STEP_AUTO_RESET: FTL_E_INVALID. */
+
+/* Terminal observations of ftl_step_final, device arrays ([n] = one row per env of the handle).  Rows of envs whose `ended` is 0 are
+ * not written. */
+typedef struct ftl_final_outputs {
+    float*   obs_num;    /* [n][10]           the terminal rows of ftl_outputs.obs_num / lasers / target / policy_obs: what the */
+    float*   lasers;     /* [n][lasers_len]   same call without FTL_STEP_AUTO_RESET returns for the env.  Needed (non-NULL) */
+    double*  target;     /* [n][2]            under FTL_STEP_AUTO_RESET only; policy_obs may be NULL (needs out->policy_obs) */
+    float*   policy_obs; /* [n][H][W]         optional */
+    uint8_t* ended;      /* [n]  1: an episode ended in this call (done raised by this call's step; under FTL_STEP_AUTO_RESET every env
+                                 whose outputs carry done = 1) -- always written, for every env */
+    uint8_t* restarted;  /* [n]  1: this call re-initialised the env -- always written, for every env */
+} ftl_final_outputs;
 
 /* Game.__init__ (ENV:45-417): validate + freeze the config. device < 0 is rejected (there is no CPU path). */
 int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle** out);
@@ -370,6 +392,20 @@ int ftl_step(ftl_handle* h, const double* action, const ftl_outputs* out, uint32
  *                                 (constant_follower_speed=True; the speed command of ENV:910-911 is overwritten by ENV:927) */
 enum { FTL_ACTION_BOX2 = 0, FTL_ACTION_DISCRETE = 1, FTL_ACTION_TURN = 2 };
 int ftl_step_encoded(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, uint32_t flags, void* stream);
+
+/* ftl_step_encoded plus the masks / terminal observations an RL loop needs (fin NULL: exactly ftl_step_encoded).
+ *   FTL_STEP_AUTO_RESET ("same-step", SB3 `terminal_observation`, gymnasium `final_obs`): `out` and every state word are bit-identical to
+ *     the same call without `fin`; the rows of fin->obs_num / lasers / target / policy_obs of the ended envs are bit-identical to what a
+ *     step WITHOUT auto-reset returns for them; restarted = ended.  The step defers the reset of the envs that finish, the sensors scan
+ *     their terminal state, ftl_final_copy_kernel copies those rows and a reset pass (the frame kernel's wavefronts without a finished env
+ *     exit at once, the ray / aux kernels skip the others) re-initialises them, on the handle's stream(s) inside this call.
+ *   FTL_STEP_NEXT_RESET or no flag: only fin->ended and fin->restarted are written (the final_* pointers may be NULL); under
+ *     FTL_STEP_NEXT_RESET restarted marks the envs that were done on entry, ended the envs whose episode ended in this call.
+ * Mission status FTL_MISSION_FINISHED_BY_TIME in the terminal status row is the reference's time limit (ENV:1126-1134): a truncation,
+ * which a value bootstrap treats differently from the other statuses.  The reference checks the step limit after the frame's crash
+ * tests, so an env that crashes in the frame that reaches max_steps reports FINISHED_BY_TIME as well. */
+int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, const ftl_final_outputs* fin,
+                   uint32_t flags, void* stream);
 
 /* ---- episode metrics + error report (ENV:941-944 reports overall_reward / step_count at done) --------
  * Every env slot accumulates, at the step in which an episode ends (done set by this step; under FTL_STEP_AUTO_RESET
