@@ -15,6 +15,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_frames_group.hpp"), os.path.join(_PKG, "csrc", "ftl_aux.hpp"), os.path.join(_PKG, "csrc", "ftl_gazebo.hpp"), os.path.join(_ROOT, "include", "ftl_gazebo.h"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp"),
            os.path.join(_PKG, "csrc", "ftl_scenario_dev.hpp"),
            os.path.join(_PKG, "csrc", "ftl_crmath.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_render.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
 # translation units: the device code + C-ABI, and the host-only scenario generator (reset-time, no GPU code)
 UNITS = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp")]
@@ -86,6 +87,11 @@ def load():
     lib.ftl_generate_scenarios_device.argtypes = [C.POINTER(abi.Config), C.POINTER(abi.ScenParams), vp, i32, C.POINTER(abi.Scenarios), vp,
                                                   vp, C.c_size_t, vp]
     lib.ftl_generate_scenarios_device.restype = C.c_int
+    lib.ftl_sizeof_render_params.restype = C.c_size_t
+    lib.ftl_render_workspace.argtypes = [vp, i32, C.POINTER(C.c_size_t)]
+    lib.ftl_render_workspace.restype = C.c_int
+    lib.ftl_render.argtypes = [vp, vp, i32, C.POINTER(abi.RenderParams), vp, C.c_size_t, vp, vp]
+    lib.ftl_render.restype = C.c_int
     # include/ftl_gazebo.h
     lib.ftl_gz_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.ftl_gz_destroy.argtypes = [vp]
@@ -108,6 +114,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_state_field", "ftl_load_scenarios", "ftl_set_reset_window", "ftl_tune", "ftl_reset", "ftl_step", "ftl_step_encoded", "ftl_step_final", "ftl_last_error", "ftl_generate_scenarios",
            "ftl_generate_scenarios_device_workspace", "ftl_generate_scenarios_device",
            "ftl_episode_metrics", "ftl_kernel_timing", "ftl_kernel_times",
+           "ftl_sizeof_render_params", "ftl_render_workspace", "ftl_render",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -159,3 +159,14 @@ class FinalOutputs(C.Structure):
     """ftl_final_outputs: the terminal rows and the ended / restarted masks of ftl_step_final."""
     _fields_ = [("obs_num", C.c_void_p), ("lasers", C.c_void_p), ("target", C.c_void_p), ("policy_obs", C.c_void_p),
                 ("ended", C.c_void_p), ("restarted", C.c_void_p)]
+
+
+# ftl_render (include/ftl.h): layer bits and the image parameters
+RENDER_PATH, RENDER_BOX, RENDER_OBJECTS, RENDER_RECTS, RENDER_SENSORS, RENDER_TARGET = 1, 2, 4, 8, 16, 32
+RENDER_ALL = 63
+
+
+class RenderParams(C.Structure):
+    """ftl_render_params: output size, world pixels per output pixel, world coordinate of output pixel (0, 0)'s corner, layers."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("scale", C.c_float), ("origin_x", C.c_float), ("origin_y", C.c_float),
+                ("layers", C.c_uint32), ("_pad", C.c_int32)]

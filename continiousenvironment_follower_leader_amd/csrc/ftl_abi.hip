@@ -52,6 +52,7 @@ struct ftl_handle {
     hipStream_t side; hipEvent_t ev_fork, ev_join; bool split;
     int win_base, win_count, win_stride; // pool entries the auto-reset draws from (ftl_set_reset_window)
     size_t lds_pad;          // FTL_DEBUG_LDS_PAD (diagnostic: lowers the frame kernel's occupancy without touching the code), read once at create
+    float* last_lasers;      // ftl_outputs.lasers of the last ftl_reset / ftl_step* call (ftl_render's hit points)
 };
 
 namespace {
@@ -156,7 +157,7 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
     h->device = device;
     h->bound = false; h->have_scen = false; h->dP = nullptr; h->dirty = true;
     h->rg_mem = nullptr; h->rg_tot = nullptr; h->rg_parity = 0; h->rg_launches = 0; h->mt_mem = nullptr; h->timing = false; h->tev_used = 0;
-    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr;
+    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->last_lasers = nullptr;
     {   // measured: +9 % with random_frames_per_step (long frame kernels whose tails the other half's ray kernel fills), -1 % with a
         // fixed 10 frames per step -- so it is on for the former only; FTL_SPLIT=0/1 overrides
         const char* sp = getenv("FTL_SPLIT");
@@ -548,6 +549,7 @@ int ftl_reset(ftl_handle* h, const int32_t* scen_idx, const uint8_t* mask, const
     if (out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
     FtlCall call; call.mode = 1; call.scen_idx = scen_idx; call.mask = mask; call.out = *out; call.action = nullptr; call.flags = 0; call.action_kind = FTL_ACTION_BOX2; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
     call.ended = nullptr; call.restarted = nullptr;
+    h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     return launch(h, call, stream);
 }
 
@@ -577,6 +579,7 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
     if (same_step && fin->policy_obs && !out->policy_obs) return fail(FTL_E_INVALID, "ftl_final_outputs.policy_obs needs ftl_outputs.policy_obs");
     FtlCall call; call.mode = 0; call.action = (const double*)action; call.action_kind = encoding; call.out = *out; call.flags = flags; call.scen_idx = nullptr; call.mask = nullptr; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
     call.ended = fin ? fin->ended : nullptr; call.restarted = fin ? fin->restarted : nullptr;
+    h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     if (!same_step) return launch(h, call, stream);
     // same-step: the step defers the reset of the envs that finish (their terminal state gets the usual sensor scans), their terminal rows
     // go to `fin`, then a reset pass over fin->ended re-initialises them as the in-kernel auto-reset would have -- all on `stream`, after
@@ -645,6 +648,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 
 #include "ftl_gazebo.hpp"      // follower-relative tracker / ray sensors (include/ftl_gazebo.h), same translation unit
 #include "ftl_scenario_dev.hpp"  // the scenario generator on the GPU (ftl_generate_scenarios_device), same translation unit
+#include "ftl_render.hpp"        // batched top-down RGB frames (ftl_render), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

@@ -138,8 +138,15 @@ class Game:
         self.done = bool(self._vec.done[0].item())
         return self._obs(), float(self._vec.reward[0].item()), self.done, info
 
-    def render(self, *a, **k):
-        raise NotImplementedError("rendering (pygame display, ENV:1196-1202) is outside the accelerated path")
+    def render(self, custom_message=None, **kwargs):                # ENV:1196-1202
+        """The screen as a numpy uint8 ``[game_height, game_width, 3]`` array when ``return_render_matrix`` (the default), else None.
+        Drawn on the GPU (``VecGame.render``: the layers of the show_* flags, no text -- ``custom_message`` is accepted and not drawn);
+        ``kwargs`` go to ``VecGame.render`` (scale, size, origin, layers)."""
+        if not self.cfg.kwargs.get("return_render_matrix", True):
+            return None
+        if self._vec is None:
+            raise RuntimeError("reset() first")
+        return self._vec.render([0], **kwargs)[0].cpu().numpy()
 
     def close(self):
         if self._vec is not None:

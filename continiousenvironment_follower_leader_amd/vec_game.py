@@ -437,6 +437,49 @@ class VecGame:
                 self._fields[name] = torch.as_strided(self.state[a:a + span + (-span) % esz].view(tdt), (self.n, per.value), (st.value // esz, 1))
         return self._fields[name]
 
+    # ------------------------------------------------------------------ rendering (ftl_render)
+    def render_layers(self):
+        """FTL_RENDER_* bits of the constructor's show_* flags (ENV:267-272); the target ring is always drawn (ENV:1278)."""
+        return _render_layers(self.cfg)
+
+    def render(self, env_ids=None, scale=1.0, size=None, origin=(0, 0), layers=None, out=None):
+        """Top-down RGB frames of envs ``env_ids`` (env indices, repeats allowed; None: all) as a uint8 device tensor ``[k, H, W, 3]``
+        (row-major ``[y][x][rgb]``, the reference's ``render()`` matrix), enqueued on the current stream without a host synchronisation.
+        ``scale``: world pixels per output pixel; ``size``: (W, H) in output pixels (default: the world at this scale); ``origin``: world
+        coordinate of the top-left corner; ``layers``: FTL_RENDER_* bits (None: the constructor's show_* flags); ``out``: a contiguous
+        uint8 ``[k, H, W, 3]`` tensor to write into (e.g. frame t of a ``[T, k, H, W, 3]`` recording).  Reads the state and the outputs of
+        the last reset / step, writes nothing else (include/ftl.h, ftl_render).  Memory: the image is k * H * W * 3 bytes and the cached
+        workspace about k * (route_cap + traj_cap + ...) * 32 bytes (59 KB per env on config B) -- ``env_ids=None`` on a 65,536-env batch
+        asks for 3.9 GB of workspace and, at scale 1, 295 GB of frames: pass the envs to record.  The workspace of the last k is kept
+        until the next call with another k (``release_render_workspace`` frees it)."""
+        ids = _render_ids(env_ids, self.n, self.device)
+        return self._render_ids(ids, scale, size, origin, layers, out)
+
+    def release_render_workspace(self):
+        """Free the workspace ``render`` keeps for its last k (the memory returns to torch's caching allocator)."""
+        self._render_ws = None
+
+    def _render_ids(self, ids, scale, size, origin, layers, out):
+        k = int(ids.numel())
+        if k == 0:
+            raise ValueError("no env to render")
+        rp, (w, h) = _render_params(self.cfg, scale, size, origin, layers)
+        if out is None:
+            out = torch.empty(k, h, w, 3, dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != (k, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous uint8 tensor [%d, %d, %d, 3] on %s" % (k, h, w, self.device))
+        ws = getattr(self, "_render_ws", None)
+        if ws is None or ws[0] != k:           # the workspace of the last k is kept (a recorder renders the same k again and again)
+            nb = C.c_size_t()
+            _lib.check(self.lib.ftl_render_workspace(self.h, k, C.byref(nb)), self.lib)
+            self._render_ws = None                # (the old buffer goes before the new one is allocated)
+            ws = self._render_ws = (k, torch.empty(nb.value, dtype=torch.uint8, device=self.device))
+        buf = ws[1]
+        buf.record_stream(torch.cuda.current_stream(self.device))     # (freed later: not reused before this call's kernels are done)
+        _lib.check(self.lib.ftl_render(self.h, ids.data_ptr(), k, C.byref(rp), buf.data_ptr(), buf.numel(), out.data_ptr(), self._stream()), self.lib)
+        self._keep_render = ids
+        return out
+
     def tracker_obs(self, env):
         """(leader_positions_hist, corridor) of one env, as the reference returns them under the tracker key
         (sensors.py:324-325): hist f64[C,2]; corridor f64[C,2(right/left),2]."""
@@ -450,6 +493,45 @@ class VecGame:
         else:
             hist = self.state_field("hist")[env].view(cap, 2)[idx].cpu().numpy()
         return hist, corr
+
+
+_SHOW_FLAGS = (("show_leader_path_flag", abi.RENDER_PATH), ("show_box_flag", abi.RENDER_BOX), ("show_objects_flag", abi.RENDER_OBJECTS),
+               ("show_rectangles_flag", abi.RENDER_RECTS), ("show_sensors_flag", abi.RENDER_SENSORS))
+
+
+def _render_layers(cfg):
+    bits = abi.RENDER_TARGET
+    for key, bit in _SHOW_FLAGS:
+        if cfg.kwargs.get(key, True):
+            bits |= bit
+    return bits
+
+
+def _render_ids(env_ids, n, device):
+    """int32 device tensor of env indices; ids given on the host are range-checked here (device ids out of range give white frames)."""
+    if env_ids is None:
+        return torch.arange(n, dtype=torch.int32, device=device)
+    if isinstance(env_ids, torch.Tensor) and env_ids.device.type == "cuda":
+        return env_ids.to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+    a = np.asarray(env_ids.cpu() if isinstance(env_ids, torch.Tensor) else env_ids, dtype=np.int64).reshape(-1)
+    if a.size and (a.min() < 0 or a.max() >= n):
+        raise ValueError("env_ids outside [0, %d)" % n)
+    return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+def _render_params(cfg, scale, size, origin, layers):
+    import math
+    scale = float(scale)
+    if not scale > 0 or not math.isfinite(scale):
+        raise ValueError("scale must be positive")
+    if size is None:
+        size = (int(math.ceil(cfg.c.width / scale)), int(math.ceil(cfg.c.height / scale)))
+    w, h = int(size[0]), int(size[1])
+    rp = abi.RenderParams()
+    rp.width, rp.height, rp.scale = w, h, scale
+    rp.origin_x, rp.origin_y = float(origin[0]), float(origin[1])
+    rp.layers = _render_layers(cfg) if layers is None else int(layers)
+    return rp, (w, h)
 
 
 def _terminated_truncated(ended, status):
@@ -650,6 +732,38 @@ class PipelinedVecGame:
             if a.name == name:
                 return self.lasers[:, a.out_offset:a.out_offset + a.out_len].view(self.n, *a.shape)
         raise KeyError(name)
+
+    def render_layers(self):
+        return _render_layers(self.cfg)
+
+    def release_render_workspace(self):
+        for g in self.games:
+            g.release_render_workspace()
+
+    def render(self, env_ids=None, scale=1.0, size=None, origin=(0, 0), layers=None, out=None):
+        """``VecGame.render`` over env indices of the whole batch (ids may span parts, repeats allowed).  A synchronisation point: it
+        joins the parts and reads the ids on the host; the frames are then enqueued on the current stream."""
+        self.join()
+        ids = _render_ids(env_ids, self.n, self.device).cpu().numpy().astype(np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n):
+            raise ValueError("env_ids outside [0, %d)" % self.n)
+        _, (w, h) = _render_params(self.cfg, scale, size, origin, layers)
+        k = len(ids)
+        if out is None:
+            out = torch.empty(k, h, w, 3, dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != (k, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous uint8 tensor [%d, %d, %d, 3] on %s" % (k, h, w, self.device))
+        for g, sh in zip(self.games, self.shards):
+            sel = np.nonzero((ids >= sh.lo) & (ids < sh.hi))[0]
+            if sel.size == 0:
+                continue
+            local = torch.from_numpy((ids[sel] - sh.lo).astype(np.int32)).to(self.device)
+            if sel.size == k:                  # every id in this part: straight into out
+                g._render_ids(local, scale, size, origin, layers, out)
+            else:
+                part = g._render_ids(local, scale, size, origin, layers, None)
+                out.index_copy_(0, torch.from_numpy(sel).to(self.device), part)
+        return out
 
     def kernel_timing(self, enable=True):
         """Measurement hook.  While enabled the parts run one after the other on the CURRENT stream, so that every kernel's HIP events

@@ -434,6 +434,78 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 int ftl_kernel_timing(ftl_handle* h, int32_t enable);
 int ftl_kernel_times(ftl_handle* h, double* ms, int32_t* n_steps);
 
+/* ---- batched top-down RGB frames (render(), ENV:1196-1202, layers of _show_tick ENV:1229-1281) --------------------------------
+ * ftl_render draws k envs of the handle into rgb[k][height][width][3] (uint8, row-major [y][x][r, g, b]: the reference's
+ * np.transpose(pygame.surfarray.array3d(.), (1, 0, 2))).  It reads the state, the scenario pool and the `lasers` output of the last
+ * ftl_reset / ftl_step* call on the handle (that buffer must still be alive) and writes nothing but `rgb` and the caller's workspace:
+ * a render never changes a later step.  env_ids are env indices of the handle (not slots of its cost-sorted permutation); repeats are
+ * allowed; an id outside [0, n_envs) gives a white frame.  Asynchronous on `stream`.
+ *
+ * Coverage rules (what a pixel shows).  Output pixel (i, j) samples the world point origin + (i + 0.5, j + 0.5) * scale.  Positions
+ * and radii scale; stroke widths w do not: they are max(w / scale, 1) output pixels.  In output pixels:
+ *   disc:      distance d to the centre <= r;           ring of width w: r - w < d <= r;
+ *   segment:   distance to the segment (round ends) <= w / 2;
+ *   rotated rectangle (centre c, unit axes u, v = u rotated by +90 deg, half sizes hw, hh): |dot(p - c, u)| <= hw && |dot(p - c, v)| <= hh;
+ *   outline of an integer rect (x, y, w, h): the points inside [x, x + w) x [y, y + h) that lie within one output pixel of its border
+ *              (at scale 1 and origin 0 exactly pygame.draw.rect(width=1)'s pixels).
+ * The last primitive in painter's order that covers a pixel sets its colour; there is no anti-aliasing; uncovered pixels are white.
+ *
+ * Painter's order (layer bits below; FTL_RENDER_TARGET stands for the ring the reference always draws):
+ *   PATH     the route (pool route[0..route_len)) as a 1-px red polyline when route_len > 2; the bridge point (mean of the centres of
+ *            the two bridge-wall rects = static rects 0 and 1, present when n_static >= 2) as a black disc of r 5; the finish point (the
+ *            route's last way-point) as a red disc of r 5.  finish_point2 / 3 of multiple_end_points are not in the pool: not drawn.
+ *   BOX      a green disc of r max_dev at each green-zone point when there are more than 5: the reference's green_zone_trajectory_points
+ *            (ENV:1828-1841), built in the last frame before that frame's trajectory append (ENV:968-969, 1074-1075) = trajectory points
+ *            green_len - 2 down to green_len - 1 - green_count (FTL_EI_GREEN_LEN: the trajectory length the window was built on); then
+ *            the red ring of r min_distance around the leader, width 2 when FTL_EI_TOO_CLOSE is set, else 1.
+ *   OBJECTS  leader, follower, the static rects (bridge walls, rocks), then the bears (game_object_list, game_dynamic_list): a robot is a
+ *            rectangle img_w x img_h centred on its f32 position, u = (cos, sin) of its direction; a static rect is the filled
+ *            axis-aligned rect.  RECTS adds the 1-px red outline of the object's hitbox (rb_int / the static rect) right after each
+ *            body, so RECTS draws nothing without OBJECTS (show_object, ENV:1217-1227).
+ *   SENSORS  in dict order (the ray sensors with after_tracker = 0, the v2 tracker, the others).  A ray sensor draws 1-px lines from the
+ *            follower to the end points at laser_length, then discs at the collide points: the follower plus a row's reading along the
+ *            ray (the hit, or the end point without one).  LeaderCorridor_lasers / _v2 (explicit_angles or lenient, SEN:728-733): one
+ *            r-5 disc per ray from the newest row, lines and discs in FTL_RGB_RAY_V2.  The others (SEN:970-985): per output row, oldest
+ *            first, a disc per ray, r 3 in FTL_RGB_RAY_HIT_OLD for the older rows and r 5 in FTL_RGB_RAY_HIT for the newest.  Compas
+ *            sensors draw their lines only.  The v2 tracker draws its history points (discs of r 3) and, with more than one corridor
+ *            point, the two corridor borders and the two end caps as 3-px segments (sensors.py:329-339).  The v1 tracker and the aux
+ *            sensors draw nothing.
+ *   TARGET   a red ring of r 10, width 2 at the current way-point route[cur_target_id] (the leader's start with an empty route). */
+enum { FTL_RENDER_PATH = 1, FTL_RENDER_BOX = 2, FTL_RENDER_OBJECTS = 4, FTL_RENDER_RECTS = 8,
+       FTL_RENDER_SENSORS = 16, FTL_RENDER_TARGET = 32 };
+#define FTL_RENDER_ALL 63u
+/* colours, 0xRRGGBB: the reference's colours dict (ENV:206-214) and sensor show() colours; body colours per object class stand in for
+ * the sprites */
+#define FTL_RGB_WHITE 0xFFFFFFu
+#define FTL_RGB_BLACK 0x000000u
+#define FTL_RGB_RED 0xFF0000u
+#define FTL_RGB_GREEN 0x00FF00u
+#define FTL_RGB_LEADER 0x0000FFu
+#define FTL_RGB_FOLLOWER 0xFF8C00u
+#define FTL_RGB_WALL 0x1E1E1Eu
+#define FTL_RGB_ROCK 0x808080u
+#define FTL_RGB_BEAR 0x8B4513u
+#define FTL_RGB_RAY 0xC86464u        /* (200, 100, 100), SEN:971 */
+#define FTL_RGB_RAY_HIT 0xC81440u    /* (200, 20, 64), SEN:981 */
+#define FTL_RGB_RAY_HIT_OLD 0xFF4B6Eu /* (255, 75, 110), SEN:984 */
+#define FTL_RGB_RAY_V2 0xC80064u     /* (200, 0, 100): LeaderCorridor_lasers_v2 (lenient), SEN:728-733 */
+#define FTL_RGB_TRACK_HIST 0x500A0Au /* (80, 10, 10), sensors.py:331 */
+#define FTL_RGB_CORRIDOR 0x967832u   /* (150, 120, 50), sensors.py:336-339 */
+typedef struct ftl_render_params {
+    int32_t  width, height;      /* output image size, pixels */
+    float    scale;              /* world pixels per output pixel (> 0) */
+    float    origin_x, origin_y; /* world coordinate of the top-left corner of output pixel (0, 0) */
+    uint32_t layers;             /* FTL_RENDER_* bits */
+    int32_t  _pad;
+} ftl_render_params;
+size_t ftl_sizeof_render_params(void);
+/* device workspace ftl_render needs for k envs (owned by the caller, reusable across calls of the same k) */
+int ftl_render_workspace(const ftl_handle* h, int32_t k, size_t* bytes);
+/* FTL_E_INVALID before any device work: k <= 0, width / height <= 0, scale <= 0 or not finite, unknown layer bits, NULL pointers,
+ * a workspace below ftl_render_workspace; FTL_E_STATE without bound state / scenarios. */
+int ftl_render(ftl_handle* h, const int32_t* env_ids, int32_t k, const ftl_render_params* rp, void* workspace, size_t workspace_bytes,
+               uint8_t* rgb, void* stream);
+
 const char* ftl_last_error(void);
 
 /* indices into the "env_int" state field */
