@@ -16,6 +16,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_scenario_dev.hpp"),
            os.path.join(_PKG, "csrc", "ftl_crmath.hpp"),
            os.path.join(_PKG, "csrc", "ftl_render.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_snapshot.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
 # translation units: the device code + C-ABI, and the host-only scenario generator (reset-time, no GPU code)
 UNITS = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp")]
@@ -92,6 +93,14 @@ def load():
     lib.ftl_render_workspace.restype = C.c_int
     lib.ftl_render.argtypes = [vp, vp, i32, C.POINTER(abi.RenderParams), vp, C.c_size_t, vp, vp]
     lib.ftl_render.restype = C.c_int
+    lib.ftl_env_bytes.argtypes = [vp]
+    lib.ftl_env_bytes.restype = C.c_size_t
+    lib.ftl_env_layout_id.argtypes = [vp]
+    lib.ftl_env_layout_id.restype = C.c_uint64
+    lib.ftl_pack_envs.argtypes = [vp, vp, i32, vp, vp]
+    lib.ftl_pack_envs.restype = C.c_int
+    lib.ftl_unpack_envs.argtypes = [vp, vp, vp, i32, u32, vp]
+    lib.ftl_unpack_envs.restype = C.c_int
     # include/ftl_gazebo.h
     lib.ftl_gz_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.ftl_gz_destroy.argtypes = [vp]
@@ -115,6 +124,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_generate_scenarios_device_workspace", "ftl_generate_scenarios_device",
            "ftl_episode_metrics", "ftl_kernel_timing", "ftl_kernel_times",
            "ftl_sizeof_render_params", "ftl_render_workspace", "ftl_render",
+           "ftl_env_bytes", "ftl_env_layout_id", "ftl_pack_envs", "ftl_unpack_envs",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -34,7 +34,9 @@ FTL_METRICS_CLEAR = 1
  EI_STEP_COUNT, EI_FINISH_TIMER, EI_TRAJ_LEN, EI_TRK_COUNTER, EI_CORR_LO, EI_CORR_HI, EI_SEED_END,
  EI_SNAP_COUNT, EI_DYN_INDEX0, EI_DYN_INDEX1, EI_DYN_INDEX2, EI_DYN_INDEX3, EI_DYN_INDEX4, EI_DYN_INDEX5, EI_ERROR, EI_EPISODES,
  EI_GREEN_COUNT, EI_GREEN_LEN, EI_SCAN_OK, EI_SNAP_HEAD, EI_HINT, EI_GREEN_TINY, EI_RESETS, EI_ACC_CONSUMED,
- EI_HINT_X, EI_HINT_Y, EI_CLR_GREEN, EI_CLR_ALL, EI_FPS, EI_HW0_LO, EI_HW0_HI, EI_HIST1_LEN, EI_ERROR_STICKY, EI_COUNT) = range(42)
+ EI_HINT_X, EI_HINT_Y, EI_CLR_GREEN, EI_CLR_ALL, EI_FPS, EI_HW0_LO, EI_HW0_HI, EI_HIST1_LEN, EI_ERROR_STICKY, EI_STREAM, EI_COUNT) = range(43)
+# ftl_unpack_envs flags (include/ftl.h)
+FTL_ENV_SLOT_STATS, FTL_ENV_OWN_STREAM = 1, 2
 ED_ACC_PENALTY, ED_OVERALL_REWARD, ED_SPARE0, ED_SPARE1, ED_BEAR_POINTS = range(5)
 ED_GREEN_W = ED_BEAR_POINTS + 2 * FTL_MAX_BEARS
 ED_CUR_MULT, ED_CUR_ACC, ED_CUM_SPEED = ED_GREEN_W + 1, ED_GREEN_W + 2, ED_GREEN_W + 3

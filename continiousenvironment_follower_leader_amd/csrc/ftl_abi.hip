@@ -649,6 +649,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 #include "ftl_gazebo.hpp"      // follower-relative tracker / ray sensors (include/ftl_gazebo.h), same translation unit
 #include "ftl_scenario_dev.hpp"  // the scenario generator on the GPU (ftl_generate_scenarios_device), same translation unit
 #include "ftl_render.hpp"        // batched top-down RGB frames (ftl_render), same translation unit
+#include "ftl_snapshot.hpp"      // snapshot / clone / restore of env rows (ftl_pack_envs, ftl_unpack_envs), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

@@ -131,9 +131,15 @@ __device__ __forceinline__ double d_uniform01(unsigned long long seed, unsigned 
     return (double)(d_mix64(key + 0x9E3779B97F4A7C15ULL * (frame + 1)) >> 11) * (1.0 / 9007199254740992.0);
 }
 
-// device twin of ftl_rand_frames (include/ftl.h): np.random.randint(lo, hi) of ENV:405 / 940
-__device__ __forceinline__ int d_rand_frames(const ftl_config& c, int env, int resets, int step_count) {
-    const double u = d_uniform01(c.rng_seed, (unsigned long long)(c.env_id_base + env), (unsigned long long)resets,
+// global id of env `env`'s random stream: env_id_base + env, moved by FTL_EI_STREAM when a row was cloned / restored into this slot
+// (ftl_unpack_envs).  No kernel writes the word, so it is read where a draw needs it instead of being held in a register.
+__device__ __forceinline__ int d_stream_id(const FtlDevParams& P, int env) {
+    return P.cfg.env_id_base + env + rec_field(P.env_int, P, env)[FTL_EI_STREAM];
+}
+
+// device twin of ftl_rand_frames (include/ftl.h): np.random.randint(lo, hi) of ENV:405 / 940; `stream` = d_stream_id
+__device__ __forceinline__ int d_rand_frames(const ftl_config& c, int stream, int resets, int step_count) {
+    const double u = d_uniform01(c.rng_seed, (unsigned long long)stream, (unsigned long long)resets,
                                  (unsigned long long)step_count | (1ULL << 40));
     const int v = c.rand_fps_lo + (int)(u * (double)(c.rand_fps_hi - c.rand_fps_lo));
     return v < c.rand_fps_hi ? v : c.rand_fps_hi - 1;
@@ -282,7 +288,7 @@ __device__ __forceinline__ void g_reset(const FtlDevParams& P, GCtx& E, int scen
         E.trk_counter = 0; E.corr_lo = 0; E.corr_hi = 0; E.seed_end = 0; E.snap_count = 0; E.snap_head = 0;
         E.hint = 0; E.hx = 3.0e38f; E.hy = 3.0e38f; E.clr_g = 0.0f; E.clr_a = 0.0f;     // no cached point, no bound
         if (c.has_tracker == 1 && E.r == 0) rec_field(P.env_int, P, E.env)[FTL_EI_HIST1_LEN] = 0;   // v1 tracker reset(), SEN:223-226
-        if (c.rand_fps_hi > 0 && E.fps == 0) E.fps = d_rand_frames(c, E.env, 0, 0);      // the constructor's draw (ENV:405)
+        if (c.rand_fps_hi > 0 && E.fps == 0) E.fps = d_rand_frames(c, d_stream_id(P, E.env), 0, 0);      // the constructor's draw (ENV:405)
         E.cur_mult = 1.0; E.cur_acc = 0.0; E.cum_speed = 0.0; E.resets += 1;      // ENV:449, 591-592; acc_consumed persists (ENV:1170)
     }
     // The initial trajectory (83-261 points).  When only a few envs of the wavefront reset -- the in-kernel auto-reset: one in most such
@@ -696,7 +702,7 @@ __device__ __forceinline__ void g_frame(const FtlDevParams& P, GCtx& E, const Li
             const int lo = (int)c.max_distance, k = 2 * E.rb.dyn_index;
             auto draw = [&](int kk, int stop) {
                 const int nn = (stop - lo + 9) / 10;
-                const double u = d_uniform01(c.rng_seed, (unsigned long long)(c.env_id_base + E.env), (unsigned long long)E.resets,
+                const double u = d_uniform01(c.rng_seed, (unsigned long long)d_stream_id(P, E.env), (unsigned long long)E.resets,
                                              (unsigned long long)E.step_count | (1ULL << 41) | ((unsigned long long)b << 44) | ((unsigned long long)kk << 48));
                 const int v = (int)(u * (double)nn);
                 return (double)(lo + 10 * (v < nn ? v : nn - 1));
@@ -714,7 +720,7 @@ __device__ __forceinline__ void g_frame(const FtlDevParams& P, GCtx& E, const Li
             for (int i = 0; i < c.n_speed_regime; i++) if (c.speed_key[i] <= E.step_count) sel = i;   // dict order, last match wins
             if (sel >= 0) {
                 if (c.speed_is_range[sel]) {
-                    double u = d_uniform01(c.rng_seed, (unsigned long long)(c.env_id_base + E.env), (unsigned long long)E.resets, (unsigned long long)E.step_count);
+                    double u = d_uniform01(c.rng_seed, (unsigned long long)d_stream_id(P, E.env), (unsigned long long)E.resets, (unsigned long long)E.step_count);
                     E.cur_mult = c.speed_lo[sel] + (c.speed_hi[sel] - c.speed_lo[sel]) * u;
                 } else E.cur_mult = c.speed_lo[sel];
             }
@@ -1589,7 +1595,7 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_FRAMESG_WPE) ftl_frames_group_ke
                 if (f < f_max && (!REG || f < E.fps)) g_tail(TK, E, (int)((w >> (8 * j)) & 255u), sc, reward, i0, i1, i2);
             }
         }
-        if (REG && P.cfg.rand_fps_hi > 0) E.fps = d_rand_frames(P.cfg, E.env, E.resets, E.step_count);      // ENV:939-940: the next step's frames
+        if (REG && P.cfg.rand_fps_hi > 0) E.fps = d_rand_frames(P.cfg, d_stream_id(P, E.env), E.resets, E.step_count);      // ENV:939-940: the next step's frames
         if (E.valid && E.r == 0) {
             C.out.reward[E.env] = reward; C.out.done[E.env] = (uint8_t)E.done;
             C.out.status[3 * (size_t)E.env] = (uint8_t)i0; C.out.status[3 * (size_t)E.env + 1] = (uint8_t)i1; C.out.status[3 * (size_t)E.env + 2] = (uint8_t)i2;

@@ -148,6 +148,25 @@ class Game:
             raise RuntimeError("reset() first")
         return self._vec.render([0], **kwargs)[0].cpu().numpy()
 
+    def clone_state(self):
+        """The env's state for ``restore_state`` (ALE cloneState; the reference's Game is ``copy.deepcopy``-ed): the device snapshot of the
+        env with its slot records, and the facade's own state -- ``done``, ``simulation_number``, the seed counters and the scenario pool
+        (the one-entry pool this episode was generated into, kept alive here)."""
+        if self._vec is None:
+            raise RuntimeError("reset() first")
+        return dict(snapshot=self._vec.snapshot([0]), done=self.done, simulation_number=self.simulation_number, seed=self._seed,
+                    resets_since_seed=self._resets_since_seed, pool=self._vec.pool)
+
+    def restore_state(self, state):
+        """Bring back a ``clone_state``: the next ``step`` calls return what they returned after the clone.  A pool that a later ``reset()``
+        replaced is loaded again."""
+        self._ensure()
+        if self._vec.pool is not state["pool"]:
+            self._vec.load_scenarios(state["pool"])
+        self._vec.restore(state["snapshot"], [0], slot_stats=True)
+        self.done, self.simulation_number = state["done"], state["simulation_number"]
+        self._seed, self._resets_since_seed = state["seed"], state["resets_since_seed"]
+
     def close(self):
         if self._vec is not None:
             self._vec.close()

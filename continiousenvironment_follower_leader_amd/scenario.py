@@ -369,6 +369,7 @@ class DeviceScenarioRing:
             dest = torch.where(keep, pos + seg * S, torch.full_like(pos, self.K * S))
             for k in SCEN_KEYS:
                 self.pool.t[k].index_copy_(0, dest, g[k])
+            self.pool.version += 1                 # (snapshots taken before this write no longer restore: EnvSnapshot)
             need = S - have
             total = cnt[-1:]
             consumed = torch.where(have + total >= S, torch.searchsorted(cnt, need) + 1, torch.full_like(have, self._chunk))

@@ -5,6 +5,8 @@ follow_the_leader_continuous_env.py:434-543, 908-945).
 PyTorch is used for plumbing only: it owns the device buffers (state blob, scenario pool, outputs) and the
 stream; all arithmetic happens in ``libftl_hip.so`` behind the C-ABI of ``include/ftl.h``."""
 import ctypes as C
+import hashlib
+import uuid
 from contextlib import nullcontext as _nullcontext
 
 import numpy as np
@@ -60,6 +62,8 @@ class ScenarioPool:
         self._bind()
 
     def _bind(self):
+        if not hasattr(self, "uid"):           # identity + content version: what an EnvSnapshot is tied to (EnvSnapshot.pool_token)
+            self.uid, self.version = uuid.uuid4().hex, 0
         s = abi.Scenarios()
         s.n_scenarios = self.n
         for k, v in self.t.items():
@@ -88,6 +92,17 @@ class ScenarioPool:
         with torch.cuda.stream(stream) if stream is not None else _nullcontext():
             for k, v in host.items():
                 self.t[k][base:base + n].copy_(v if isinstance(v, torch.Tensor) else torch.from_numpy(v), non_blocking=True)
+        self.version += 1
+
+    def digest(self):
+        """sha256 of the pool's contents (entries ``[0, n)`` of every array, host copies): what ``VecGame.state_dict`` records so that a
+        checkpoint is only loaded next to the worlds its episodes run on.  Synchronises."""
+        h = hashlib.sha256()
+        for k in sorted(self.t):
+            t = self.t[k][:self.n].contiguous().cpu()
+            h.update(k.encode())
+            h.update(t.view(torch.uint8).numpy().tobytes() if t.numel() else b"")
+        return h.hexdigest()
 
     @classmethod
     def generate(cls, cfg, seeds, device, n_threads=0):
@@ -230,6 +245,10 @@ class VecGame:
         self._out = o
         self.pool = None
         self._fields = {}
+        self._window = None
+        self._tune = {}
+        self.env_bytes = int(self.lib.ftl_env_bytes(self.h))
+        self.layout_id = int(self.lib.ftl_env_layout_id(self.h))
 
     def close(self):
         if getattr(self, "h", None):
@@ -246,19 +265,23 @@ class VecGame:
     def load_scenarios(self, pool: ScenarioPool):
         self.pool = pool
         _lib.check(self.lib.ftl_load_scenarios(self.h, C.byref(pool.c_struct)), self.lib)
+        self._window = (0, pool.n, self.n % pool.n)
 
     def set_reset_window(self, base, count, stride=0):
         """Pool entries ``[base, base + count)`` the in-kernel auto-reset draws from and the step of its walk (``ftl_set_reset_window``;
         the whole pool with stride n_envs after ``load_scenarios``): how a ``ScenarioRing`` hands freshly generated worlds to a running
         batch.  ``stride`` should be coprime to ``count`` (0 keeps n_envs)."""
         _lib.check(self.lib.ftl_set_reset_window(self.h, int(base), int(count), int(stride)), self.lib)
+        self._window = (int(base), int(count), (int(stride) if int(stride) > 0 else self.n) % int(count))
 
     def tune(self, coscheduled_envs=None, regroup_every=None, two_streams=None):
         """Scheduling hints (``ftl_tune``; results never depend on them): how many envs are stepped on the device at the same time when
         this batch is one of several on several streams, how often the cost order of the envs is rebuilt, the handle's own two-stream mode."""
-        for key, v in ((abi.FTL_TUNE_COSCHEDULED_ENVS, coscheduled_envs), (abi.FTL_TUNE_REGROUP_EVERY, regroup_every), (abi.FTL_TUNE_TWO_STREAMS, two_streams)):
+        for name, key, v in (("coscheduled_envs", abi.FTL_TUNE_COSCHEDULED_ENVS, coscheduled_envs), ("regroup_every", abi.FTL_TUNE_REGROUP_EVERY, regroup_every),
+                             ("two_streams", abi.FTL_TUNE_TWO_STREAMS, two_streams)):
             if v is not None:
                 _lib.check(self.lib.ftl_tune(self.h, key, int(v)), self.lib)
+                self._tune[name] = int(v)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -397,6 +420,131 @@ class VecGame:
         if bits:
             raise error_for_bits(bits, n)
 
+    # ------------------------------------------------------------------ snapshot / clone / restore (ftl_pack_envs, ftl_unpack_envs)
+    def output_rows(self):
+        """name -> the per-env output tensors a snapshot carries: the step outputs, ``policy_obs`` and the final buffers when enabled."""
+        names = list(_OUT_NAMES) + (["policy_obs"] if self.policy_obs is not None else [])
+        if self.final_obs:
+            names += ["final_obs_num", "final_lasers", "final_target", "ended", "restarted"]
+            names += ["final_policy_obs"] if self.final_policy_obs is not None else []
+        return {k: getattr(self, k) for k in names}
+
+    def snapshot(self, env_ids=None):
+        """``EnvSnapshot`` of envs ``env_ids`` (env indices of this batch, repeats allowed; None: all) -- the packed state rows and the output
+        rows, enqueued on the current stream.  Tied to the scenario pool as it is now (see ``EnvSnapshot``).  Reads the ids on the host."""
+        ids = _host_ids(env_ids, self.n)
+        return self._snapshot_ids(ids)
+
+    def _snapshot_ids(self, ids):
+        self._need_pool()
+        k = int(ids.numel())
+        rows = torch.empty(k, self.env_bytes, dtype=torch.uint8, device=self.device)
+        dev = ids.to(device=self.device, dtype=torch.int32)
+        if k:
+            _lib.check(self.lib.ftl_pack_envs(self.h, dev.data_ptr(), k, rows.data_ptr(), self._stream()), self.lib)
+        idx = dev.long()
+        outs = {name: t.index_select(0, idx) for name, t in self.output_rows().items()}
+        return EnvSnapshot(rows, outs, self.layout_id, _pool_token(self.pool))
+
+    def restore(self, snap, env_ids=None, slot_stats=False, own_stream=False):
+        """Write the envs of ``snap`` into envs ``env_ids`` of this batch (distinct indices, one per snapshot row; None: 0 .. len(snap) - 1):
+        their state and their output rows, so that ``obs_num`` etc. show the restored envs at once.  Each env then continues its source's
+        episode bit for bit under the same actions: it keeps its source's random stream (``own_stream=True``: the destination's own, which
+        diverges on the first random draw).  ``slot_stats=True`` also moves the slot's episode records (``ep_stats``, episode count, sticky
+        error word: ``episode_metrics`` counts the source's episodes again); by default the destination keeps its own.  Raises ValueError,
+        with nothing written, for ids out of range or repeated, a snapshot of another layout, or a pool that changed since the snapshot."""
+        ids = _host_ids(env_ids, self.n) if env_ids is not None else torch.arange(len(snap), dtype=torch.int64)
+        self._check_snapshot(snap, ids)
+        self._restore_ids(snap, ids, slot_stats, own_stream)
+
+    def _check_snapshot(self, snap, ids, n=None):
+        n = self.n if n is None else n
+        self._need_pool()
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("restore() takes an EnvSnapshot")
+        if snap.layout_id != self.layout_id:
+            raise ValueError("the snapshot was taken from a batch of another layout (config, capacities or sensors differ)")
+        if snap.pool_token != _pool_token(self.pool):
+            raise ValueError("the scenario pool is not the one the snapshot was taken on, or it was written since (ScenarioPool.write, a "
+                             "moving ScenarioRing / DeviceScenarioRing): snapshots are tied to the pool contents")
+        if int(ids.numel()) != len(snap):
+            raise ValueError("%d destination ids for %d snapshot rows" % (ids.numel(), len(snap)))
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise ValueError("env_ids outside [0, %d)" % n)
+        if torch.unique(ids).numel() != ids.numel():
+            raise ValueError("duplicate destination env ids")
+        missing = [k for k in self.output_rows() if k not in snap.outputs]
+        if missing:
+            raise ValueError("the snapshot lacks the output rows %s of this batch" % missing)
+
+    def _restore_ids(self, snap, ids, slot_stats, own_stream):
+        k = int(ids.numel())
+        if k == 0:
+            return
+        flags = (abi.FTL_ENV_SLOT_STATS if slot_stats else 0) | (abi.FTL_ENV_OWN_STREAM if own_stream else 0)
+        rows = snap.rows.to(self.device).contiguous()
+        dev = ids.to(device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.ftl_unpack_envs(self.h, rows.data_ptr(), dev.data_ptr(), k, flags, self._stream()), self.lib)
+        self._keep_restore = (rows, dev)
+        idx = dev.long()
+        for name, t in self.output_rows().items():
+            t.index_copy_(0, idx, snap.outputs[name].to(self.device))
+
+    def clone(self, src_ids, dst_ids, slot_stats=False, own_stream=False):
+        """Copy envs ``src_ids`` into envs ``dst_ids`` (``restore`` of a ``snapshot``: every source is read before any destination is written,
+        so a destination may also be a source, e.g. a permutation).  The search case: one env into K slots, each stepped with another action."""
+        src, dst = _host_ids(src_ids, self.n), _host_ids(dst_ids, self.n)
+        if src.numel() != dst.numel():
+            raise ValueError("src_ids and dst_ids differ in length")
+        if torch.unique(dst).numel() != dst.numel():
+            raise ValueError("duplicate destination env ids")
+        self._need_pool()
+        self._restore_ids(self._snapshot_ids(src), dst, slot_stats, own_stream)
+
+    def state_dict(self):
+        """The whole batch as a checkpoint of plain tensors (``torch.save`` / ``torch.load`` it): every env's row in global env order, with
+        its slot records, the output rows, ``env_id_base`` / ``n_envs``, the reset window, the ``tune`` settings and a content digest of
+        the scenario pool.  Synchronises."""
+        self._need_pool()
+        snap = self._snapshot_ids(torch.arange(self.n, dtype=torch.int64))
+        return dict(format=1, layout_id=self.layout_id, env_id_base=int(self.cfg.c.env_id_base), n_envs=self.n,
+                    rows=snap.rows.cpu(), outputs={k: v.cpu() for k, v in snap.outputs.items()},
+                    reset_window=self._window, tune=dict(self._tune), pool_n=int(self.pool.n), pool_digest=self.pool.digest())
+
+    def load_state_dict(self, sd, apply_tune=True, _digest=None):
+        """Continue a checkpoint of ``state_dict``: this batch takes the rows whose global env ids (env_id_base + index) it owns, with their
+        slot records -- a checkpoint of one batch loads into batches of other sizes / bases that together cover it (re-sharding, shard.py).
+        Needs ``load_scenarios`` of a pool with the checkpoint's contents first; sets the checkpoint's reset window (its stride, not this
+        batch's n_envs) and, with ``apply_tune``, its ``tune`` settings where they fit this batch."""
+        self._need_pool()
+        if sd.get("format") != 1 or int(sd["layout_id"]) != self.layout_id:
+            raise ValueError("the checkpoint was taken from a batch of another layout (config, capacities or sensors differ)")
+        base0, n0 = int(sd["env_id_base"]), int(sd["n_envs"])
+        lo = int(self.cfg.c.env_id_base) - base0
+        if lo < 0 or lo + self.n > n0:
+            raise ValueError("the checkpoint holds global envs [%d, %d); this batch is [%d, %d)"
+                             % (base0, base0 + n0, self.cfg.c.env_id_base, self.cfg.c.env_id_base + self.n))
+        if int(sd["pool_n"]) != self.pool.n or sd["pool_digest"] != (_digest or self.pool.digest()):
+            raise ValueError("the scenario pool differs from the checkpoint's (content digest)")
+        missing = [k for k in self.output_rows() if k not in sd["outputs"]]
+        if missing:
+            raise ValueError("the checkpoint lacks the output rows %s of this batch" % missing)
+        snap = EnvSnapshot(sd["rows"][lo:lo + self.n], {k: v[lo:lo + self.n] for k, v in sd["outputs"].items()}, self.layout_id,
+                           _pool_token(self.pool))
+        self._restore_ids(snap, torch.arange(self.n, dtype=torch.int64), True, False)
+        if sd.get("reset_window") is not None:
+            b, c, st = sd["reset_window"]
+            self.set_reset_window(b, c, st if st > 0 else c)       # (stride c: the walk's step 0 mod c, not this batch's n_envs)
+        if apply_tune:
+            t = dict(sd.get("tune") or {})
+            if t.get("coscheduled_envs", self.n) < self.n:
+                t.pop("coscheduled_envs")
+            self.tune(**t)
+
+    def _need_pool(self):
+        if self.pool is None:
+            raise _lib.FtlError("load_scenarios() first")
+
     # ------------------------------------------------------------------ views
     def laser_view(self, name):
         for l in self.cfg.lasers:
@@ -493,6 +641,52 @@ class VecGame:
         else:
             hist = self.state_field("hist")[env].view(cap, 2)[idx].cpu().numpy()
         return hist, corr
+
+
+_OUT_NAMES = ("obs_num", "lasers", "target", "reward", "done", "status")
+
+
+class EnvSnapshot:
+    """Saved envs (``VecGame.snapshot``): ``rows`` uint8 ``[k, env_bytes]`` -- the packed state of each env (include/ftl.h, ftl_pack_envs)
+    --, ``outputs`` name -> ``[k, ...]`` output rows (obs_num, lasers, target, reward, done, status, and policy_obs / the final buffers
+    when the batch has them), ``layout_id`` (``ftl_env_layout_id``) and ``pool_token`` = (uid, version) of the scenario pool.
+
+    A snapshot holds scenario INDICES, not scenarios: it restores only into a batch that runs the same ``ScenarioPool`` object, unwritten
+    since (``ScenarioPool.write`` and a moving ``ScenarioRing`` / ``DeviceScenarioRing`` bump its version).  ``cpu()`` / ``to(device)``
+    move it; it survives ``torch.save`` / ``torch.load`` (kept with the same pool object in the process, or use ``state_dict``)."""
+
+    def __init__(self, rows, outputs, layout_id, pool_token):
+        self.rows, self.outputs, self.layout_id, self.pool_token = rows, dict(outputs), int(layout_id), tuple(pool_token)
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def to(self, device):
+        return EnvSnapshot(self.rows.to(device), {k: v.to(device) for k, v in self.outputs.items()}, self.layout_id, self.pool_token)
+
+    def cpu(self):
+        return self.to("cpu")
+
+
+if hasattr(torch.serialization, "add_safe_globals"):       # torch.load(weights_only=True), the default, may rebuild it
+    torch.serialization.add_safe_globals([EnvSnapshot])
+
+
+def _pool_token(pool):
+    return (pool.uid, int(pool.version))
+
+
+def _host_ids(env_ids, n):
+    """int64 host tensor of env indices in [0, n) (None: all)."""
+    if env_ids is None:
+        return torch.arange(n, dtype=torch.int64)
+    a = torch.as_tensor(env_ids.detach().cpu() if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids)).reshape(-1)
+    if a.dtype.is_floating_point or a.dtype == torch.bool:
+        raise ValueError("env ids must be integers")
+    a = a.to(torch.int64)
+    if a.numel() and (int(a.min()) < 0 or int(a.max()) >= n):
+        raise ValueError("env ids outside [0, %d)" % n)
+    return a
 
 
 _SHOW_FLAGS = (("show_leader_path_flag", abi.RENDER_PATH), ("show_box_flag", abi.RENDER_BOX), ("show_objects_flag", abi.RENDER_OBJECTS),
@@ -764,6 +958,80 @@ class PipelinedVecGame:
                 part = g._render_ids(local, scale, size, origin, layers, None)
                 out.index_copy_(0, torch.from_numpy(sel).to(self.device), part)
         return out
+
+    # snapshot / clone / restore over global env indices: each is a synchronisation point (the parts are joined first, as state_field
+    # does); rows move between the parts through ftl_pack_envs / ftl_unpack_envs on the current stream, which the parts' next steps wait for
+    def snapshot(self, env_ids=None):
+        """``VecGame.snapshot`` over env indices of the whole batch (joins the parts first)."""
+        self.join()
+        return self._snapshot_ids(_host_ids(env_ids, self.n))
+
+    def _snapshot_ids(self, ids):
+        g0 = self.games[0]
+        g0._need_pool()
+        k = int(ids.numel())
+        rows = torch.empty(k, g0.env_bytes, dtype=torch.uint8, device=self.device)
+        outs = {name: torch.empty((k,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for name, t in g0.output_rows().items()}
+        for g, sh in zip(self.games, self.shards):
+            sel = torch.nonzero((ids >= sh.lo) & (ids < sh.hi)).reshape(-1)
+            if sel.numel() == 0:
+                continue
+            part, dsel = g._snapshot_ids(ids[sel] - sh.lo), sel.to(self.device)
+            rows.index_copy_(0, dsel, part.rows)
+            for name, t in outs.items():
+                t.index_copy_(0, dsel, part.outputs[name])
+        return EnvSnapshot(rows, outs, g0.layout_id, _pool_token(self.pool))
+
+    def restore(self, snap, env_ids=None, slot_stats=False, own_stream=False):
+        """``VecGame.restore`` into env indices of the whole batch (joins the parts first; every check before anything is written)."""
+        self.join()
+        ids = _host_ids(env_ids, self.n) if env_ids is not None else torch.arange(len(snap), dtype=torch.int64)
+        self.games[0]._check_snapshot(snap, ids, self.n)
+        self._restore_ids(snap, ids, slot_stats, own_stream)
+
+    def _restore_ids(self, snap, ids, slot_stats, own_stream):
+        for g, sh in zip(self.games, self.shards):
+            sel = torch.nonzero((ids >= sh.lo) & (ids < sh.hi)).reshape(-1)
+            if sel.numel() == 0:
+                continue
+            r = sel.to(snap.rows.device)
+            sub = EnvSnapshot(snap.rows.index_select(0, r), {k: v.index_select(0, sel.to(v.device)) for k, v in snap.outputs.items()},
+                              snap.layout_id, snap.pool_token)
+            g._restore_ids(sub, ids[sel] - sh.lo, slot_stats, own_stream)
+
+    def clone(self, src_ids, dst_ids, slot_stats=False, own_stream=False):
+        """``VecGame.clone`` over env indices of the whole batch; sources and destinations may lie in different parts."""
+        self.join()
+        src, dst = _host_ids(src_ids, self.n), _host_ids(dst_ids, self.n)
+        if src.numel() != dst.numel():
+            raise ValueError("src_ids and dst_ids differ in length")
+        if torch.unique(dst).numel() != dst.numel():
+            raise ValueError("duplicate destination env ids")
+        self._restore_ids(self._snapshot_ids(src), dst, slot_stats, own_stream)
+
+    def state_dict(self):
+        """``VecGame.state_dict`` of the whole batch (rows of every part in global env order)."""
+        self.join()
+        g0 = self.games[0]
+        g0._need_pool()
+        snap = self._snapshot_ids(torch.arange(self.n, dtype=torch.int64))
+        return dict(format=1, layout_id=g0.layout_id, env_id_base=int(self.cfg.c.env_id_base), n_envs=self.n,
+                    rows=snap.rows.cpu(), outputs={k: v.cpu() for k, v in snap.outputs.items()},
+                    reset_window=g0._window, tune={}, pool_n=int(self.pool.n), pool_digest=self.pool.digest())
+
+    def load_state_dict(self, sd):
+        """``VecGame.load_state_dict`` for every part (each takes the rows of its global env ids); the parts keep their own scheduling
+        hints.  Joins the parts first."""
+        self.join()
+        if self.pool is None:
+            raise _lib.FtlError("load_scenarios() first")
+        digest = self.pool.digest()
+        for g in self.games:                    # (every part checks the checkpoint before the first one writes: same layout, same range)
+            lo = int(g.cfg.c.env_id_base) - int(sd["env_id_base"])
+            if int(sd["layout_id"]) != g.layout_id or lo < 0 or lo + g.n > int(sd["n_envs"]):
+                raise ValueError("the checkpoint does not cover this batch's envs with the same layout")
+        for g in self.games:
+            g.load_state_dict(sd, apply_tune=False, _digest=digest)
 
     def kernel_timing(self, enable=True):
         """Measurement hook.  While enabled the parts run one after the other on the CURRENT stream, so that every kernel's HIP events

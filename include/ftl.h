@@ -506,6 +506,34 @@ int ftl_render_workspace(const ftl_handle* h, int32_t k, size_t* bytes);
 int ftl_render(ftl_handle* h, const int32_t* env_ids, int32_t k, const ftl_render_params* rp, void* workspace, size_t workspace_bytes,
                uint8_t* rgb, void* stream);
 
+/* ---- snapshot, clone and restore of env states (ALE cloneState / restoreState, copy.deepcopy of the reference's Game) ----------------
+ * A packed env row holds everything of one env that the state buffer stores, so that unpacking it into any slot of any handle with the
+ * same layout id continues the env's episode bit for bit (with the same actions and the same scenario pool):
+ *   row = [record][traj][hist][corr][traj_bb][ep_stats][hist1][corr32][zero padding to ftl_env_bytes]
+ *   record: the bytes of the per-env record that hold its fields (env_int, fol_cs, rb_pos, rb_dbl, snap_win, snap_rects, env_dbl, rb_int
+ *           at their ftl_state_field offsets; the record's tail padding up to its stride is not stored); then every dense field in
+ *           ftl_state_field order, each at a 16-byte aligned row offset, its gap zero-filled; a field with per_env 0 takes no bytes.
+ *   The whole trajectory (traj_cap points) and every block box are stored, not only the live prefix.
+ *   Stream rule: word FTL_EI_STREAM of the row's env_int holds the ABSOLUTE global stream id (env_id_base + env + offset of the source);
+ *           unpacking into slot `dst` stores id - env_id_base - dst, so the env keeps drawing from its source's stream in any slot,
+ *           handle or shard layout.
+ * ftl_env_bytes: bytes of one row (a multiple of 256).  ftl_env_layout_id: 64-bit hash of the frozen config without n_envs and
+ * env_id_base, of FTL_ABI_VERSION and of the row format; rows move only between handles with equal ids.  Neither touches the device.
+ * ftl_pack_envs copies envs env_ids[0..k) into rows[k][ftl_env_bytes] (DEVICE pointers; rows 16-byte aligned).  ftl_unpack_envs copies
+ * rows[i] into env env_ids[i]; env_ids must be distinct, rows must not overlap the state buffer.  By default the destination keeps what
+ * belongs to its slot rather than to the episode -- its "ep_stats" record and its FTL_EI_EPISODES / FTL_EI_ERROR_STICKY words -- so that
+ * ftl_episode_metrics counts every episode once; FTL_ENV_SLOT_STATS moves them too (checkpoints).  FTL_ENV_OWN_STREAM keeps the
+ * destination's FTL_EI_STREAM word (the copy then draws from the destination's own stream and diverges from its source on the first
+ * random draw).  Ids are not range-checked on the device (the caller checks them, as for ftl_reset's scenario indices).  Rejected with
+ * FTL_E_INVALID before any device work: k < 0, NULL pointers with k > 0, rows not 16-byte aligned, unknown flag bits; FTL_E_STATE
+ * without bound state.  k == 0 does nothing.  Asynchronous on `stream`; the outputs (obs, lasers, ...) are the caller's to copy. */
+#define FTL_ENV_SLOT_STATS 1u  /* also move ep_stats, FTL_EI_EPISODES, FTL_EI_ERROR_STICKY (checkpoints); default: dst keeps its own */
+#define FTL_ENV_OWN_STREAM 2u  /* dst keeps its own random stream instead of the row's */
+size_t   ftl_env_bytes(const ftl_handle* h);
+uint64_t ftl_env_layout_id(const ftl_handle* h);
+int ftl_pack_envs(const ftl_handle* h, const int32_t* env_ids, int32_t k, void* rows, void* stream);
+int ftl_unpack_envs(ftl_handle* h, const void* rows, const int32_t* env_ids, int32_t k, uint32_t flags, void* stream);
+
 const char* ftl_last_error(void);
 
 /* indices into the "env_int" state field */
@@ -532,6 +560,9 @@ enum {
     FTL_EI_HIST1_LEN,   /* v1 tracker: points in the "hist1" field */
     FTL_EI_ERROR_STICKY, /* OR of every FTL_ERR_* bit this env slot ever raised: survives reset / auto-reset (FTL_EI_ERROR is per
                           episode); cleared by ftl_episode_metrics(FTL_METRICS_CLEAR) */
+    FTL_EI_STREAM,      /* offset of the env's random stream from its own global index: every draw of the step kernels is keyed by
+                          env_id_base + env + this word (0 in a zeroed state: the env's own stream).  Written only by ftl_unpack_envs;
+                          reset / auto-reset keep it, like FTL_EI_RESETS */
     FTL_EI_COUNT
 };
 /* indices into the "env_dbl" state field; bear waypoints follow at FTL_ED_BEAR_POINTS + 2*b */
