@@ -22,9 +22,12 @@ LEADER = ("moving", "crash", "finished")
 FTL_ERR_TRAJ_OVERFLOW, FTL_ERR_CORR_OVERFLOW, FTL_ERR_EMPTY_CORRIDOR, FTL_ERR_TRACKER_SEED, FTL_ERR_HIST1_OVERFLOW = 1, 2, 4, 8, 16
 FTL_ERR_LIDAR_OVERFLOW = 32
 FTL_ERR_BAD_ACTION = 64
+FTL_ERR_BAD_STREAM = 128
 FTL_ACTION_BOX2, FTL_ACTION_DISCRETE, FTL_ACTION_TURN = 0, 1, 2
 FTL_STEP_AUTO_RESET = 1
 FTL_STEP_NEXT_RESET = 4
+FTL_STEP_QUEUE_RESET = 8
+FTL_EPISODE_DONE_AT_RESET = 1
 FTL_N_METRICS = 8
 FTL_METRICS_CLEAR = 1
 (M_EPISODES, M_RETURN_SUM, M_FRAMES_SUM, M_SUCCESS, M_CRASH, M_LOW_REWARD, M_TOO_FAR, M_TIMEOUT) = range(8)
@@ -161,6 +164,22 @@ class FinalOutputs(C.Structure):
     """ftl_final_outputs: the terminal rows and the ended / restarted masks of ftl_step_final."""
     _fields_ = [("obs_num", C.c_void_p), ("lasers", C.c_void_p), ("target", C.c_void_p), ("policy_obs", C.c_void_p),
                 ("ended", C.c_void_p), ("restarted", C.c_void_p)]
+
+
+class EpisodeRecord(C.Structure):
+    """ftl_episode_record: one row per entry of an episode queue, written once (``RECORD_DTYPE`` is the same row for numpy)."""
+    _fields_ = [("state", C.c_int32), ("scenario", C.c_int32), ("env", C.c_int32), ("frames", C.c_int32), ("calls", C.c_int32),
+                ("status", C.c_int32 * 3), ("errors", C.c_uint32), ("flags", C.c_uint32), ("ret", C.c_double), ("stream", C.c_int64)]
+
+
+RECORD_DTYPE = [("state", "<i4"), ("scenario", "<i4"), ("env", "<i4"), ("frames", "<i4"), ("calls", "<i4"), ("status", "<i4", (3,)),
+                ("errors", "<u4"), ("flags", "<u4"), ("ret", "<f8"), ("stream", "<i8")]
+
+
+class EpisodeQueueC(C.Structure):
+    """ftl_episode_queue: device pointers of a queue's arrays (``vec_game.EpisodeQueue`` owns them)."""
+    _fields_ = [("scenario", C.c_void_p), ("stream", C.c_void_p), ("stream_base", C.c_int64), ("n", C.c_int32), ("_pad", C.c_int32),
+                ("head", C.c_void_p), ("records", C.c_void_p), ("ticket", C.c_void_p)]
 
 
 # ftl_render (include/ftl.h): layer bits and the image parameters

@@ -150,6 +150,8 @@ class ScenarioPool:
 def error_for_bits(bits, n_envs=1):
     """Exception object for a set of FTL_ERR_* bits: the type the reference raises where it has one."""
     where = "%d env(s)" % n_envs
+    if bits & abi.FTL_ERR_BAD_STREAM:
+        return ValueError("an episode queue's stream id outside 0 .. 2**31 - 1 in %s" % where)
     if bits & abi.FTL_ERR_BAD_ACTION:           # ENV:922: discrete_rotation_speed_to_value[action] with an action outside 0..4
         return KeyError("Discrete(5) action outside 0..4 in %s" % where)
     if bits & abi.FTL_ERR_TRACKER_SEED:         # SEN:264-297 (the tracker is scanned before every ray sensor, CLS:263-267)
@@ -175,7 +177,10 @@ class VecGame:
     ``final_obs=True`` adds the persistent tensors of ``ftl_step_final``, passed on every step except ``auto_reset=True``:
     ``final_obs_num``, ``final_lasers``, ``final_target`` (+ ``final_policy_obs`` with ``policy_obs``) hold the terminal observation
     of the envs whose episode ended in the last ``auto_reset="same_step"`` step (other rows keep older values); ``ended`` u8[N] marks
-    the envs whose episode ended in the last step, ``restarted`` u8[N] the envs it re-initialised (``terminated_truncated()``)."""
+    the envs whose episode ended in the last step, ``restarted`` u8[N] the envs it re-initialised (``terminated_truncated()``).
+
+    Evaluation: ``set_episode_queue`` / ``reset_from_queue`` / ``step(a, auto_reset="queue")`` play a list of scenarios exactly once
+    each, whichever slot is free, with one record per entry (``EpisodeQueue``); ``evaluate(policy, scen_ids)`` is the whole loop."""
 
     def __init__(self, n_envs, device="cuda:0", config: GameConfig = None, policy_obs=False, _outputs=None, final_obs=False, **game_kwargs):
         self.cfg = config if config is not None else make_config(**game_kwargs)
@@ -247,6 +252,8 @@ class VecGame:
         self._fields = {}
         self._window = None
         self._tune = {}
+        self.queue = None
+        self.ticket = None
         self.env_bytes = int(self.lib.ftl_env_bytes(self.h))
         self.layout_id = int(self.lib.ftl_env_layout_id(self.h))
 
@@ -313,7 +320,9 @@ class VecGame:
         ``auto_reset``: False -- finished envs stay done; True -- they are re-initialised inside this step, the outputs keep the terminal
         reward / done / status and the new episode's observation (FTL_STEP_AUTO_RESET); ``"same_step"`` -- True plus the terminal
         observations in the final buffers (needs ``final_obs=True``); ``"next_step"`` -- this step returns the terminal observation, an env
-        that is done on entry is re-initialised instead of stepped (its action ignored; reward 0, done 0, status 0: FTL_STEP_NEXT_RESET).
+        that is done on entry is re-initialised instead of stepped (its action ignored; reward 0, done 0, status 0: FTL_STEP_NEXT_RESET);
+        ``"queue"`` -- a finished env records its episode and takes the next entry of the attached episode queue, or parks
+        (``set_episode_queue``; FTL_STEP_QUEUE_RESET; outputs as under True, the final buffers are filled when the batch has them).
         ``check_errors=True`` synchronises and raises what the reference would have raised in any env (``raise_on_errors``);
         the default leaves the per-env sticky error words for ``error_report()`` so that the step stays asynchronous."""
         action, enc = self._encode_action(action, self.n)
@@ -336,7 +345,52 @@ class VecGame:
             return abi.FTL_STEP_AUTO_RESET, fin
         if auto_reset == "next_step":
             return abi.FTL_STEP_NEXT_RESET, fin
-        raise ValueError('auto_reset must be False, True, "same_step" or "next_step" (got %r)' % (auto_reset,))
+        if auto_reset == "queue":
+            if getattr(self, "queue", None) is None:
+                raise _lib.FtlError('auto_reset="queue" needs set_episode_queue() first')
+            return abi.FTL_STEP_QUEUE_RESET, fin
+        raise ValueError('auto_reset must be False, True, "same_step", "next_step" or "queue" (got %r)' % (auto_reset,))
+
+    # ------------------------------------------------------------------ episode queue (ftl_set_episode_queue, ftl_queue_start)
+    def set_episode_queue(self, scen_ids, stream_ids=None, stream_base=0):
+        """Attach a queue of pool indices ``scen_ids`` [Q] to this batch and return its ``EpisodeQueue``: every entry is played exactly
+        once by whichever slot is free, entry q on random stream ``stream_ids[q]`` (default ``stream_base + q``), and its result goes to
+        row q of the queue's table.  The episode of entry q is what env q of a fresh ``VecGame(Q, env_id_base=stream_base)`` reset on
+        ``scen_ids`` plays under the same actions, whatever ``n_envs`` is.  ``scen_ids`` may be an ``EpisodeQueue`` (the parts of a
+        pipelined batch share one); ``None`` detaches.  Follow with ``reset_from_queue()`` and ``step(a, auto_reset="queue")``.  A queue is
+        not refilled while it drains: attach a new one."""
+        if scen_ids is None:
+            _lib.check(self.lib.ftl_set_episode_queue(self.h, None), self.lib)
+            self.queue = self.ticket = self._queue_c = None
+            return None
+        self._need_pool()
+        q = scen_ids if isinstance(scen_ids, EpisodeQueue) else EpisodeQueue(scen_ids, stream_ids, stream_base, self.device, self.pool.n)
+        ticket = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        c = q.c_struct(ticket)
+        _lib.check(self.lib.ftl_set_episode_queue(self.h, C.byref(c)), self.lib)
+        self.queue, self.ticket, self._queue_c = q, ticket, c
+        return q
+
+    def reset_from_queue(self):
+        """The queue's ``reset()``: slot e takes entry head + e (slots past the end of the queue park: ``ticket`` -1, done set); returns the
+        first observations like ``reset``."""
+        if self.queue is None:
+            raise _lib.FtlError("set_episode_queue() first")
+        _lib.check(self.lib.ftl_queue_start(self.h, C.byref(self._out), self._stream()), self.lib)
+        return self.obs_num, self.lasers
+
+    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None):
+        """Play every scenario of ``scen_ids`` exactly once with ``action = policy((obs_num, lasers))`` and return the records (structured
+        numpy array, ``abi.RECORD_DTYPE``, row q = entry q).  The queue's ``finished()`` count is read (one synchronisation) every
+        ``check_every`` calls.  ``max_calls`` defaults to ceil(Q / n_envs) * (max_steps // least frames per step + 2) + check_every --
+        no hand-out order needs more -- and exceeding it raises instead of spinning.  Detaches the queue afterwards."""
+        q = self.set_episode_queue(scen_ids, stream_ids)
+        try:
+            obs = self.reset_from_queue()
+            _evaluate_loop(self.cfg, self.n, q, lambda: obs, lambda a: self.step(a, auto_reset="queue"), policy, check_every, max_calls)
+            return q.records()
+        finally:
+            self.set_episode_queue(None)
 
     def terminated_truncated(self):
         """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
@@ -431,7 +485,9 @@ class VecGame:
 
     def snapshot(self, env_ids=None):
         """``EnvSnapshot`` of envs ``env_ids`` (env indices of this batch, repeats allowed; None: all) -- the packed state rows and the output
-        rows, enqueued on the current stream.  Tied to the scenario pool as it is now (see ``EnvSnapshot``).  Reads the ids on the host."""
+        rows, enqueued on the current stream.  Tied to the scenario pool as it is now (see ``EnvSnapshot``).  Reads the ids on the host.
+        Refused while an episode queue is attached: the rows would not say which entries their envs are playing."""
+        _refuse_with_queue(self.queue, "snapshot()")
         ids = _host_ids(env_ids, self.n)
         return self._snapshot_ids(ids)
 
@@ -504,7 +560,9 @@ class VecGame:
     def state_dict(self):
         """The whole batch as a checkpoint of plain tensors (``torch.save`` / ``torch.load`` it): every env's row in global env order, with
         its slot records, the output rows, ``env_id_base`` / ``n_envs``, the reset window, the ``tune`` settings and a content digest of
-        the scenario pool.  Synchronises."""
+        the scenario pool.  Synchronises.  Refused while an episode queue is attached (a half-drained queue is not part of a checkpoint:
+        drain it or detach it first)."""
+        _refuse_with_queue(self.queue, "state_dict()")
         self._need_pool()
         snap = self._snapshot_ids(torch.arange(self.n, dtype=torch.int64))
         return dict(format=1, layout_id=self.layout_id, env_id_base=int(self.cfg.c.env_id_base), n_envs=self.n,
@@ -672,6 +730,83 @@ if hasattr(torch.serialization, "add_safe_globals"):       # torch.load(weights_
     torch.serialization.add_safe_globals([EnvSnapshot])
 
 
+class EpisodeQueue:
+    """A list of Q scenarios to be played exactly once each, and the table of their results, on the device (``ftl_episode_queue``).
+
+    Owns the arrays: ``scenario`` i32[Q], ``stream`` i64[Q] or None (entry q then plays on stream ``stream_base + q``), ``head`` i32[1]
+    (the next entry to hand out) and the records.  ``records()`` copies the table to the host (one synchronisation) as a structured numpy
+    array of ``abi.RECORD_DTYPE``: state (0 not started, 1 running, 2 finished), scenario, env (the slot that played it), frames, calls,
+    status[3], errors, flags (``abi.FTL_EPISODE_DONE_AT_RESET``), ret, stream.  ``table()`` gives the columns as device tensors (views of
+    the records, no copy; ``errors`` / ``flags`` as int32 bit patterns); ``finished()`` / ``remaining()`` are device scalars."""
+
+    def __init__(self, scen_ids, stream_ids=None, stream_base=0, device="cuda:0", pool_n=None):
+        self.device = torch.device(device)
+        scen = torch.as_tensor(scen_ids).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        self.n = int(scen.numel())
+        if self.n <= 0:
+            raise ValueError("an episode queue needs at least one entry")
+        if bool((scen < 0).any()) or (pool_n is not None and bool((scen >= pool_n).any())):
+            raise ValueError("scen_ids out of range")
+        self.scenario = scen
+        self.stream, self.stream_base = None, int(stream_base)
+        if stream_ids is not None:
+            st = torch.as_tensor(stream_ids).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+            if st.numel() != self.n:
+                raise ValueError("stream_ids must have one entry per scenario")
+            if bool((st < 0).any()) or bool((st > 2 ** 31 - 1).any()):
+                raise ValueError("stream ids must lie in 0 .. 2**31 - 1")
+            self.stream = st
+        self.head = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._words = C.sizeof(abi.EpisodeRecord) // 8
+        self._rec = torch.zeros(self.n, self._words, dtype=torch.int64, device=self.device)
+
+    def c_struct(self, ticket):
+        """``abi.EpisodeQueueC`` of this queue for a handle whose slots' tickets live in ``ticket`` (i32[n_envs], device)."""
+        c = abi.EpisodeQueueC()
+        c.scenario, c.stream = self.scenario.data_ptr(), (self.stream.data_ptr() if self.stream is not None else None)
+        c.stream_base, c.n = self.stream_base, self.n
+        c.head, c.records, c.ticket = self.head.data_ptr(), self._rec.data_ptr(), ticket.data_ptr()
+        return c
+
+    def records(self):
+        return self._rec[:self.n].cpu().numpy().view(np.dtype(abi.RECORD_DTYPE)).reshape(self.n)
+
+    def table(self):
+        w = self._rec[:self.n].view(torch.int32)          # [Q, 14]
+        return dict(state=w[:, 0], scenario=w[:, 1], env=w[:, 2], frames=w[:, 3], calls=w[:, 4], status=w[:, 5:8], errors=w[:, 8],
+                    flags=w[:, 9], ret=self._rec[:self.n].view(torch.float64)[:, 5], stream=self._rec[:self.n, 6])
+
+    def finished(self):
+        return (self._rec[:self.n].view(torch.int32)[:, 0] == 2).sum()
+
+    def remaining(self):
+        return self.n - self.finished()
+
+
+def _refuse_with_queue(queue, what):
+    if queue is not None:
+        raise _lib.FtlError("%s with an episode queue attached: a half-drained queue cannot be saved -- drain it (evaluate) or detach it "
+                            "(set_episode_queue(None)) first" % what)
+
+
+def _evaluate_loop(cfg, n, q, obs, step, policy, check_every, max_calls):
+    """The loop of ``evaluate``: ``obs()`` -> the observation tuple on the current stream, ``step(action)`` one queue step."""
+    check_every = max(int(check_every), 1)
+    c = cfg.c
+    least = c.rand_fps_lo if c.rand_fps_hi > 0 else c.frames_per_step
+    if max_calls is None:
+        max_calls = -(-q.n // n) * (c.max_steps // least + 2) + check_every
+    calls = 0
+    while True:
+        step(policy(obs()))
+        calls += 1
+        if calls % check_every == 0 or calls >= max_calls:
+            if int(q.finished()) == q.n:
+                return calls
+            if calls >= max_calls:
+                raise _lib.FtlError("evaluate: %d of %d episodes finished after max_calls = %d calls" % (int(q.finished()), q.n, max_calls))
+
+
 def _pool_token(pool):
     return (pool.uid, int(pool.version))
 
@@ -795,6 +930,7 @@ class PipelinedVecGame:
         if self.final_obs and "final_policy_obs" not in outs:
             self.final_policy_obs = None
         self.pool = None
+        self.queue = None
         self._serial = False
         self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, **z)
         self._stream_ptrs = [C.c_void_p(s.cuda_stream) for s in self.streams]
@@ -887,6 +1023,50 @@ class PipelinedVecGame:
             _lib.check(g.lib.ftl_step_final(g.h, base + sh.lo * row, enc, C.byref(g._out), fin, flags, sptr), g.lib)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
 
+    def set_episode_queue(self, scen_ids, stream_ids=None, stream_base=0):
+        """``VecGame.set_episode_queue`` for the whole batch: the parts share ONE queue -- one head, one table -- so every entry is still
+        played exactly once and its record is the same as on one ``VecGame``; which part plays what depends on timing."""
+        if scen_ids is None:
+            for g in self.games:
+                g.set_episode_queue(None)
+            self.queue = None
+            return None
+        if self.pool is None:
+            raise _lib.FtlError("load_scenarios() first")
+        q = scen_ids if isinstance(scen_ids, EpisodeQueue) else EpisodeQueue(scen_ids, stream_ids, stream_base, self.device, self.pool.n)
+        self.join()
+        for g in self.games:
+            g.set_episode_queue(q)
+        self.queue = q
+        return q
+
+    ticket = property(lambda self: torch.cat([g.ticket for g in self.games]) if self.queue is not None else None)
+
+    def reset_from_queue(self):
+        """``VecGame.reset_from_queue`` of every part on its stream, then ``join()``."""
+        if self.queue is None:
+            raise _lib.FtlError("set_episode_queue() first")
+        for k, g in enumerate(self.games):
+            with self._on(k):
+                g.reset_from_queue()
+        self.join()
+        return self.obs_num, self.lasers
+
+    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None):
+        """``VecGame.evaluate`` over the parts; the policy sees the whole batch's rows, so the parts are joined after every step."""
+        q = self.set_episode_queue(scen_ids, stream_ids)
+        try:
+            self.reset_from_queue()
+
+            def obs():
+                self.join()
+                return self.obs_num, self.lasers
+            _evaluate_loop(self.cfg, self.n, q, obs, lambda a: self.step(a, auto_reset="queue"), policy, check_every, max_calls)
+            self.join()
+            return q.records()
+        finally:
+            self.set_episode_queue(None)
+
     def terminated_truncated(self):
         """``VecGame.terminated_truncated`` over all rows: computed on the current stream, so ``join()`` first (or take part k's rows
         of ``ended`` / ``status`` on ``stream(k)``)."""
@@ -962,7 +1142,8 @@ class PipelinedVecGame:
     # snapshot / clone / restore over global env indices: each is a synchronisation point (the parts are joined first, as state_field
     # does); rows move between the parts through ftl_pack_envs / ftl_unpack_envs on the current stream, which the parts' next steps wait for
     def snapshot(self, env_ids=None):
-        """``VecGame.snapshot`` over env indices of the whole batch (joins the parts first)."""
+        """``VecGame.snapshot`` over env indices of the whole batch (joins the parts first).  Refused while an episode queue is attached."""
+        _refuse_with_queue(self.queue, "snapshot()")
         self.join()
         return self._snapshot_ids(_host_ids(env_ids, self.n))
 
@@ -1010,7 +1191,8 @@ class PipelinedVecGame:
         self._restore_ids(self._snapshot_ids(src), dst, slot_stats, own_stream)
 
     def state_dict(self):
-        """``VecGame.state_dict`` of the whole batch (rows of every part in global env order)."""
+        """``VecGame.state_dict`` of the whole batch (rows of every part in global env order).  Refused while an episode queue is attached."""
+        _refuse_with_queue(self.queue, "state_dict()")
         self.join()
         g0 = self.games[0]
         g0._need_pool()

@@ -58,6 +58,8 @@ enum { FTL_LEADER_MOVING = 0, FTL_LEADER_CRASH = 1, FTL_LEADER_FINISHED = 2 };
 #define FTL_ERR_HIST1_OVERFLOW 16u    /* v1 tracker history longer than hist1_cap */
 #define FTL_ERR_LIDAR_OVERFLOW 32u    /* more than 128 objects within range of a LaserSensor: the extra ones were ignored */
 #define FTL_ERR_BAD_ACTION 64u        /* ftl_step_encoded: a Discrete(5) action outside 0..4 (reference: KeyError at ENV:922); stepped as action 2 */
+#define FTL_ERR_BAD_STREAM 128u       /* episode queue: a stream id of ftl_episode_queue.stream outside 0 .. INT32_MAX (sticky word only); the
+                                         entry was played on the id's low 32 bits */
 
 /* robot kinematic limits, px/frame and deg/frame (ENV:330-357, 556-566, 704-714; CLS:59-105) */
 typedef struct ftl_robot_params {
@@ -533,6 +535,71 @@ size_t   ftl_env_bytes(const ftl_handle* h);
 uint64_t ftl_env_layout_id(const ftl_handle* h);
 int ftl_pack_envs(const ftl_handle* h, const int32_t* env_ids, int32_t k, void* rows, void* stream);
 int ftl_unpack_envs(ftl_handle* h, const void* rows, const int32_t* env_ids, int32_t k, uint32_t flags, void* stream);
+
+/* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
+ * replay) ---------------------------------------------------------------------------------------------------------------------------
+ * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
+ * window and so play MORE episodes in the slots whose episodes are short.  Here the caller attaches a queue of Q pool indices; each entry
+ * is played once, by whichever slot is free; its result goes to row q of `records`; a slot that finds the queue empty parks.
+ *
+ * Equivalence (the contract): the episode played for entry q -- every observation, reward and status of it, and its record -- is what env q
+ * of a FRESH handle with env_id_base = s0, reset with scen_idx = the queue and stepped without auto-reset, gives under the same actions,
+ * where s0 + q is the entry's stream id.  It is a pure function of (config, pool entry, stream id, actions): neither the slot, nor the
+ * handle, nor what the slot played before enters.  To that end a slot that takes an entry gets the random-stream words of a fresh env:
+ * FTL_EI_STREAM = stream id - env_id_base - slot, and FTL_EI_RESETS, FTL_EI_FPS, FTL_EI_ACC_CONSUMED zeroed as in a zeroed state buffer.
+ * Stream ids lie in 0 .. INT32_MAX (the step kernels key their draws by a 32-bit id); with stream == NULL that is checked at attach time
+ * (FTL_E_INVALID), otherwise on the device (FTL_ERR_BAD_STREAM in the slot's sticky error word).
+ *
+ * ftl_queue_start is the queue's ftl_reset: slot e = 0 .. n_envs - 1 takes entry head + e (one fetch-add of n_envs on head), is placed and
+ * scanned exactly as ftl_reset does, and `out` holds the first observations.  Slots past the end of the queue park: ticket -1; they are
+ * placed on the queue's entry 0 and their done word is set, so that they step like a finished env without auto-reset (ENV:908-945 steps a
+ * finished env as well).  Outputs of parked slots mean nothing (their done byte stays 1).
+ *
+ * ftl_step_final / ftl_step_encoded / ftl_step with FTL_STEP_QUEUE_RESET: a step without auto-reset (the sensors scan the terminal state of
+ * the envs that finish), then ftl_queue_kernel: every slot whose done byte is set and whose ticket is >= 0 writes the record of its entry
+ * from its terminal state and output rows and takes the next entry; then, with `fin`, the terminal rows are copied as under
+ * FTL_STEP_AUTO_RESET; then the masked reset pass of ftl_step_final places the slots that took an entry (`out` keeps the terminal reward /
+ * done / status and gets the new episode's observation, as under FTL_STEP_AUTO_RESET).  fin->ended = a record was written, fin->restarted =
+ * a new entry was taken.  Within one call the finishing slots take entries in ascending slot order: base = fetch-add(head, number of
+ * finishing slots), once per call, then base + rank; an entry index >= n is not taken -- the slot parks.  One handle is therefore
+ * deterministic down to which slot played what.  Several handles (the parts of a pipelined batch) may share head, records and the entry
+ * arrays, each with a ticket array of its own: then who plays what depends on timing, the records do not.
+ * A world that is done at reset (empty route, ENV:508-510) is recorded by the next call with frames 0, calls 0, ret 0, status 0/0/0 and
+ * FTL_EPISODE_DONE_AT_RESET, and counts as one episode in "ep_stats"; `errors` then holds what that one call raised.
+ * "ep_stats", FTL_EI_EPISODES and the sticky error word keep their bookkeeping: ftl_episode_metrics over a drained queue equals the column
+ * sums of the records.  Combined with another reset flag: FTL_E_INVALID; without a queue attached: FTL_E_STATE.
+ * ftl_set_episode_queue copies the struct (the arrays stay the caller's, alive and unchanged while attached; head and ticket are written by
+ * the library only, records too); it touches no device memory.  NULL detaches: the handle is then exactly what it was before. */
+#define FTL_STEP_QUEUE_RESET 8u
+#define FTL_EPISODE_DONE_AT_RESET 1u
+typedef struct ftl_episode_record {   /* one row per queue entry, written once */
+    int32_t state;        /* 0 not started, 1 running, 2 finished */
+    int32_t scenario;     /* pool index it ran on */
+    int32_t env;          /* slot of the handle that ran it */
+    int32_t frames;       /* step_count at done (ENV:944) */
+    int32_t calls;        /* ftl_step* calls the episode took (while state is 1: the handle's call counter when the entry was taken) */
+    int32_t status[3];    /* mission / agent / leader status of the terminal step */
+    uint32_t errors;      /* FTL_ERR_* bits the episode raised */
+    uint32_t flags;       /* FTL_EPISODE_DONE_AT_RESET: the world was done at reset */
+    double  ret;          /* overall_reward at done (ENV:943) */
+    int64_t stream;       /* the stream id it was played with */
+} ftl_episode_record;
+size_t ftl_sizeof_episode_record(void);
+
+typedef struct ftl_episode_queue {    /* all pointers are DEVICE pointers the caller owns */
+    const int32_t* scenario;   /* [Q] */
+    const int64_t* stream;     /* [Q] or NULL: stream id of entry q = stream_base + q */
+    int64_t  stream_base;
+    int32_t  n;                /* Q */
+    int32_t  _pad;
+    int32_t* head;             /* [1]  next entry to hand out; may be SHARED by several handles */
+    ftl_episode_record* records;  /* [Q] */
+    int32_t* ticket;           /* [n_envs] entry each slot is playing, -1 = parked */
+} ftl_episode_queue;
+size_t ftl_sizeof_episode_queue(void);
+
+int ftl_set_episode_queue(ftl_handle* h, const ftl_episode_queue* q);   /* NULL detaches */
+int ftl_queue_start(ftl_handle* h, const ftl_outputs* out, void* stream);
 
 const char* ftl_last_error(void);
 
