@@ -161,6 +161,8 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
     if (!h) return fail(FTL_E_DEVICE, "out of host memory");
     memset(&h->P, 0, sizeof h->P);
     h->P.cfg = *cfg;
+    // (which pass a sensor belongs to is a flag: the host tables and the kernels compare it with 0 / 1)
+    for (int k = 0; k < FTL_MAX_LASERS; k++) h->P.cfg.lasers[k].after_tracker = cfg->lasers[k].after_tracker ? 1 : 0;
     h->device = device;
     h->bound = false; h->have_scen = false; h->dP = nullptr; h->dirty = true;
     h->rg_mem = nullptr; h->rg_tot = nullptr; h->rg_parity = 0; h->rg_launches = 0; h->mt_mem = nullptr; h->timing = false; h->tev_used = 0;
@@ -211,15 +213,11 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
     P.lasers_len = off; P.total_rays = rays; P.hmax = hmax;
     {   // ray directions relative to the heading (glibc cos / sin, as the reference's np.cos(np.radians(.))) and the no-hit reading
         const double deg2rad = 3.141592653589793 / 180.0;
-        int g = 0; bool miss_ok = true;
+        bool miss_ok = true;
         const double span = (double)(cfg->width > cfg->height ? cfg->width : cfg->height);
         const double margin = 1e-11 * (span > 2048.0 ? span / 2048.0 : 1.0);
         for (int k = 0; k < cfg->n_lasers; k++) {
             const ftl_laser_cfg& l = cfg->lasers[k];
-            for (int i = 0; i < l.count && g < FTL_MAX_RAYS; i++, g++) {
-                const double a = l.explicit_angles ? l.ray_angles[i & 7] : l.angle_offset + i * (360.0 / (double)l.count);
-                P.ray_rot[g][0] = cos(a * deg2rad); P.ray_rot[g][1] = sin(a * deg2rad);
-            }
             // float64 |end - origin| = laser_length within 4e-13 (coordinates < 2048): float32(.) is float32(laser_length) unless a
             // rounding boundary of float32 lies that close
             miss_ok = miss_ok && (float)(l.length - margin) == (float)l.length && (float)(l.length + margin) == (float)l.length;
@@ -234,12 +232,28 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
             rs.reach2 = ((float)l.length + 2.0f) * ((float)l.length + 2.0f);
             rs.inv_step = (float)l.count * 0.15915494309189535f; rs.inv_count = 1.0f / (float)l.count;
             rs.off_u = (float)(l.angle_offset * deg2rad) * rs.inv_step;
-            rs.slack = 0.02f + 0.01f * (float)l.count * 0.15915494f;
+            rs.slack = 0.022f + 0.01f * (float)l.count * 0.15915494f;   // 0.01 rad + 0.022 ray spacings (0.002 of them: the arc is scaled per sensor after it was
+                                                                        // normalised in radians -- float32 roundings of values below 2 x count)
             rs.flags = ((ro == 1 || ro == 2) ? 1u : 0u) | ((ro == 1 || ro == 3) ? 2u : 0u) | (l.react_corridor ? 4u : 0u) | (l.react_green ? 8u : 0u)
                      | (l.explicit_angles ? 16u : 0u) | (which ? 32u : 0u) | (l.compas ? 64u : 0u);
             if (!l.compas) rb[which] += l.count;
         }
         P.inv_nrect_dyn = (65536u + (unsigned)(P.R - 1) - 1u) / (unsigned)(P.R - 1);
+        // per-ray records of phase 2, rays in pass order: the sensors scanned before the tracker, then those scanned after it
+        int g = 0;
+        for (int which = 0; which < 2; which++) {
+            P.pass_base[which] = g; P.pass_lmax[which] = 0.0f;
+            for (int k = 0; k < cfg->n_lasers; k++) {
+                const ftl_laser_cfg& l = cfg->lasers[k];
+                if ((l.after_tracker ? 1 : 0) != which || l.compas) continue;
+                P.pass_lmax[which] = fmaxf(P.pass_lmax[which], (float)l.length);
+                for (int i = 0; i < l.count && g < FTL_MAX_RAYS; i++, g++) {
+                    const double a = l.explicit_angles ? l.ray_angles[i & 7] : l.angle_offset + i * (360.0 / (double)l.count);
+                    P.ray_dir[g].c = cos(a * deg2rad); P.ray_dir[g].s = sin(a * deg2rad); P.ray_dir[g].len = l.length;
+                }
+            }
+            P.pass_rays[which] = g - P.pass_base[which];
+        }
     }
     if (rays > 1023) { delete h; return fail(FTL_E_INVALID, "more than 1023 rays per env (the candidate list of the ray kernel packs a ray index into 10 bits)"); }
     if (hmax * (P.R - 1) > FTL_WAVE) { delete h; return fail(FTL_E_INVALID, "max_prev_obs x (1 + bears) exceeds one wavefront of snapshot rects"); }

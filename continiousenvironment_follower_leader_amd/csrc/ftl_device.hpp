@@ -19,6 +19,7 @@
 // fuse); the translation unit is compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/ftl.h"
@@ -45,9 +46,17 @@ struct FtlRaySensor {
     float slack;                   // widening of the candidate arc, in ray spacings (>= 0.01 rad)
     uint32_t flags;                // bits 0-3: reacts to SEG_STATIC / DYNAMIC / CORRIDOR / GREEN; 16: explicit ray angles; 32: scanned after the tracker; 64: not a ray-kernel sensor (compas)
 };
+// per-ray record of the ray kernel's phase 2 (built on the host in ftl_create).  Rays in PASS order: the rays of the sensors scanned
+// before the tracker (config order, compas entries left out), then those of the sensors scanned after it -- a lane loads the record of its
+// ray instead of searching the sensor list for it
+// (32 bytes, 16-byte aligned: the lane reads (c, s) with one 16-byte load, and a record never crosses a 64-byte line)
+struct alignas(16) FtlRayDir { double c, s, len, _pad; };   // (cos, sin) of the ray's angle relative to the heading (glibc), laser_length
 struct FtlDevParams {
     ftl_config cfg;
     int32_t n_envs, R, lasers_len, total_rays, hmax, lds_rays;
+    int32_t pass_rays[2], pass_base[2];   // rays of the sensors scanned before / after the tracker, and where they start in ray_dir
+    float pass_lmax[2];               // longest laser_length of the pass (float32)
+    int32_t _pad_pass[2];             // (keeps ray_dir below on a 32-byte boundary: static_assert behind the struct)
     int32_t fr_rec_off, fr_rec_stride, fr_pend_off, fr_env_off, fr_defer, fr_lds;   // frame kernel: LDS offsets of the frame records / pending items / slot -> env table
                                       // (+ the item counter), "the later frames' position searches wait for the end of the step", total dynamic LDS
     int32_t corr_lds_cap;             // corridor points the ray kernel stages in LDS (a power of two <= cfg.corr_cap; a longer window is read in place)
@@ -68,8 +77,8 @@ struct FtlDevParams {
     double* fol_cs;                   // [n_envs][2]: cos, sin of the follower's direction as the frame kernel leaves it (one sincos per lane
                                       // there serves 16 envs; here it would be one per ray)
     // ray directions relative to the follower's heading, host-computed with glibc: (cos, sin) of (first_laser_angle_offset + i * 360 / N)
-    // -- or of ray_angles[i] -- in degrees, indexed by the ray's position over ALL ray sensors in config order
-    double ray_rot[FTL_MAX_RAYS][2];
+    // -- or of ray_angles[i] -- in degrees, and the ray's length; pass order (above)
+    FtlRayDir ray_dir[FTL_MAX_RAYS];
     FtlRaySensor ray_sens[FTL_MAX_LASERS];   // phase 3 of the ray kernel: what it needs of each sensor, packed (two scalar loads)
     uint32_t inv_nrect_dyn;           // ceil(65536 / (R - 1)): source index / objects per snapshot without an integer division
     int32_t miss_const;               // 1: a ray without a hit reads float32(laser_length) exactly for every sensor (checked on the host: the
@@ -79,6 +88,7 @@ struct FtlDevParams {
     int32_t* perm; uint8_t* keys; uint16_t* rank; int32_t* bh;
     ftl_scenarios scen;
 };
+static_assert(sizeof(FtlRayDir) == 32 && offsetof(FtlDevParams, ray_dir) % 32 == 0, "ray_dir: 16-byte loads of its records must be aligned, and a record must not straddle a cache line (the device copy is 256-byte aligned)");
 // per-call arguments (passed by value in the kernarg segment)
 struct FtlCall {
     const double* action; const int32_t* scen_idx; const uint8_t* mask;
@@ -527,9 +537,9 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
         int lane_v = (int)threadIdx.x;
         asm volatile("" : "+v"(lane_v));
         const int lane = lane_v;
-        int n_sens = 0; float lmax = 0.0f;
-        FTL_FOR_LASERS(k) if (c.lasers[k].after_tracker == which) { n_sens++; lmax = fmaxf(lmax, (float)c.lasers[k].length); }
-        if (n_sens == 0) continue;
+        const int n_rays = P.pass_rays[which], pbase = P.pass_base[which];      // the rays of the pass's sensors share one index space
+        if (n_rays == 0) continue;
+        const float lmax = P.pass_lmax[which];
         // this lane's snapshot rect and static rect: requested here, with the pass's other loads, and dead after phase 1 (held across
         // the passes they cost the test loop of phase 3 eight registers)
         // (with room for both in one wavefront -- 37 + 10 lanes on the bench workload -- the snapshot rects sit in the lanes behind the
@@ -652,23 +662,12 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
         // ---- phase 2: ray ends + accumulators; the rays of ALL sensors of this group share one index space (a sensor
         // of 12 rays alone would leave 52 lanes idle through the f64 sin/cos)
         {
-            int n_rays = 0;
-            FTL_FOR_LASERS(k) if (c.lasers[k].after_tracker == which) n_rays += c.lasers[k].count;
             for (int g = lane; g < n_rays; g += FTL_WAVE) {
-                int i = g, gi = 0, gb = 0; double len = 0; bool found = false;
-#pragma unroll
-                for (int k = 0; k < FTL_MAX_LASERS; k++) if (k < c.n_lasers) {       // (every sensor: the rotation table is indexed over all of them)
-                    const int N = c.lasers[k].count;
-                    if (c.lasers[k].after_tracker == which && !(EXPL && c.lasers[k].compas)) {
-                        if (!found && i < N) { found = true; len = c.lasers[k].length; gi = gb + i; }
-                        if (!found) i -= N;
-                    }
-                    gb += N;
-                }
                 // direction of ray i = heading + offset_i (sensors.py:888-891, 609-632): cos / sin by angle addition from the heading's
                 // (frame kernel) and the offset's (host) -- within 2-3 ulp of the reference's cos(radians(heading + offset_i)), like the
-                // device's own sincos
-                const double2 rot = reinterpret_cast<const double2*>(&P.ray_rot[0][0])[gi];
+                // device's own sincos.  The offset's cos / sin and the ray's length come from the ray's host-built record.
+                const double2 rot = *reinterpret_cast<const double2*>(&P.ray_dir[pbase + g].c);
+                const double len = P.ray_dir[pbase + g].len;
                 const double co = fcd * rot.x - fsd * rot.y, s = fsd * rot.x + fcd * rot.y;
                 const double ex = (double)cx + co * len, ey = (double)cy + s * len;
                 s_ray[g] = make_double2(ex, ey);
@@ -754,14 +753,19 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
                 }
                 FTL_RTIC(3);
                 float4 sg = make_float4(0.f, 0.f, 0.f, 0.f); unsigned sm = 0;
-                float angA = 0.0f, angB = 0.0f, dmin2 = 3.0e38f;
+                // the arc, once for all sensors: where it starts (radians from the heading, any turn) and how wide it is (<= pi)
+                float a0 = 0.0f, wd = 0.0f, dmin2 = 3.0e38f;
                 if (m >= 0) {
                     fetch(mq, m, sg, sm);
                     if (sm == 0u) m = -1;                    // (unstaged corridor spans list every segment: one outside all windows faces no ray)
                 }
                 if (m >= 0) {
                     const float ax = sg.x - cx, ay = sg.y - cy, bx = sg.z - cx, by = sg.w - cy;
-                    angA = arc_atan2(ay, ax); angB = arc_atan2(by, bx);
+                    const float angA = arc_atan2(ay, ax), angB = arc_atan2(by, bx);
+                    float diff = angB - angA; if (diff < 0.0f) diff += 6.283185307179586f;
+                    a0 = angA; wd = diff;
+                    if (diff > 3.141592653589793f) { a0 = angB; wd = 6.283185307179586f - diff; }
+                    a0 -= fdir_rad;
                     // closest approach of the segment to the follower (culling only: 2 px of slack in the records' reach)
                     const float ex_ = bx - ax, ey_ = by - ay;
                     const float l2 = __builtin_fmaf(ex_, ex_, ey_ * ey_);
@@ -789,19 +793,18 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
                     const int N = rs.count, rbase = rs.rbase;
                     int i0 = 0, cnt = 0;
                     if (m >= 0 && ((rs.flags >> mq) & 1u) && !(dmin2 > rs.reach2)) {      // the sensor reacts to this class and can reach the segment
-                        // candidate rays: the arc [uA, uB] the segment subtends, in units of the ray spacing from ray 0
+                        // candidate rays: the arc in units of this sensor's ray spacing from its ray 0.  The slack (>= 0.01 rad, and 0.022
+                        // spacings on top) dwarfs what the arc can be off by -- 2e-5 rad per arc_atan2 and a few float32 roundings of values
+                        // below 2 N -- so the rays listed here always include every ray the reference's test can accept.
                         const float fN = (float)N;
-                        const float phis = __builtin_fmaf(fdir_rad, rs.inv_step, rs.off_u);
-                        float uA = __builtin_fmaf(angA, rs.inv_step, -phis), uB = __builtin_fmaf(angB, rs.inv_step, -phis);
-                        uA = __builtin_fmaf(-floorf(uA * rs.inv_count), fN, uA); uB = __builtin_fmaf(-floorf(uB * rs.inv_count), fN, uB);   // into [0, N) (an ulp outside is absorbed by the wrap below)
-                        float diff = uB - uA; if (diff < 0.0f) diff += fN;
-                        float start = uA, wd = diff;
-                        if (diff > 0.5f * fN) { start = uB; wd = fN - diff; }
-                        if ((rs.flags & 16u) || dmin2 < 4.0f || wd > 0.5f * fN - 0.05f) { i0 = 0; cnt = N; }   // through / next to the origin, or rays
+                        const float wu = wd * rs.inv_step;
+                        if ((rs.flags & 16u) || dmin2 < 4.0f || wu > 0.5f * fN - 0.05f) { i0 = 0; cnt = N; }   // through / next to the origin, or rays
                                                                                               // at explicit angles (<= 7 of them): every ray
                         else {
-                            i0 = (int)ceilf(start - rs.slack);                              // slack >= 0.01 rad, far above float error
-                            cnt = (int)floorf(start + wd + rs.slack) - i0 + 1;
+                            float st = __builtin_fmaf(a0, rs.inv_step, -rs.off_u);
+                            st = __builtin_fmaf(-floorf(st * rs.inv_count), fN, st);           // into [0, N) (an ulp outside is absorbed by the wrap below)
+                            i0 = (int)ceilf(st - rs.slack);
+                            cnt = (int)floorf(st + wu + rs.slack) - i0 + 1;
                             cnt = cnt > N ? N : cnt;
                         }
                     }
@@ -880,8 +883,6 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
             if constexpr (!EXPL) {
                 // One RAY per lane, the rays of all sensors of the pass in one index space (as in phase 2); the lane writes its ray's H rows
                 // (one (ray, age) pair per lane, below, takes three rounds on the bench workload and fifteen under a 180-ray sensor).
-                int n_rays = 0;
-                FTL_FOR_LASERS(k) if (c.lasers[k].after_tracker == which) n_rays += c.lasers[k].count;
                 for (int g = lane; g < n_rays; g += FTL_WAVE) {
                     int i = g, H = 0, N = 0, ooff = 0, poff = -1; float flen = 1.0f; bool found = false;
                     FTL_FOR_LASERS(k) if (c.lasers[k].after_tracker == which) {
