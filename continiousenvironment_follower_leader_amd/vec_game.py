@@ -5,7 +5,9 @@ follow_the_leader_continuous_env.py:434-543, 908-945).
 PyTorch is used for plumbing only: it owns the device buffers (state blob, scenario pool, outputs) and the
 stream; all arithmetic happens in ``libftl_hip.so`` behind the C-ABI of ``include/ftl.h``."""
 import ctypes as C
+import dataclasses
 import hashlib
+import math
 import uuid
 from contextlib import nullcontext as _nullcontext
 
@@ -14,6 +16,7 @@ import torch
 
 from . import _lib, abi
 from .config import GameConfig, make_config
+from .shard import shard_range
 
 _DT = {0: torch.int32, 1: torch.float32, 2: torch.float64}
 
@@ -166,7 +169,217 @@ def error_for_bits(bits, n_envs=1):
                          "reference -- raise the capacity in make_config()" % (", ".join(names) or hex(bits), where))
 
 
-class VecGame:
+def _output_table(cfg, policy_obs, final_obs):
+    """name -> (shape after the env axis, dtype) of the per-env output tensors of a batch, in the order snapshots carry them: the step
+    outputs, ``policy_obs`` when asked for and the config has sensors for it, and with ``final_obs`` their ``final_`` twins plus the
+    ``ended`` / ``restarted`` masks.  A new per-env output is one row here."""
+    f32, f64, u8 = torch.float32, torch.float64, torch.uint8
+    t = dict(obs_num=((abi.FTL_OBS_NUM,), f32), lasers=((max(cfg.lasers_len, 1),), f32), target=((2,), f64), reward=((), f64),
+             done=((), u8), status=((3,), u8))
+    # fused ContinuousObserveModifier_sensorPrev output (wrappers.py:169-221): [n, H, sum of row widths], float32, over the
+    # sensor classes the wrapper concatenates (LaserSpec.in_policy_obs), in dict order
+    sel = [l for l in cfg.lasers if l.in_policy_obs]
+    if policy_obs and sel:
+        hs = {l.history for l in sel}
+        if len(hs) != 1:
+            raise ValueError("policy_obs needs the same max_prev_obs on every sensor it concatenates (wrappers.py:207, 217 assert it)")
+        t["policy_obs"] = ((hs.pop(), sum(l.width for l in sel)), f32)
+    if final_obs:                              # ftl_final_outputs: terminal rows + ended / restarted masks
+        t.update(final_obs_num=t["obs_num"], final_lasers=t["lasers"], final_target=t["target"], ended=((), u8), restarted=((), u8))
+        if "policy_obs" in t:
+            t["final_policy_obs"] = t["policy_obs"]
+    return t
+
+
+class _BatchBase:
+    """What ``VecGame`` and ``PipelinedVecGame`` share: every call whose body is the same once the parts have been waited for.
+
+    A subclass provides ``_wait_parts()`` (the current stream waits for whatever steps the batch on other streams), the per-ids
+    operations ``_snapshot_ids`` / ``_restore_ids`` / ``_render_ids`` and the attributes ``cfg``, ``n``, ``device``, ``pool``, ``queue``,
+    ``layout_id``, ``env_bytes``, ``_window``, ``_tune``."""
+
+    def _set_outputs(self, outs, final_obs):
+        """Keep the output tensors ``outs`` (name -> tensor, the rows of ``_output_table``) as attributes and as ``output_rows()``."""
+        self.final_obs = bool(final_obs)
+        self.policy_obs = None
+        if self.final_obs:
+            self.final_policy_obs = None
+        for name, t in outs.items():
+            setattr(self, name, t)
+        self._rows = outs
+
+    def output_rows(self):
+        """name -> the per-env output tensors a snapshot carries: the step outputs, ``policy_obs`` and the final buffers when enabled."""
+        return self._rows
+
+    def _need_pool(self):
+        if self.pool is None:
+            raise _lib.FtlError("load_scenarios() first")
+
+    def _need_queue(self):
+        if self.queue is None:
+            raise _lib.FtlError("set_episode_queue() first")
+
+    def _reset_args(self, scen_idx, mask):
+        """(scen_idx i32[N], mask u8[N] or None) of a ``reset`` call as contiguous device tensors, checked."""
+        self._need_pool()
+        if scen_idx is None:
+            scen_idx = torch.arange(self.n, dtype=torch.int32, device=self.device) % self.pool.n
+        scen_idx = torch.as_tensor(scen_idx, dtype=torch.int32, device=self.device).contiguous()
+        if scen_idx.numel() != self.n:
+            raise ValueError("scen_idx must have one entry per env")
+        if bool((scen_idx < 0).any()) or bool((scen_idx >= self.pool.n).any()):
+            raise ValueError("scen_idx out of range")
+        if mask is not None:
+            mask = torch.as_tensor(mask, dtype=torch.uint8, device=self.device).contiguous()
+        return scen_idx, mask
+
+    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None):
+        """Play every scenario of ``scen_ids`` exactly once with ``action = policy((obs_num, lasers))`` and return the records (structured
+        numpy array, ``abi.RECORD_DTYPE``, row q = entry q).  The queue's ``finished()`` count is read (one synchronisation) every
+        ``check_every`` calls.  ``max_calls`` defaults to ceil(Q / n_envs) * (max_steps // least frames per step + 2) + check_every --
+        no hand-out order needs more -- and exceeding it raises instead of spinning.  Detaches the queue afterwards.  The policy sees the
+        whole batch's rows, so the parts of a pipelined batch are joined after every step."""
+        q = self.set_episode_queue(scen_ids, stream_ids)
+        try:
+            self.reset_from_queue()
+
+            def obs():
+                self._wait_parts()
+                return self.obs_num, self.lasers
+            _evaluate_loop(self.cfg, self.n, q, obs, lambda a: self.step(a, auto_reset="queue"), policy, check_every, max_calls)
+            self._wait_parts()
+            return q.records()
+        finally:
+            self.set_episode_queue(None)
+
+    def terminated_truncated(self):
+        """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
+        truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap
+        continues from the terminal observation), terminated = ended and not truncated.  The statuses are the reference's own: it tests
+        the step limit after the crash tests of the frame, so a crash in the frame that reaches max_steps reads as a time-out.
+        Computed on the current stream: on a pipelined batch ``join()`` first (or take part k's rows of ``ended`` / ``status`` on
+        ``stream(k)``)."""
+        if not self.final_obs:
+            raise ValueError("terminated_truncated() needs %s(..., final_obs=True)" % type(self).__name__)
+        ended = self.ended.bool()
+        truncated = ended & (self.status[:, 0] == abi.MISSION.index("finished_by_time"))
+        return ended & ~truncated, truncated
+
+    # ------------------------------------------------------------------ snapshot / clone / restore (ftl_pack_envs, ftl_unpack_envs)
+    # over env indices of the whole batch; on a pipelined batch each is a synchronisation point (the parts are joined first, as
+    # state_field does): rows move between the parts on the current stream, which the parts' next steps wait for
+    def snapshot(self, env_ids=None):
+        """``EnvSnapshot`` of envs ``env_ids`` (env indices of this batch, repeats allowed; None: all) -- the packed state rows and the output
+        rows, enqueued on the current stream.  Tied to the scenario pool as it is now (see ``EnvSnapshot``).  Reads the ids on the host.
+        Refused while an episode queue is attached: the rows would not say which entries their envs are playing."""
+        _refuse_with_queue(self.queue, "snapshot()")
+        self._wait_parts()
+        ids = _host_ids(env_ids, self.n)
+        self._need_pool()
+        return self._snapshot_ids(ids)
+
+    def restore(self, snap, env_ids=None, slot_stats=False, own_stream=False):
+        """Write the envs of ``snap`` into envs ``env_ids`` of this batch (distinct indices, one per snapshot row; None: 0 .. len(snap) - 1):
+        their state and their output rows, so that ``obs_num`` etc. show the restored envs at once.  Each env then continues its source's
+        episode bit for bit under the same actions: it keeps its source's random stream (``own_stream=True``: the destination's own, which
+        diverges on the first random draw).  ``slot_stats=True`` also moves the slot's episode records (``ep_stats``, episode count, sticky
+        error word: ``episode_metrics`` counts the source's episodes again); by default the destination keeps its own.  Raises ValueError,
+        with nothing written, for ids out of range or repeated, a snapshot of another layout, or a pool that changed since the snapshot."""
+        self._wait_parts()
+        ids = _host_ids(env_ids, self.n) if env_ids is not None else torch.arange(len(snap), dtype=torch.int64)
+        self._check_snapshot(snap, ids)
+        self._restore_ids(snap, ids, slot_stats, own_stream)
+
+    def _check_snapshot(self, snap, ids):
+        self._need_pool()
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("restore() takes an EnvSnapshot")
+        if snap.layout_id != self.layout_id:
+            raise ValueError("the snapshot was taken from a batch of another layout (config, capacities or sensors differ)")
+        if snap.pool_token != _pool_token(self.pool):
+            raise ValueError("the scenario pool is not the one the snapshot was taken on, or it was written since (ScenarioPool.write, a "
+                             "moving ScenarioRing / DeviceScenarioRing): snapshots are tied to the pool contents")
+        if int(ids.numel()) != len(snap):
+            raise ValueError("%d destination ids for %d snapshot rows" % (ids.numel(), len(snap)))
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
+            raise ValueError("env_ids outside [0, %d)" % self.n)
+        if torch.unique(ids).numel() != ids.numel():
+            raise ValueError("duplicate destination env ids")
+        missing = [k for k in self.output_rows() if k not in snap.outputs]
+        if missing:
+            raise ValueError("the snapshot lacks the output rows %s of this batch" % missing)
+
+    def clone(self, src_ids, dst_ids, slot_stats=False, own_stream=False):
+        """Copy envs ``src_ids`` into envs ``dst_ids`` (``restore`` of a ``snapshot``: every source is read before any destination is written,
+        so a destination may also be a source, e.g. a permutation; on a pipelined batch they may lie in different parts).  The search
+        case: one env into K slots, each stepped with another action."""
+        self._wait_parts()
+        src, dst = _host_ids(src_ids, self.n), _host_ids(dst_ids, self.n)
+        if src.numel() != dst.numel():
+            raise ValueError("src_ids and dst_ids differ in length")
+        if torch.unique(dst).numel() != dst.numel():
+            raise ValueError("duplicate destination env ids")
+        self._need_pool()
+        self._restore_ids(self._snapshot_ids(src), dst, slot_stats, own_stream)
+
+    def state_dict(self):
+        """The whole batch as a checkpoint of plain tensors (``torch.save`` / ``torch.load`` it): every env's row in global env order, with
+        its slot records, the output rows, ``env_id_base`` / ``n_envs``, the reset window, the ``tune`` settings (none for a pipelined
+        batch: its parts keep their own) and a content digest of the scenario pool.  Synchronises.  Refused while an episode queue is
+        attached (a half-drained queue is not part of a checkpoint: drain it or detach it first)."""
+        _refuse_with_queue(self.queue, "state_dict()")
+        self._wait_parts()
+        self._need_pool()
+        snap = self._snapshot_ids(torch.arange(self.n, dtype=torch.int64))
+        return dict(format=1, layout_id=self.layout_id, env_id_base=int(self.cfg.c.env_id_base), n_envs=self.n,
+                    rows=snap.rows.cpu(), outputs={k: v.cpu() for k, v in snap.outputs.items()},
+                    reset_window=self._window, tune=dict(self._tune), pool_n=int(self.pool.n), pool_digest=self.pool.digest())
+
+    # ------------------------------------------------------------------ views
+    def laser_view(self, name):
+        for l in self.cfg.lasers:
+            if l.name == name:
+                return self.lasers[:, l.out_offset:l.out_offset + l.history * l.width].view(self.n, l.history, l.width)
+        raise KeyError(name)
+
+    def aux_view(self, name):
+        """Output block of a LaserSensor / LeaderTrackDetector_vector / _radar sensor: float32 ``[n_envs, *shape]`` with the shape
+        the reference's ``scan`` returns (SEN:131-134, 381, 476)."""
+        for a in self.cfg.aux:
+            if a.name == name:
+                return self.lasers[:, a.out_offset:a.out_offset + a.out_len].view(self.n, *a.shape)
+        raise KeyError(name)
+
+    # ------------------------------------------------------------------ rendering (ftl_render)
+    def render_layers(self):
+        """FTL_RENDER_* bits of the constructor's show_* flags (ENV:267-272); the target ring is always drawn (ENV:1278)."""
+        return _render_layers(self.cfg)
+
+    def render(self, env_ids=None, scale=1.0, size=None, origin=(0, 0), layers=None, out=None):
+        """Top-down RGB frames of envs ``env_ids`` (env indices, repeats allowed; None: all) as a uint8 device tensor ``[k, H, W, 3]``
+        (row-major ``[y][x][rgb]``, the reference's ``render()`` matrix), enqueued on the current stream without a host synchronisation.
+        ``scale``: world pixels per output pixel; ``size``: (W, H) in output pixels (default: the world at this scale); ``origin``: world
+        coordinate of the top-left corner; ``layers``: FTL_RENDER_* bits (None: the constructor's show_* flags); ``out``: a contiguous
+        uint8 ``[k, H, W, 3]`` tensor to write into (e.g. frame t of a ``[T, k, H, W, 3]`` recording).  Reads the state and the outputs of
+        the last reset / step, writes nothing else (include/ftl.h, ftl_render).  Memory: the image is k * H * W * 3 bytes and the cached
+        workspace about k * (route_cap + traj_cap + ...) * 32 bytes (59 KB per env on config B) -- ``env_ids=None`` on a 65,536-env batch
+        asks for 3.9 GB of workspace and, at scale 1, 295 GB of frames: pass the envs to record.  The workspace of the last k is kept
+        until the next call with another k (``release_render_workspace`` frees it).  On a pipelined batch the ids may span parts and the
+        call is a synchronisation point: it joins the parts and reads the ids on the host."""
+        self._wait_parts()
+        return self._render_ids(_render_ids(env_ids, self.n, self.device), scale, size, origin, layers, out)
+
+    def _render_out(self, k, w, h, out):
+        """The tensor ``render`` writes ``k`` frames of ``w`` x ``h`` into: ``out`` checked, or a new one."""
+        if out is None:
+            return torch.empty(k, h, w, 3, dtype=torch.uint8, device=self.device)
+        if tuple(out.shape) != (k, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous uint8 tensor [%d, %d, %d, 3] on %s" % (k, h, w, self.device))
+        return out
+
+
+class VecGame(_BatchBase):
     """N parallel envs on one GPU.
 
     ``reset(scen_idx, mask)`` / ``step(action, auto_reset)`` return views of persistent device tensors:
@@ -201,53 +414,27 @@ class VecGame:
         base = self.state.data_ptr()
         self._state_off = (-base) % 256
         _lib.check(self.lib.ftl_bind_state(self.h, base + self._state_off, nbytes), self.lib)
-        L = max(self.cfg.lasers_len, 1)
-        z = dict(device=self.device)
-        def out(name, *shape, dtype):          # an output tensor of this batch, or the rows of a larger one that the caller owns (PipelinedVecGame)
+        outs = {}
+        for name, (shape, dtype) in _output_table(self.cfg, policy_obs, final_obs).items():
             if _outputs is None:
-                return torch.zeros(self.n, *shape, dtype=dtype, **z)
-            t = _outputs[name]
+                outs[name] = torch.zeros(self.n, *shape, dtype=dtype, device=self.device)
+                continue
+            t = outs[name] = _outputs[name]    # the rows of a larger tensor that the caller owns (PipelinedVecGame)
             if tuple(t.shape) != (self.n, *shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
                 raise ValueError("output tensor %r does not fit this batch" % name)
-            return t
-        self.obs_num = out("obs_num", abi.FTL_OBS_NUM, dtype=torch.float32)
-        self.lasers = out("lasers", L, dtype=torch.float32)
-        self.target = out("target", 2, dtype=torch.float64)
-        self.reward = out("reward", dtype=torch.float64)
-        self.done = out("done", dtype=torch.uint8)
-        self.status = out("status", 3, dtype=torch.uint8)
-        o = abi.Outputs()
-        o.obs_num, o.lasers, o.target = self.obs_num.data_ptr(), self.lasers.data_ptr(), self.target.data_ptr()
-        o.reward, o.done, o.status = self.reward.data_ptr(), self.done.data_ptr(), self.status.data_ptr()
-        # fused ContinuousObserveModifier_sensorPrev output (wrappers.py:169-221): [n, H, sum of row widths], float32, over the
-        # sensor classes the wrapper concatenates (LaserSpec.in_policy_obs), in dict order
-        sel = [l for l in self.cfg.lasers if l.in_policy_obs]
-        hs = {l.history for l in sel}
-        self.policy_obs = None
-        if policy_obs and sel:
-            if len(hs) != 1:
-                raise ValueError("policy_obs needs the same max_prev_obs on every sensor it concatenates (wrappers.py:207, 217 assert it)")
-            self.policy_obs = out("policy_obs", hs.pop(), sum(l.width for l in sel), dtype=torch.float32)
-            o.policy_obs = self.policy_obs.data_ptr()
-        self.final_obs = bool(final_obs)
-        self._fin = None
-        if self.final_obs:                     # ftl_final_outputs: terminal rows + ended / restarted masks
-            self.final_obs_num = out("final_obs_num", abi.FTL_OBS_NUM, dtype=torch.float32)
-            self.final_lasers = out("final_lasers", L, dtype=torch.float32)
-            self.final_target = out("final_target", 2, dtype=torch.float64)
-            self.final_policy_obs = None
-            if self.policy_obs is not None:
-                self.final_policy_obs = out("final_policy_obs", *self.policy_obs.shape[1:], dtype=torch.float32)
-            self.ended = out("ended", dtype=torch.uint8)
-            self.restarted = out("restarted", dtype=torch.uint8)
-            f = abi.FinalOutputs()
-            f.obs_num, f.lasers, f.target = self.final_obs_num.data_ptr(), self.final_lasers.data_ptr(), self.final_target.data_ptr()
-            f.policy_obs = self.final_policy_obs.data_ptr() if self.final_policy_obs is not None else None
-            f.ended, f.restarted = self.ended.data_ptr(), self.restarted.data_ptr()
-            self._fin = f
-        self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, **z)
-        self._errors = torch.zeros(2, dtype=torch.int32, **z)
-        self._out = o
+        self._set_outputs(outs, final_obs)
+        o, f = abi.Outputs(), abi.FinalOutputs()
+        for field, _ in abi.Outputs._fields_:
+            if field in outs:
+                setattr(o, field, outs[field].data_ptr())
+        for field, _ in abi.FinalOutputs._fields_:      # a field that ftl_outputs has too is that output's final_ twin
+            t = outs.get("final_" + field if hasattr(o, field) else field)
+            if t is not None:
+                setattr(f, field, t.data_ptr())
+        self._fin = f if self.final_obs else None
+        self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, device=self.device)
+        self._errors = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._out, self._out_ref = o, C.byref(o)
         self.pool = None
         self._fields = {}
         self._window = None
@@ -294,19 +481,8 @@ class VecGame:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def reset(self, scen_idx=None, mask=None, check_errors=False, live_errors=False):
-        if self.pool is None:
-            raise _lib.FtlError("load_scenarios() first")
-        if scen_idx is None:
-            scen_idx = torch.arange(self.n, dtype=torch.int32, device=self.device) % self.pool.n
-        scen_idx = torch.as_tensor(scen_idx, dtype=torch.int32, device=self.device).contiguous()
-        if scen_idx.numel() != self.n:
-            raise ValueError("scen_idx must have one entry per env")
-        if bool((scen_idx < 0).any()) or bool((scen_idx >= self.pool.n).any()):
-            raise ValueError("scen_idx out of range")
-        mptr = None
-        if mask is not None:
-            mask = torch.as_tensor(mask, dtype=torch.uint8, device=self.device).contiguous()
-            mptr = mask.data_ptr()
+        scen_idx, mask = self._reset_args(scen_idx, mask)
+        mptr = mask.data_ptr() if mask is not None else None
         self._keep = (scen_idx, mask)
         _lib.check(self.lib.ftl_reset(self.h, scen_idx.data_ptr(), mptr, C.byref(self._out), self._stream()), self.lib)
         if check_errors:
@@ -327,10 +503,15 @@ class VecGame:
         the default leaves the per-env sticky error words for ``error_report()`` so that the step stays asynchronous."""
         action, enc = self._encode_action(action, self.n)
         flags, fin = self._step_mode(auto_reset)
-        _lib.check(self.lib.ftl_step_final(self.h, action.data_ptr(), enc, C.byref(self._out), fin, flags, self._stream()), self.lib)
+        self._step_final(action.data_ptr(), enc, flags, fin, self._stream())
         if check_errors:
             self.raise_on_errors(live_errors)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
+
+    def _step_final(self, action_ptr, enc, flags, fin, stream):
+        """The one call of ``ftl_step_final``: ``action_ptr`` the device address of this batch's first action row, ``fin`` as
+        ``_step_mode`` gives it, ``stream`` a ``c_void_p``."""
+        _lib.check(self.lib.ftl_step_final(self.h, action_ptr, enc, self._out_ref, fin, flags, stream), self.lib)
 
     def _step_mode(self, auto_reset):
         """(FTL_STEP_* flags, ftl_final_outputs pointer or None) of a ``step(auto_reset=...)`` value."""
@@ -374,32 +555,9 @@ class VecGame:
     def reset_from_queue(self):
         """The queue's ``reset()``: slot e takes entry head + e (slots past the end of the queue park: ``ticket`` -1, done set); returns the
         first observations like ``reset``."""
-        if self.queue is None:
-            raise _lib.FtlError("set_episode_queue() first")
+        self._need_queue()
         _lib.check(self.lib.ftl_queue_start(self.h, C.byref(self._out), self._stream()), self.lib)
         return self.obs_num, self.lasers
-
-    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None):
-        """Play every scenario of ``scen_ids`` exactly once with ``action = policy((obs_num, lasers))`` and return the records (structured
-        numpy array, ``abi.RECORD_DTYPE``, row q = entry q).  The queue's ``finished()`` count is read (one synchronisation) every
-        ``check_every`` calls.  ``max_calls`` defaults to ceil(Q / n_envs) * (max_steps // least frames per step + 2) + check_every --
-        no hand-out order needs more -- and exceeding it raises instead of spinning.  Detaches the queue afterwards."""
-        q = self.set_episode_queue(scen_ids, stream_ids)
-        try:
-            obs = self.reset_from_queue()
-            _evaluate_loop(self.cfg, self.n, q, lambda: obs, lambda a: self.step(a, auto_reset="queue"), policy, check_every, max_calls)
-            return q.records()
-        finally:
-            self.set_episode_queue(None)
-
-    def terminated_truncated(self):
-        """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
-        truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap
-        continues from the terminal observation), terminated = ended and not truncated.  The statuses are the reference's own: it tests
-        the step limit after the crash tests of the frame, so a crash in the frame that reaches max_steps reads as a time-out."""
-        if not self.final_obs:
-            raise ValueError("terminated_truncated() needs VecGame(..., final_obs=True)")
-        return _terminated_truncated(self.ended, self.status)
 
     def _encode_action(self, action, n):
         """(tensor to hand to ftl_step_encoded, FTL_ACTION_* encoding) for an action of ``n`` envs of this config (ENV:909-925)."""
@@ -474,25 +632,11 @@ class VecGame:
         if bits:
             raise error_for_bits(bits, n)
 
-    # ------------------------------------------------------------------ snapshot / clone / restore (ftl_pack_envs, ftl_unpack_envs)
-    def output_rows(self):
-        """name -> the per-env output tensors a snapshot carries: the step outputs, ``policy_obs`` and the final buffers when enabled."""
-        names = list(_OUT_NAMES) + (["policy_obs"] if self.policy_obs is not None else [])
-        if self.final_obs:
-            names += ["final_obs_num", "final_lasers", "final_target", "ended", "restarted"]
-            names += ["final_policy_obs"] if self.final_policy_obs is not None else []
-        return {k: getattr(self, k) for k in names}
-
-    def snapshot(self, env_ids=None):
-        """``EnvSnapshot`` of envs ``env_ids`` (env indices of this batch, repeats allowed; None: all) -- the packed state rows and the output
-        rows, enqueued on the current stream.  Tied to the scenario pool as it is now (see ``EnvSnapshot``).  Reads the ids on the host.
-        Refused while an episode queue is attached: the rows would not say which entries their envs are playing."""
-        _refuse_with_queue(self.queue, "snapshot()")
-        ids = _host_ids(env_ids, self.n)
-        return self._snapshot_ids(ids)
+    # ------------------------------------------------------------------ the per-ids operations under snapshot / restore / clone
+    def _wait_parts(self):
+        pass
 
     def _snapshot_ids(self, ids):
-        self._need_pool()
         k = int(ids.numel())
         rows = torch.empty(k, self.env_bytes, dtype=torch.uint8, device=self.device)
         dev = ids.to(device=self.device, dtype=torch.int32)
@@ -501,37 +645,6 @@ class VecGame:
         idx = dev.long()
         outs = {name: t.index_select(0, idx) for name, t in self.output_rows().items()}
         return EnvSnapshot(rows, outs, self.layout_id, _pool_token(self.pool))
-
-    def restore(self, snap, env_ids=None, slot_stats=False, own_stream=False):
-        """Write the envs of ``snap`` into envs ``env_ids`` of this batch (distinct indices, one per snapshot row; None: 0 .. len(snap) - 1):
-        their state and their output rows, so that ``obs_num`` etc. show the restored envs at once.  Each env then continues its source's
-        episode bit for bit under the same actions: it keeps its source's random stream (``own_stream=True``: the destination's own, which
-        diverges on the first random draw).  ``slot_stats=True`` also moves the slot's episode records (``ep_stats``, episode count, sticky
-        error word: ``episode_metrics`` counts the source's episodes again); by default the destination keeps its own.  Raises ValueError,
-        with nothing written, for ids out of range or repeated, a snapshot of another layout, or a pool that changed since the snapshot."""
-        ids = _host_ids(env_ids, self.n) if env_ids is not None else torch.arange(len(snap), dtype=torch.int64)
-        self._check_snapshot(snap, ids)
-        self._restore_ids(snap, ids, slot_stats, own_stream)
-
-    def _check_snapshot(self, snap, ids, n=None):
-        n = self.n if n is None else n
-        self._need_pool()
-        if not isinstance(snap, EnvSnapshot):
-            raise TypeError("restore() takes an EnvSnapshot")
-        if snap.layout_id != self.layout_id:
-            raise ValueError("the snapshot was taken from a batch of another layout (config, capacities or sensors differ)")
-        if snap.pool_token != _pool_token(self.pool):
-            raise ValueError("the scenario pool is not the one the snapshot was taken on, or it was written since (ScenarioPool.write, a "
-                             "moving ScenarioRing / DeviceScenarioRing): snapshots are tied to the pool contents")
-        if int(ids.numel()) != len(snap):
-            raise ValueError("%d destination ids for %d snapshot rows" % (ids.numel(), len(snap)))
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
-            raise ValueError("env_ids outside [0, %d)" % n)
-        if torch.unique(ids).numel() != ids.numel():
-            raise ValueError("duplicate destination env ids")
-        missing = [k for k in self.output_rows() if k not in snap.outputs]
-        if missing:
-            raise ValueError("the snapshot lacks the output rows %s of this batch" % missing)
 
     def _restore_ids(self, snap, ids, slot_stats, own_stream):
         k = int(ids.numel())
@@ -545,29 +658,6 @@ class VecGame:
         idx = dev.long()
         for name, t in self.output_rows().items():
             t.index_copy_(0, idx, snap.outputs[name].to(self.device))
-
-    def clone(self, src_ids, dst_ids, slot_stats=False, own_stream=False):
-        """Copy envs ``src_ids`` into envs ``dst_ids`` (``restore`` of a ``snapshot``: every source is read before any destination is written,
-        so a destination may also be a source, e.g. a permutation).  The search case: one env into K slots, each stepped with another action."""
-        src, dst = _host_ids(src_ids, self.n), _host_ids(dst_ids, self.n)
-        if src.numel() != dst.numel():
-            raise ValueError("src_ids and dst_ids differ in length")
-        if torch.unique(dst).numel() != dst.numel():
-            raise ValueError("duplicate destination env ids")
-        self._need_pool()
-        self._restore_ids(self._snapshot_ids(src), dst, slot_stats, own_stream)
-
-    def state_dict(self):
-        """The whole batch as a checkpoint of plain tensors (``torch.save`` / ``torch.load`` it): every env's row in global env order, with
-        its slot records, the output rows, ``env_id_base`` / ``n_envs``, the reset window, the ``tune`` settings and a content digest of
-        the scenario pool.  Synchronises.  Refused while an episode queue is attached (a half-drained queue is not part of a checkpoint:
-        drain it or detach it first)."""
-        _refuse_with_queue(self.queue, "state_dict()")
-        self._need_pool()
-        snap = self._snapshot_ids(torch.arange(self.n, dtype=torch.int64))
-        return dict(format=1, layout_id=self.layout_id, env_id_base=int(self.cfg.c.env_id_base), n_envs=self.n,
-                    rows=snap.rows.cpu(), outputs={k: v.cpu() for k, v in snap.outputs.items()},
-                    reset_window=self._window, tune=dict(self._tune), pool_n=int(self.pool.n), pool_digest=self.pool.digest())
 
     def load_state_dict(self, sd, apply_tune=True, _digest=None):
         """Continue a checkpoint of ``state_dict``: this batch takes the rows whose global env ids (env_id_base + index) it owns, with their
@@ -599,25 +689,7 @@ class VecGame:
                 t.pop("coscheduled_envs")
             self.tune(**t)
 
-    def _need_pool(self):
-        if self.pool is None:
-            raise _lib.FtlError("load_scenarios() first")
-
-    # ------------------------------------------------------------------ views
-    def laser_view(self, name):
-        for l in self.cfg.lasers:
-            if l.name == name:
-                return self.lasers[:, l.out_offset:l.out_offset + l.history * l.width].view(self.n, l.history, l.width)
-        raise KeyError(name)
-
-    def aux_view(self, name):
-        """Output block of a LaserSensor / LeaderTrackDetector_vector / _radar sensor: float32 ``[n_envs, *shape]`` with the shape
-        the reference's ``scan`` returns (SEN:131-134, 381, 476)."""
-        for a in self.cfg.aux:
-            if a.name == name:
-                return self.lasers[:, a.out_offset:a.out_offset + a.out_len].view(self.n, *a.shape)
-        raise KeyError(name)
-
+    # ------------------------------------------------------------------ views of the state
     def follower_info(self, name):
         """FollowerInfo.scan for every env (SEN:834-842): float32 [n, speed_direction_param] = (follower speed / max_speed,
         direction / 360, then ones) -- two divisions on the state, done with torch on the device."""
@@ -643,24 +715,7 @@ class VecGame:
                 self._fields[name] = torch.as_strided(self.state[a:a + span + (-span) % esz].view(tdt), (self.n, per.value), (st.value // esz, 1))
         return self._fields[name]
 
-    # ------------------------------------------------------------------ rendering (ftl_render)
-    def render_layers(self):
-        """FTL_RENDER_* bits of the constructor's show_* flags (ENV:267-272); the target ring is always drawn (ENV:1278)."""
-        return _render_layers(self.cfg)
-
-    def render(self, env_ids=None, scale=1.0, size=None, origin=(0, 0), layers=None, out=None):
-        """Top-down RGB frames of envs ``env_ids`` (env indices, repeats allowed; None: all) as a uint8 device tensor ``[k, H, W, 3]``
-        (row-major ``[y][x][rgb]``, the reference's ``render()`` matrix), enqueued on the current stream without a host synchronisation.
-        ``scale``: world pixels per output pixel; ``size``: (W, H) in output pixels (default: the world at this scale); ``origin``: world
-        coordinate of the top-left corner; ``layers``: FTL_RENDER_* bits (None: the constructor's show_* flags); ``out``: a contiguous
-        uint8 ``[k, H, W, 3]`` tensor to write into (e.g. frame t of a ``[T, k, H, W, 3]`` recording).  Reads the state and the outputs of
-        the last reset / step, writes nothing else (include/ftl.h, ftl_render).  Memory: the image is k * H * W * 3 bytes and the cached
-        workspace about k * (route_cap + traj_cap + ...) * 32 bytes (59 KB per env on config B) -- ``env_ids=None`` on a 65,536-env batch
-        asks for 3.9 GB of workspace and, at scale 1, 295 GB of frames: pass the envs to record.  The workspace of the last k is kept
-        until the next call with another k (``release_render_workspace`` frees it)."""
-        ids = _render_ids(env_ids, self.n, self.device)
-        return self._render_ids(ids, scale, size, origin, layers, out)
-
+    # ------------------------------------------------------------------ rendering (ftl_render): the hook under render()
     def release_render_workspace(self):
         """Free the workspace ``render`` keeps for its last k (the memory returns to torch's caching allocator)."""
         self._render_ws = None
@@ -670,10 +725,7 @@ class VecGame:
         if k == 0:
             raise ValueError("no env to render")
         rp, (w, h) = _render_params(self.cfg, scale, size, origin, layers)
-        if out is None:
-            out = torch.empty(k, h, w, 3, dtype=torch.uint8, device=self.device)
-        elif tuple(out.shape) != (k, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous uint8 tensor [%d, %d, %d, 3] on %s" % (k, h, w, self.device))
+        out = self._render_out(k, w, h, out)
         ws = getattr(self, "_render_ws", None)
         if ws is None or ws[0] != k:           # the workspace of the last k is kept (a recorder renders the same k again and again)
             nb = C.c_size_t()
@@ -699,9 +751,6 @@ class VecGame:
         else:
             hist = self.state_field("hist")[env].view(cap, 2)[idx].cpu().numpy()
         return hist, corr
-
-
-_OUT_NAMES = ("obs_num", "lasers", "target", "reward", "done", "status")
 
 
 class EnvSnapshot:
@@ -849,7 +898,6 @@ def _render_ids(env_ids, n, device):
 
 
 def _render_params(cfg, scale, size, origin, layers):
-    import math
     scale = float(scale)
     if not scale > 0 or not math.isfinite(scale):
         raise ValueError("scale must be positive")
@@ -863,13 +911,16 @@ def _render_params(cfg, scale, size, origin, layers):
     return rp, (w, h)
 
 
-def _terminated_truncated(ended, status):
-    ended = ended.bool()
-    truncated = ended & (status[:, 0] == abi.MISSION.index("finished_by_time"))
-    return ended & ~truncated, truncated
+def _split_ids(ids, shards, games):
+    """Split env indices of a whole batch (int64 host tensor, any order, repeats allowed) over its parts: for every part that owns some
+    of them ``(game, positions in ids, the part's own indices of those envs)``.  A new per-ids operation is one loop over this."""
+    for g, sh in zip(games, shards):
+        pos = torch.nonzero((ids >= sh.lo) & (ids < sh.hi)).reshape(-1)
+        if pos.numel():
+            yield g, pos, ids[pos] - sh.lo
 
 
-class PipelinedVecGame:
+class PipelinedVecGame(_BatchBase):
     """A batch of N envs stepped as ``parts`` independent sub-batches, each on its own HIP stream of this process.
 
     Envs never interact, so part k's step t+1 depends on nothing but part k's step t.  Run that way -- no join between the parts --
@@ -886,30 +937,13 @@ class PipelinedVecGame:
     and feeding ``step_part(k, action_k)`` -- the double-buffered sampling loop of asynchronous RL frameworks."""
 
     def __init__(self, n_envs, parts=2, device="cuda:0", config: GameConfig = None, policy_obs=False, final_obs=False, **game_kwargs):
-        import dataclasses
-        from .shard import shard_range
         cfg = config if config is not None else make_config(**game_kwargs)
         self.cfg, self.n, self.device = cfg, int(n_envs), torch.device(device)
         if parts < 1 or parts > self.n:
             raise ValueError("parts must be in 1..n_envs")
-        z = dict(device=self.device)
-        L = max(cfg.lasers_len, 1)
-        outs = dict(obs_num=torch.zeros(self.n, abi.FTL_OBS_NUM, dtype=torch.float32, **z), lasers=torch.zeros(self.n, L, dtype=torch.float32, **z),
-                    target=torch.zeros(self.n, 2, dtype=torch.float64, **z), reward=torch.zeros(self.n, dtype=torch.float64, **z),
-                    done=torch.zeros(self.n, dtype=torch.uint8, **z), status=torch.zeros(self.n, 3, dtype=torch.uint8, **z))
-        sel = [l for l in cfg.lasers if l.in_policy_obs]
-        if policy_obs and sel:
-            hs = {l.history for l in sel}
-            if len(hs) != 1:
-                raise ValueError("policy_obs needs the same max_prev_obs on every sensor it concatenates (wrappers.py:207, 217 assert it)")
-            outs["policy_obs"] = torch.zeros(self.n, hs.pop(), sum(l.width for l in sel), dtype=torch.float32, **z)
-        self.final_obs = bool(final_obs)
-        if self.final_obs:                     # the final buffers of VecGame(final_obs=True), rows of shared tensors like the outputs
-            outs.update(final_obs_num=torch.zeros_like(outs["obs_num"]), final_lasers=torch.zeros_like(outs["lasers"]),
-                        final_target=torch.zeros_like(outs["target"]), ended=torch.zeros_like(outs["done"]),
-                        restarted=torch.zeros_like(outs["done"]))
-            if "policy_obs" in outs:
-                outs["final_policy_obs"] = torch.zeros_like(outs["policy_obs"])
+        # ONE set of output tensors; the parts write their row ranges
+        outs = {name: torch.zeros(self.n, *shape, dtype=dtype, device=self.device)
+                for name, (shape, dtype) in _output_table(cfg, policy_obs, final_obs).items()}
         self.shards = [shard_range(self.n, k, parts) for k in range(parts)]
         self.games, self.streams = [], []
         for sh in self.shards:
@@ -923,20 +957,19 @@ class PipelinedVecGame:
                 g.tune(two_streams=0, coscheduled_envs=self.n, regroup_every=8)
             self.games.append(g)
             self.streams.append(torch.cuda.Stream(device=self.device))
-        for k, v in outs.items():
-            setattr(self, k, v)
-        if "policy_obs" not in outs:
-            self.policy_obs = None
-        if self.final_obs and "final_policy_obs" not in outs:
-            self.final_policy_obs = None
+        self._set_outputs(outs, final_obs)
         self.pool = None
         self.queue = None
         self._serial = False
-        self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, **z)
+        self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, device=self.device)
         self._stream_ptrs = [C.c_void_p(s.cuda_stream) for s in self.streams]
         self._ev = torch.cuda.Event()
 
     parts = property(lambda self: len(self.games))
+    layout_id = property(lambda self: self.games[0].layout_id)
+    env_bytes = property(lambda self: self.games[0].env_bytes)
+    _window = property(lambda self: self.games[0]._window)
+    _tune = property(lambda self: {})          # (a checkpoint of the whole batch carries no hints: the parts keep their own)
 
     def close(self):
         for g in self.games:
@@ -963,6 +996,8 @@ class PipelinedVecGame:
         for s in self.streams:
             cur.wait_stream(s)
 
+    _wait_parts = join
+
     def load_scenarios(self, pool: ScenarioPool):
         self.pool = pool
         for g in self.games:
@@ -980,15 +1015,7 @@ class PipelinedVecGame:
         return torch.cat([g.state_field(name) for g in self.games], 0)
 
     def reset(self, scen_idx=None, mask=None):
-        if self.pool is None:
-            raise _lib.FtlError("load_scenarios() first")
-        if scen_idx is None:
-            scen_idx = torch.arange(self.n, dtype=torch.int32, device=self.device) % self.pool.n
-        scen_idx = torch.as_tensor(scen_idx, dtype=torch.int32, device=self.device).contiguous()
-        if scen_idx.numel() != self.n:
-            raise ValueError("scen_idx must have one entry per env")
-        if mask is not None:
-            mask = torch.as_tensor(mask, dtype=torch.uint8, device=self.device).contiguous()
+        scen_idx, mask = self._reset_args(scen_idx, mask)
         for k, (g, sh) in enumerate(zip(self.games, self.shards)):
             with self._on(k):
                 g.reset(scen_idx[sh.lo:sh.hi], None if mask is None else mask[sh.lo:sh.hi])
@@ -1020,7 +1047,7 @@ class PipelinedVecGame:
             else:
                 stream.wait_event(self._ev)
                 action.record_stream(stream)       # (the caller may drop the tensor right away: its memory must outlive the part's read)
-            _lib.check(g.lib.ftl_step_final(g.h, base + sh.lo * row, enc, C.byref(g._out), fin, flags, sptr), g.lib)
+            g._step_final(base + sh.lo * row, enc, flags, fin, sptr)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
 
     def set_episode_queue(self, scen_ids, stream_ids=None, stream_base=0):
@@ -1031,8 +1058,7 @@ class PipelinedVecGame:
                 g.set_episode_queue(None)
             self.queue = None
             return None
-        if self.pool is None:
-            raise _lib.FtlError("load_scenarios() first")
+        self._need_pool()
         q = scen_ids if isinstance(scen_ids, EpisodeQueue) else EpisodeQueue(scen_ids, stream_ids, stream_base, self.device, self.pool.n)
         self.join()
         for g in self.games:
@@ -1044,35 +1070,12 @@ class PipelinedVecGame:
 
     def reset_from_queue(self):
         """``VecGame.reset_from_queue`` of every part on its stream, then ``join()``."""
-        if self.queue is None:
-            raise _lib.FtlError("set_episode_queue() first")
+        self._need_queue()
         for k, g in enumerate(self.games):
             with self._on(k):
                 g.reset_from_queue()
         self.join()
         return self.obs_num, self.lasers
-
-    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None):
-        """``VecGame.evaluate`` over the parts; the policy sees the whole batch's rows, so the parts are joined after every step."""
-        q = self.set_episode_queue(scen_ids, stream_ids)
-        try:
-            self.reset_from_queue()
-
-            def obs():
-                self.join()
-                return self.obs_num, self.lasers
-            _evaluate_loop(self.cfg, self.n, q, obs, lambda a: self.step(a, auto_reset="queue"), policy, check_every, max_calls)
-            self.join()
-            return q.records()
-        finally:
-            self.set_episode_queue(None)
-
-    def terminated_truncated(self):
-        """``VecGame.terminated_truncated`` over all rows: computed on the current stream, so ``join()`` first (or take part k's rows
-        of ``ended`` / ``status`` on ``stream(k)``)."""
-        if not self.final_obs:
-            raise ValueError("terminated_truncated() needs PipelinedVecGame(..., final_obs=True)")
-        return _terminated_truncated(self.ended, self.status)
 
     def episode_metrics(self, clear=False):
         self.join()
@@ -1095,118 +1098,48 @@ class PipelinedVecGame:
         for g in self.games:
             g.raise_on_errors(live)
 
-    def laser_view(self, name):
-        for l in self.cfg.lasers:
-            if l.name == name:
-                return self.lasers[:, l.out_offset:l.out_offset + l.history * l.width].view(self.n, l.history, l.width)
-        raise KeyError(name)
-
-    def aux_view(self, name):
-        for a in self.cfg.aux:
-            if a.name == name:
-                return self.lasers[:, a.out_offset:a.out_offset + a.out_len].view(self.n, *a.shape)
-        raise KeyError(name)
-
-    def render_layers(self):
-        return _render_layers(self.cfg)
-
     def release_render_workspace(self):
         for g in self.games:
             g.release_render_workspace()
 
-    def render(self, env_ids=None, scale=1.0, size=None, origin=(0, 0), layers=None, out=None):
-        """``VecGame.render`` over env indices of the whole batch (ids may span parts, repeats allowed).  A synchronisation point: it
-        joins the parts and reads the ids on the host; the frames are then enqueued on the current stream."""
-        self.join()
-        ids = _render_ids(env_ids, self.n, self.device).cpu().numpy().astype(np.int64)
-        if ids.size and (ids.min() < 0 or ids.max() >= self.n):
+    # the per-ids operations over global env indices: one pass of _split_ids each, the parts' results scattered back by position
+    def _render_ids(self, ids, scale, size, origin, layers, out):
+        ids = ids.cpu().long()
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n):
             raise ValueError("env_ids outside [0, %d)" % self.n)
         _, (w, h) = _render_params(self.cfg, scale, size, origin, layers)
-        k = len(ids)
-        if out is None:
-            out = torch.empty(k, h, w, 3, dtype=torch.uint8, device=self.device)
-        elif tuple(out.shape) != (k, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous uint8 tensor [%d, %d, %d, 3] on %s" % (k, h, w, self.device))
-        for g, sh in zip(self.games, self.shards):
-            sel = np.nonzero((ids >= sh.lo) & (ids < sh.hi))[0]
-            if sel.size == 0:
-                continue
-            local = torch.from_numpy((ids[sel] - sh.lo).astype(np.int32)).to(self.device)
-            if sel.size == k:                  # every id in this part: straight into out
+        k = int(ids.numel())
+        out = self._render_out(k, w, h, out)
+        for g, pos, local in _split_ids(ids, self.shards, self.games):
+            local = local.to(device=self.device, dtype=torch.int32)
+            if pos.numel() == k:               # every id in this part: straight into out
                 g._render_ids(local, scale, size, origin, layers, out)
             else:
-                part = g._render_ids(local, scale, size, origin, layers, None)
-                out.index_copy_(0, torch.from_numpy(sel).to(self.device), part)
+                out.index_copy_(0, pos.to(self.device), g._render_ids(local, scale, size, origin, layers, None))
         return out
 
-    # snapshot / clone / restore over global env indices: each is a synchronisation point (the parts are joined first, as state_field
-    # does); rows move between the parts through ftl_pack_envs / ftl_unpack_envs on the current stream, which the parts' next steps wait for
-    def snapshot(self, env_ids=None):
-        """``VecGame.snapshot`` over env indices of the whole batch (joins the parts first).  Refused while an episode queue is attached."""
-        _refuse_with_queue(self.queue, "snapshot()")
-        self.join()
-        return self._snapshot_ids(_host_ids(env_ids, self.n))
-
     def _snapshot_ids(self, ids):
-        g0 = self.games[0]
-        g0._need_pool()
         k = int(ids.numel())
-        rows = torch.empty(k, g0.env_bytes, dtype=torch.uint8, device=self.device)
-        outs = {name: torch.empty((k,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for name, t in g0.output_rows().items()}
-        for g, sh in zip(self.games, self.shards):
-            sel = torch.nonzero((ids >= sh.lo) & (ids < sh.hi)).reshape(-1)
-            if sel.numel() == 0:
-                continue
-            part, dsel = g._snapshot_ids(ids[sel] - sh.lo), sel.to(self.device)
-            rows.index_copy_(0, dsel, part.rows)
+        rows = torch.empty(k, self.env_bytes, dtype=torch.uint8, device=self.device)
+        outs = {name: torch.empty((k,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for name, t in self.output_rows().items()}
+        for g, pos, local in _split_ids(ids, self.shards, self.games):
+            part, dpos = g._snapshot_ids(local), pos.to(self.device)
+            rows.index_copy_(0, dpos, part.rows)
             for name, t in outs.items():
-                t.index_copy_(0, dsel, part.outputs[name])
-        return EnvSnapshot(rows, outs, g0.layout_id, _pool_token(self.pool))
-
-    def restore(self, snap, env_ids=None, slot_stats=False, own_stream=False):
-        """``VecGame.restore`` into env indices of the whole batch (joins the parts first; every check before anything is written)."""
-        self.join()
-        ids = _host_ids(env_ids, self.n) if env_ids is not None else torch.arange(len(snap), dtype=torch.int64)
-        self.games[0]._check_snapshot(snap, ids, self.n)
-        self._restore_ids(snap, ids, slot_stats, own_stream)
+                t.index_copy_(0, dpos, part.outputs[name])
+        return EnvSnapshot(rows, outs, self.layout_id, _pool_token(self.pool))
 
     def _restore_ids(self, snap, ids, slot_stats, own_stream):
-        for g, sh in zip(self.games, self.shards):
-            sel = torch.nonzero((ids >= sh.lo) & (ids < sh.hi)).reshape(-1)
-            if sel.numel() == 0:
-                continue
-            r = sel.to(snap.rows.device)
-            sub = EnvSnapshot(snap.rows.index_select(0, r), {k: v.index_select(0, sel.to(v.device)) for k, v in snap.outputs.items()},
-                              snap.layout_id, snap.pool_token)
-            g._restore_ids(sub, ids[sel] - sh.lo, slot_stats, own_stream)
-
-    def clone(self, src_ids, dst_ids, slot_stats=False, own_stream=False):
-        """``VecGame.clone`` over env indices of the whole batch; sources and destinations may lie in different parts."""
-        self.join()
-        src, dst = _host_ids(src_ids, self.n), _host_ids(dst_ids, self.n)
-        if src.numel() != dst.numel():
-            raise ValueError("src_ids and dst_ids differ in length")
-        if torch.unique(dst).numel() != dst.numel():
-            raise ValueError("duplicate destination env ids")
-        self._restore_ids(self._snapshot_ids(src), dst, slot_stats, own_stream)
-
-    def state_dict(self):
-        """``VecGame.state_dict`` of the whole batch (rows of every part in global env order).  Refused while an episode queue is attached."""
-        _refuse_with_queue(self.queue, "state_dict()")
-        self.join()
-        g0 = self.games[0]
-        g0._need_pool()
-        snap = self._snapshot_ids(torch.arange(self.n, dtype=torch.int64))
-        return dict(format=1, layout_id=g0.layout_id, env_id_base=int(self.cfg.c.env_id_base), n_envs=self.n,
-                    rows=snap.rows.cpu(), outputs={k: v.cpu() for k, v in snap.outputs.items()},
-                    reset_window=g0._window, tune={}, pool_n=int(self.pool.n), pool_digest=self.pool.digest())
+        for g, pos, local in _split_ids(ids, self.shards, self.games):
+            sub = EnvSnapshot(snap.rows.index_select(0, pos.to(snap.rows.device)),
+                              {k: v.index_select(0, pos.to(v.device)) for k, v in snap.outputs.items()}, snap.layout_id, snap.pool_token)
+            g._restore_ids(sub, local, slot_stats, own_stream)
 
     def load_state_dict(self, sd):
         """``VecGame.load_state_dict`` for every part (each takes the rows of its global env ids); the parts keep their own scheduling
         hints.  Joins the parts first."""
         self.join()
-        if self.pool is None:
-            raise _lib.FtlError("load_scenarios() first")
+        self._need_pool()
         digest = self.pool.digest()
         for g in self.games:                    # (every part checks the checkpoint before the first one writes: same layout, same range)
             lo = int(g.cfg.c.env_id_base) - int(sd["env_id_base"])
