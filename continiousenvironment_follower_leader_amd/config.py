@@ -398,6 +398,16 @@ def make_config(game_width=1500, game_height=1000, framerate=500, frames_per_ste
         raise NotImplementedError(f"at most {abi.FTL_MAX_AUX} lidar / detector sensors")
     if len(lasers) > abi.FTL_MAX_LASERS:
         raise NotImplementedError(f"at most {abi.FTL_MAX_LASERS} ray sensors")
+    for l in lasers:
+        # SEN:642-673, 706 / 787 / 908: a ray sensor without corridor and green-zone edges whose obstacle list is always empty (none, or
+        # "dynamic" without bears; game_object_list always holds the leader) gets a 1-D empty edge array, and the reference's
+        # `corridor_lines[:, 0, :]` raises IndexError at the first scan with a corridor -- in reset().  Here such a sensor has no segment
+        # to hit and reads laser_length on every ray, with no error bit (include/ftl.h, "a ray sensor without edges").
+        if not l.compas and not l.react_corridor and not l.react_green and (l.react_obstacles == 0 or (l.react_obstacles == 3 and c.n_bears == 0)):
+            warn("ray sensor {!r} has no edges to react to (react_to_safe_corridor=False, react_to_green_zone=False, react_to_obstacles={}"
+                 "{}): the reference raises IndexError in reset() (too many indices for array, sensors.py:706 / 787 / 908); this build reads "
+                 "laser_length on every ray".format(l.name, {0: "False", 3: "'dynamic'"}[l.react_obstacles],
+                                                    "" if l.react_obstacles == 0 else " without bears"))
     c.n_lasers = len(lasers)
     off = 0
     for k, l in enumerate(lasers):

@@ -82,7 +82,11 @@ typedef struct ftl_laser_cfg {
     int32_t out_offset;       /* filled by the library: offset of this sensor's [history][width] block in `lasers` */
     int32_t pad_sectors;      /* SEN:932-953: rows are [front|right|behind|left], 4*count wide, zeros outside a ray's sector */
     int32_t lenient;          /* 1: LeaderCorridor_lasers_v2 (SEN:736-807) -- one row of the current edges, and a corridor of <= 1 points
-                                 reads laser_length on every ray instead of raising (no FTL_ERR_EMPTY_CORRIDOR) */
+                                 reads laser_length on every ray instead of raising (no FTL_ERR_EMPTY_CORRIDOR).
+                                 A ray sensor without edges -- of any class: react_corridor 0, react_green 0 and react_obstacles 0, or 3
+                                 ("dynamic") with n_bears 0 -- has no segment to hit: every ray reads laser_length and NO error bit is set,
+                                 although the reference raises IndexError in reset() there (its empty edge array is 1-D, SEN:706 / 787 /
+                                 908).  The case is a property of the config alone: make_config warns about it. */
     int32_t in_policy_obs;    /* 1: the sensor is one of the classes ContinuousObserveModifier_sensorPrev concatenates
                                  (LeaderCorridor_Prev_lasers_v2/_v3 and LeaderCorridor_lasers_compas, utils/wrappers.py:204, 214) */
     double length;            /* laser_length, px */

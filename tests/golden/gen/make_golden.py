@@ -15,6 +15,7 @@ Determinism policy:
 Nothing here is imported by the product; the GPU box never runs this file.
 
 usage:  python tests/golden/gen/make_golden.py [--only NAME] [--pool P] [--jobs J]
+        python tests/golden/gen/make_golden.py --fuzz LO:HI [--jobs J]      (the configs of tests/fuzz_configs.py: fuzz_s{seed}.npz)
 """
 import argparse
 import io
@@ -231,7 +232,7 @@ class Runner:
 
     def __init__(self, config_name):
         self.pygame, ENV = import_reference()
-        cfg = CONFIGS[config_name]
+        cfg = CONFIGS[config_name] if isinstance(config_name, str) else config_name      # a name of CONFIGS, or such an entry itself
         self.cfg = cfg
         import copy
         # np.random.randint of random_frames_per_step (ENV:405 in the constructor, ENV:940 at the end of
@@ -465,10 +466,36 @@ def sensor_prev_wrapper(g):
         return None
 
 
-def run_episode(config_name, seed, policy, n_steps, debug_every=1, stop_after_done=3):
+def raise_site(exc):
+    """Where the reference raised: the innermost frame of the traceback that lies in the reference package."""
+    import traceback
+    pkg = os.sep + "continuous_grid_arctic" + os.sep
+    frames = [f for f in traceback.extract_tb(exc.__traceback__) if pkg in f.filename]
+    assert frames, "the exception did not come from the reference"
+    return dict(exception=type(exc).__name__, message=str(exc), file=frames[-1].filename.split(pkg)[-1].replace(os.sep, "/"), line=frames[-1].lineno)
+
+
+def run_episode(config_name, seed, policy, n_steps, debug_every=1, stop_after_done=3, catch=False, label=None):
+    """`catch`: an exception of the reference in reset() or step() ends the record instead of the run -- the scenario and everything
+    recorded before it are kept, meta["raised"] says where it happened (and with which action, for a step)."""
     r = Runner(config_name)
-    obs0 = r.reset(seed)
+    raised = None
+    try:
+        obs0 = r.reset(seed)
+    except Exception as exc:
+        if not catch:
+            raise
+        raised = dict(phase="reset", step=-1, **raise_site(exc))
     g = r.game
+    if raised is not None:                  # reset() had built the world before the first sensor scan raised (ENV:434-543)
+        out = {"scen:" + k: v for k, v in scenario_of(g).items()}
+        for k, dt in (("actions", np.float64), ("reward", np.float64), ("done", np.uint8), ("info", np.uint8)):
+            out[k] = np.zeros((0, 2) if k == "actions" else (0, 3) if k == "info" else (0,), dt)
+        meta = dict(config=label, seed=seed, policy=policy, n_steps=0, debug_every=debug_every,
+                    kwargs=json.loads(json.dumps(r.cfg["kwargs"], default=str)), post=None, laser_names=[],
+                    numpy=np.__version__, tick="frame k sees get_ticks()==k", raised=raised)
+        out["meta"] = np.array(json.dumps(meta))
+        return out
     wrap = sensor_prev_wrapper(g)
     laser_names = [k for k, v in g.follower_sensors.items()
                    if v.get("sensor_class", k) in ("LeaderCorridor_Prev_lasers_v2", "LeaderCorridor_lasers_v2", "LeaderCorridor_lasers",
@@ -497,6 +524,8 @@ def run_episode(config_name, seed, policy, n_steps, debug_every=1, stop_after_do
             a = ram_action(g, rng, policy == "ram_rocks")
         elif policy == "straight":
             a = (0.225 * g.follower.max_speed / 0.25, 0.0)
+        elif policy == "stay":                  # the leader drives away: too_far_from_leader / low_reward under early_stopping
+            a = (0.0, 0.0)
         else:
             raise ValueError(policy)
         kind = r.cfg.get("action")
@@ -512,7 +541,13 @@ def run_episode(config_name, seed, policy, n_steps, debug_every=1, stop_after_do
             obs, rew, done, info = r.step(w)
             a = (0.25, float(w))                                       # np.concatenate([[0.25], action]), ENV:924-925
         else:
-            obs, rew, done, info = r.step(a)
+            try:
+                obs, rew, done, info = r.step(a)
+            except Exception as exc:
+                if not catch:
+                    raise
+                raised = dict(phase="step", step=t, action=[float(a[0]), float(a[1])], **raise_site(exc))
+                break
         acts.append(a)
         rews.append(float(rew))
         dones.append(bool(done))
@@ -548,10 +583,12 @@ def run_episode(config_name, seed, policy, n_steps, debug_every=1, stop_after_do
             out["dbg:" + k] = arr
         else:
             out["dbg:" + k] = np.stack(v)
-    meta = dict(config=config_name, seed=seed, policy=policy, n_steps=len(acts), debug_every=debug_every,
-                kwargs=json.loads(json.dumps(CONFIGS[config_name]["kwargs"], default=str)),
-                post=CONFIGS[config_name]["post"], laser_names=laser_names,
+    meta = dict(config=config_name if label is None else label, seed=seed, policy=policy, n_steps=len(acts), debug_every=debug_every,
+                kwargs=json.loads(json.dumps(r.cfg["kwargs"], default=str)),
+                post=r.cfg["post"], laser_names=laser_names,
                 numpy=np.__version__, tick="frame k sees get_ticks()==k")
+    if raised is not None:
+        meta["raised"] = raised
     out["meta"] = np.array(json.dumps(meta))
     return out
 
@@ -624,6 +661,53 @@ def one_episode(args):
     return name, int(out["done"].sum()), len(out["reward"]), float(out["reward"].sum())
 
 
+# ---- the config space of tests/test_gpu_fuzz.py (tests/fuzz_configs.py), one record per seed -------------------------------------------
+FUZZ_STEPS, FUZZ_LONG = 60, 40
+FUZZ_POLICIES = ("chase_noisy", "random", "chase")
+# seed -> policy, where the rule of fuzz_episode must not choose (say why next to the entry)
+FUZZ_POLICY_OF = {
+    # the three pursuit / random policies never lose the leader within 60 steps, so no record ended by early stopping; a follower that
+    # stands still under this seed's early_stopping is too_far_from_leader at step 56 (still a long episode)
+    6: "stay",
+}
+
+
+def fuzz_kwargs(seed):
+    """draw_config(seed) without the two keys of the build's own random streams: the Runner keys those with seed 0, env 0."""
+    sys.path.insert(0, os.path.dirname(GOLDEN))
+    from fuzz_configs import draw_config
+    kw = draw_config(seed)
+    del kw["rng_seed"], kw["env_id_base"]
+    return kw
+
+
+def fuzz_episode(seed):
+    """The first of FUZZ_POLICIES whose episode reaches FUZZ_LONG steps before its first done, else the longest one.  The world is that of
+    python seed `seed`, or of the first of seed + 1000, seed + 2000, ... whose route the planner finds: a failed D* search returns a
+    15,000-point route that differs from run to run (make_pool drops such scenarios for the same reason), and a record must be reproducible."""
+    entry = dict(kwargs=fuzz_kwargs(seed), post=None)
+    policies = [FUZZ_POLICY_OF[seed]] if seed in FUZZ_POLICY_OF else list(FUZZ_POLICIES)
+    best, best_len = None, -1
+    for world in range(seed, seed + 20000, 1000):
+        first = run_episode(entry, world, policies[0], FUZZ_STEPS, catch=True, label="fuzz_s%03d" % seed)
+        if bool(first["scen:found_target_point"]):
+            break
+    else:
+        raise RuntimeError("no plannable world for fuzz seed %d" % seed)
+    for policy in policies:
+        out = first if policy == policies[0] else run_episode(entry, world, policy, FUZZ_STEPS, catch=True, label="fuzz_s%03d" % seed)
+        d = np.flatnonzero(out["done"])
+        n = int(d[0]) if len(d) else len(out["done"])
+        if n > best_len:
+            best, best_len = out, n
+        if n >= FUZZ_LONG or json.loads(str(out["meta"])).get("raised", {}).get("phase") == "reset":
+            break
+    path = os.path.join(GOLDEN, "fuzz_s%03d.npz" % seed)
+    np.savez_compressed(path, **best)
+    meta = json.loads(str(best["meta"]))
+    return seed, meta["seed"], meta["policy"], len(best["done"]), best_len, meta.get("raised"), os.path.getsize(path)
+
+
 def pool_worker(args):
     config_name, seeds = args
     r = Runner(config_name)
@@ -679,7 +763,15 @@ def main():
     ap.add_argument("--pool-config", default="B")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--no-episodes", action="store_true")
+    ap.add_argument("--fuzz", default=None, metavar="LO:HI", help="record the configs of tests/fuzz_configs.py for these seeds instead (fuzz_s{seed}.npz)")
     a = ap.parse_args()
+    if a.fuzz:
+        lo, hi = (int(x) for x in a.fuzz.split(":"))
+        import multiprocessing as mp
+        with mp.Pool(min(a.jobs, hi - lo)) as p:
+            for seed, world, policy, n, n_live, raised, size in p.imap_unordered(fuzz_episode, range(lo, hi)):
+                print("fuzz %03d world=%5d %-11s steps=%3d before_done=%3d bytes=%6d %s" % (seed, world, policy, n, n_live, size, raised or ""), flush=True)
+        return
     if not a.no_episodes:
         todo = [e for e in EPISODES if a.only is None or a.only in e[0]]
         import multiprocessing as mp

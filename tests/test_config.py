@@ -162,3 +162,28 @@ def test_registry_and_params_json(tmp_path):
         make("Test-Cont-Env-Manual-v0")
     with pytest.raises(KeyError):
         make("no-such-env")
+
+
+@pytest.mark.parametrize("cls,extra", [("LeaderCorridor_lasers", {}), ("LeaderCorridor_lasers_v2", {}),
+                                       ("LeaderCorridor_Prev_lasers_v2", {"max_prev_obs": 3})])
+def test_ray_sensor_without_edges_warns(cls, extra):
+    """SEN:706 / 787 / 908: without corridor and green-zone edges and with an obstacle list that is always empty the reference raises
+    IndexError in reset() (established on the reference: react_to_obstacles False, or "dynamic" with add_bear=False; "static" and "all"
+    always hold the leader).  make_config warns exactly there (include/ftl.h: the device then reads laser_length, no error bit)."""
+    import warnings
+    from fuzz_configs import TRACKER as tracker
+
+    def config(react, corridor=False, green=False, **kw):
+        rays = dict(sensor_class=cls, react_to_safe_corridor=corridor, react_to_green_zone=green, react_to_obstacles=react, **extra)
+        return make_config(follower_sensors={"LeaderPositionsTracker_v2": tracker, "rays": rays}, **kw)
+    for react, kw in ((False, {}), ("dynamic", dict(add_bear=False))):
+        with pytest.warns(UserWarning, match="has no edges to react to"):
+            config(react, **kw)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        config("dynamic", bear_number=1)
+        config("static", add_bear=False)
+        config("all", add_bear=False)
+        config(True, add_bear=False)
+        config(False, corridor=True)
+        config("dynamic", green=True, add_bear=False)

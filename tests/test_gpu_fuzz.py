@@ -8,83 +8,12 @@ import pytest
 import torch
 
 from continiousenvironment_follower_leader_amd import abi, make_config
+from fuzz_configs import TRACKER, _aux_sensor, _ray_sensor, draw_config  # noqa: F401  (the draws live there: importable without a GPU)
+from golden_util import RADAR_BUDGET, radar_slice, radar_touches_boundary
 from oracle_batch import OracleBatch, pool_scenarios
 from test_gpu_configs import CORNER_BUDGET, WAIVERS, _actions, _compare_with_oracle, _vec
 
-RADAR_BUDGET = 0.01      # env-steps per config with a radar reading excused as a sector-boundary knife edge (worst of the 96 configs: 0.26 %; all of them together 6e-5)
-
 pytestmark = pytest.mark.gpu
-
-TRACKER = dict(sensor_class="LeaderPositionsTracker_v2", eat_close_points=False, generate_corridor=True, saving_period=8,
-               start_corridor_behind_follower=True, corridor_length=250, corridor_width=30)
-
-
-def _ray_sensor(rng, kind):
-    react = dict(react_to_green_zone=bool(rng.integers(2)), react_to_safe_corridor=bool(rng.integers(2)),
-                 react_to_obstacles=[True, False, "static", "dynamic", "all"][rng.integers(5)])
-    if not (react["react_to_green_zone"] or react["react_to_safe_corridor"] or react["react_to_obstacles"]):
-        react["react_to_safe_corridor"] = True
-    if kind == "prev":
-        return dict(sensor_class="LeaderCorridor_Prev_lasers_v2", lasers_count=int(rng.choice([12, 20, 24, 36])),
-                    laser_length=int(rng.integers(60, 220)), max_prev_obs=int(rng.integers(1, 13)), use_prev_obs=True,
-                    pad_sectors=bool(rng.integers(3) == 0), **react)
-    if kind == "v2":
-        return dict(sensor_class="LeaderCorridor_lasers_v2", lasers_count=int(rng.choice([12, 20, 24, 36])),
-                    laser_length=int(rng.integers(60, 220)), **react)
-    if kind == "front":
-        return dict(sensor_class="LeaderCorridor_lasers", front_lasers_count=int(rng.choice([3, 5])), back_lasers_count=int(rng.choice([0, 2])),
-                    laser_length=int(rng.integers(60, 180)), **react)
-    return dict(sensor_class="LeaderCorridor_lasers_compas", lasers_count=int(rng.choice([12, 20, 36])), laser_length=int(rng.integers(60, 160)),
-                max_prev_obs=int(rng.integers(1, 9)), pad_sectors=False, react_to_green_zone=True, react_to_safe_corridor=True,
-                react_to_obstacles=False)
-
-
-def _aux_sensor(rng, kind):
-    if kind == "lidar":
-        return dict(sensor_class="LaserSensor", available_angle=int(rng.choice([90, 180, 360])), angle_step=int(rng.choice([10, 15, 30])),
-                    points_number=int(rng.choice([8, 10, 20])), sensor_range=int(rng.integers(2, 6)), return_only_distances=bool(rng.integers(2)))
-    if kind == "vector":
-        return dict(sensor_class="LeaderTrackDetector_vector", position_sequence_length=int(rng.integers(4, 40)),
-                    detectable_positions=["new", "old"][rng.integers(2)])
-    return dict(sensor_class="LeaderTrackDetector_radar", position_sequence_length=int(rng.integers(4, 40)),
-                detectable_positions=["new", "old", "near"][rng.integers(3)], radar_sectors_number=int(rng.choice([8, 18, 36])))
-
-
-def draw_config(seed):
-    rng = np.random.default_rng(1000 + seed)
-    entries = []
-    for k in range(int(rng.integers(1, 4))):                    # 1-3 segment ray sensors
-        entries.append(("rays%d" % k, _ray_sensor(rng, ["prev", "prev", "v2", "front"][rng.integers(4)])))
-    if rng.integers(3) == 0:
-        entries.append(("compas", _ray_sensor(rng, "compas")))
-    for k in range(int(rng.integers(0, 3))):                    # 0-2 of lidar / leader-track detectors
-        entries.append(("aux%d" % k, _aux_sensor(rng, ["lidar", "vector", "radar"][rng.integers(3)])))
-    order = rng.permutation(len(entries))
-    at = int(rng.integers(0, len(entries) + 1))                 # the tracker's dict position: sensors before it see the first scan only
-    sensors = {}
-    for pos, j in enumerate(order):
-        if pos == at:
-            sensors["LeaderPositionsTracker_v2"] = dict(TRACKER, saving_period=int(rng.choice([4, 8])))
-        sensors[entries[j][0]] = entries[j][1]
-    if "LeaderPositionsTracker_v2" not in sensors:
-        sensors["LeaderPositionsTracker_v2"] = dict(TRACKER, saving_period=int(rng.choice([4, 8])))
-    bears = int(rng.integers(0, 5))
-    hist = max([s.get("max_prev_obs", 1) for s in sensors.values()] + [1])
-    if hist * (1 + bears) > 64:                                 # one wavefront of snapshot rects (ftl_create rejects more)
-        bears = 64 // hist - 1
-    kw = dict(follower_sensors=sensors, bear_number=bears, add_bear=bears > 0, obstacle_number=int(rng.choice([10, 35, 60])),
-              frames_per_step=int(rng.choice([3, 5, 10])), max_distance=float(rng.choice([3, 4, 5])), min_distance=float(rng.choice([0.5, 1, 1.5])),
-              max_dev=float(rng.choice([0.5, 1, 1.5])), warm_start=int(rng.choice([0, 50, 500])), max_steps=int(rng.choice([120, 5000])),
-              aggregate_reward=bool(rng.integers(4) == 0), move_bear_v4=bool(rng.integers(2)), rng_seed=int(seed), env_id_base=100 * seed)
-    if rng.integers(3) == 0:
-        kw["leader_speed_regime"] = {0: [0.2, 1], 60: 0.5, 150: [0.6, 1.0]}
-    if rng.integers(4) == 0:
-        kw["leader_acceleration_regime"] = {0: 0, 40: 0.002, 90: -0.002, 140: 0}
-    if rng.integers(4) == 0:
-        kw["random_frames_per_step"] = [3, 9]
-    if rng.integers(3) == 0:
-        kw["early_stopping"] = {"max_distance_coef": 1.5, "low_reward": -80}
-    return kw
 
 
 def _radar_knife_edges(env, cfg):
@@ -107,19 +36,12 @@ def _radar_knife_edges(env, cfg):
     for j in radars:
         A = cfg.c.aux[j]
         lo = ei[:, abi.EI_CORR_LO if A.after_tracker else abi.EI_HW0_LO]; hi = ei[:, abi.EI_CORR_HI if A.after_tracker else abi.EI_HW0_HI]
-        sa = np.pi / A.radar_sectors
         for e in range(env.n):
-            n = int(hi[e] - lo[e]); s0, s1 = 0, n
-            if A.detectable == 0: s0 = max(n - A.seq_len, 0)
-            elif A.detectable == 1: s1 = min(n, A.seq_len)
+            s0, s1 = radar_slice(int(hi[e] - lo[e]), A.detectable, A.seq_len)
             if s1 <= s0:
                 continue
             p = hist[e, (lo[e] + np.arange(s0, s1)) & (cap - 1)]
-            v = p - pos[e]
-            r = np.radians((fdir[e] + 90.0) % 360.0)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                q = np.arccos(np.clip((v[:, 0] * np.cos(r) + v[:, 1] * np.sin(r)) / np.hypot(v[:, 0], v[:, 1]), -1, 1)) / sa
-            if np.any(np.abs(q - np.rint(q)) < 1e-6):
+            if radar_touches_boundary(p, pos[e], fdir[e], A.radar_sectors):
                 mask[e, A.out_offset:A.out_offset + A.radar_sectors] = True
     return mask
 
