@@ -18,6 +18,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_render.hpp"),
            os.path.join(_PKG, "csrc", "ftl_snapshot.hpp"),
            os.path.join(_PKG, "csrc", "ftl_queue.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_sampler.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
 # translation units: the device code + C-ABI, and the host-only scenario generator (reset-time, no GPU code)
 UNITS = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp")]
@@ -108,6 +109,13 @@ def load():
     lib.ftl_set_episode_queue.restype = C.c_int
     lib.ftl_queue_start.argtypes = [vp, C.POINTER(abi.Outputs), vp]
     lib.ftl_queue_start.restype = C.c_int
+    lib.ftl_sizeof_scenario_sampler.restype = C.c_size_t
+    lib.ftl_set_scenario_sampler.argtypes = [vp, C.POINTER(abi.ScenarioSamplerC)]
+    lib.ftl_set_scenario_sampler.restype = C.c_int
+    lib.ftl_sampler_refresh.argtypes = [vp, vp]
+    lib.ftl_sampler_refresh.restype = C.c_int
+    lib.ftl_sampler_start.argtypes = [vp, C.POINTER(abi.Outputs), vp]
+    lib.ftl_sampler_start.restype = C.c_int
     # include/ftl_gazebo.h
     lib.ftl_gz_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.ftl_gz_destroy.argtypes = [vp]
@@ -133,6 +141,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_sizeof_render_params", "ftl_render_workspace", "ftl_render",
            "ftl_env_bytes", "ftl_env_layout_id", "ftl_pack_envs", "ftl_unpack_envs",
            "ftl_sizeof_episode_record", "ftl_sizeof_episode_queue", "ftl_set_episode_queue", "ftl_queue_start",
+           "ftl_sizeof_scenario_sampler", "ftl_set_scenario_sampler", "ftl_sampler_refresh", "ftl_sampler_start",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -27,7 +27,13 @@ FTL_ACTION_BOX2, FTL_ACTION_DISCRETE, FTL_ACTION_TURN = 0, 1, 2
 FTL_STEP_AUTO_RESET = 1
 FTL_STEP_NEXT_RESET = 4
 FTL_STEP_QUEUE_RESET = 8
+FTL_STEP_SAMPLE_RESET = 16
 FTL_EPISODE_DONE_AT_RESET = 1
+# columns of a scenario sampler's table (include/ftl.h, ftl_scenario_sampler)
+FTL_N_SCEN_STATS = 10
+(SS_EPISODES, SS_FRAMES_SUM, SS_SUCCESS, SS_CRASH, SS_LOW_REWARD, SS_TOO_FAR, SS_TIMEOUT, SS_RETURN_Q16, SS_DONE_AT_RESET,
+ SS_LAST_CALL) = range(10)
+SS_NAMES = ("episodes", "frames_sum", "success", "crash", "low_reward", "too_far", "timeout", "return_q16", "done_at_reset", "last_call")
 FTL_N_METRICS = 8
 FTL_METRICS_CLEAR = 1
 (M_EPISODES, M_RETURN_SUM, M_FRAMES_SUM, M_SUCCESS, M_CRASH, M_LOW_REWARD, M_TOO_FAR, M_TIMEOUT) = range(8)
@@ -128,6 +134,30 @@ def uniform01(rng_seed, env_id, resets, frame):
     return (mix64(key + 0x9E3779B97F4A7C15 * (frame + 1)) >> 11) * (1.0 / 9007199254740992.0)
 
 
+def mulhi64(a, b):
+    return ((a & _M64) * (b & _M64)) >> 64
+
+
+def sample_scenario(rng_seed, stream_id, resets, cdf, base=0):
+    """Python twin of ftl_sample_scenario() in include/ftl.h, in Python integers: the pool index ``base + idx`` an env on stream
+    ``stream_id`` draws when its episode number ``resets`` ends.  ``cdf``: the inclusive prefix sums of the uint32 weights."""
+    key = mix64(rng_seed + 0x9E3779B97F4A7C15 * (stream_id + 1)) ^ mix64(0xD1B54A32D192ED03 * (resets + 1))
+    x = mix64(key + 0x9E3779B97F4A7C15 * ((1 << 42) + 1))
+    count = len(cdf)
+    total = int(cdf[count - 1])
+    if total == 0:
+        return base + mulhi64(x, count)
+    r = mulhi64(x, total)
+    lo, hi = 0, count - 1
+    while lo < hi:
+        mid = lo + (hi - lo) // 2
+        if int(cdf[mid]) <= r:
+            lo = mid + 1
+        else:
+            hi = mid
+    return base + lo
+
+
 class Scenarios(C.Structure):
     _fields_ = [("n_scenarios", C.c_int32), ("_pad", C.c_int32),
                 ("static_rects", C.c_void_p), ("robot_pos", C.c_void_p), ("robot_dir", C.c_void_p),
@@ -180,6 +210,11 @@ class EpisodeQueueC(C.Structure):
     """ftl_episode_queue: device pointers of a queue's arrays (``vec_game.EpisodeQueue`` owns them)."""
     _fields_ = [("scenario", C.c_void_p), ("stream", C.c_void_p), ("stream_base", C.c_int64), ("n", C.c_int32), ("_pad", C.c_int32),
                 ("head", C.c_void_p), ("records", C.c_void_p), ("ticket", C.c_void_p)]
+
+
+class ScenarioSamplerC(C.Structure):
+    """ftl_scenario_sampler: device pointers of a sampler's arrays (``vec_game.ScenarioSampler`` owns them)."""
+    _fields_ = [("weight", C.c_void_p), ("cdf", C.c_void_p), ("base", C.c_int32), ("count", C.c_int32), ("table", C.c_void_p)]
 
 
 # ftl_render (include/ftl.h): layer bits and the image parameters

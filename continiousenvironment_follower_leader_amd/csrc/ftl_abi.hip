@@ -27,6 +27,7 @@ constexpr int FTL_N_FIELDS = 15;
 }  // namespace
 
 struct FtlQueueState;        // ftl_queue.hpp
+struct FtlSamplerState;      // ftl_sampler.hpp
 
 struct ftl_handle {
     FtlDevParams P;          // host copy of the frozen parameters
@@ -56,11 +57,16 @@ struct ftl_handle {
     size_t lds_pad;          // FTL_DEBUG_LDS_PAD (diagnostic: lowers the frame kernel's occupancy without touching the code), read once at create
     float* last_lasers;      // ftl_outputs.lasers of the last ftl_reset / ftl_step* call (ftl_render's hit points)
     FtlQueueState* queue;    // the episode queue (ftl_set_episode_queue); null until one is attached
+    FtlSamplerState* sampler;  // the scenario sampler (ftl_set_scenario_sampler); null until one is attached
 };
 
 static void ftl_queue_destroy(ftl_handle* h);
 static int ftl_queue_attached(const ftl_handle* h);
 static int ftl_queue_finish_step(ftl_handle* h, const FtlCall& step, const ftl_outputs* out, const ftl_final_outputs* fin, void* stream);
+static void ftl_sampler_destroy(ftl_handle* h);
+static int ftl_sampler_attached(const ftl_handle* h);
+static int ftl_sampler_check_window(const ftl_handle* h);
+static int ftl_sampler_finish_step(ftl_handle* h, const FtlCall& step, const ftl_outputs* out, const ftl_final_outputs* fin, void* stream);
 
 namespace {
 
@@ -166,7 +172,7 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
     h->device = device;
     h->bound = false; h->have_scen = false; h->dP = nullptr; h->dirty = true;
     h->rg_mem = nullptr; h->rg_tot = nullptr; h->rg_parity = 0; h->rg_launches = 0; h->mt_mem = nullptr; h->timing = false; h->tev_used = 0;
-    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->last_lasers = nullptr; h->queue = nullptr;
+    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->last_lasers = nullptr; h->queue = nullptr; h->sampler = nullptr;
     {   // measured: +9 % with random_frames_per_step (long frame kernels whose tails the other half's ray kernel fills), -1 % with a
         // fixed 10 frames per step -- so it is on for the former only; FTL_SPLIT=0/1 overrides
         const char* sp = getenv("FTL_SPLIT");
@@ -333,6 +339,7 @@ void ftl_destroy(ftl_handle* h) {
     if (!h) return;
     if (h->dP || h->rg_mem || h->side || h->mt_mem) (void)hipSetDevice(h->device);
     ftl_queue_destroy(h);
+    ftl_sampler_destroy(h);
     if (h->dP) (void)hipFree(h->dP);
     if (h->mt_mem) (void)hipFree(h->mt_mem);
     for (hipEvent_t ev : h->tev) (void)hipEventDestroy(ev);
@@ -586,21 +593,24 @@ int ftl_step_encoded(ftl_handle* h, const void* action, int32_t encoding, const 
 int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, const ftl_final_outputs* fin,
                    uint32_t flags, void* stream) {
     if (!h || !action) return fail(FTL_E_INVALID, "null argument");
-    flags &= FTL_STEP_AUTO_RESET | FTL_STEP_NEXT_RESET | FTL_STEP_QUEUE_RESET;   // (other bits were always ignored; the kernel's internal ones stay internal)
+    flags &= FTL_STEP_AUTO_RESET | FTL_STEP_NEXT_RESET | FTL_STEP_QUEUE_RESET | FTL_STEP_SAMPLE_RESET;   // (other bits were always ignored; the kernel's internal ones stay internal)
     if ((flags & FTL_STEP_AUTO_RESET) && (flags & FTL_STEP_NEXT_RESET)) return fail(FTL_E_INVALID, "FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET exclude each other");
     const bool queue = (flags & FTL_STEP_QUEUE_RESET) != 0;
     if (queue && flags != FTL_STEP_QUEUE_RESET) return fail(FTL_E_INVALID, "FTL_STEP_QUEUE_RESET excludes the other reset flags");
+    const bool sample = (flags & FTL_STEP_SAMPLE_RESET) != 0;
+    if (sample && flags != FTL_STEP_SAMPLE_RESET) return fail(FTL_E_INVALID, "FTL_STEP_SAMPLE_RESET excludes the other reset flags");
     if (encoding < FTL_ACTION_BOX2 || encoding > FTL_ACTION_TURN) return fail(FTL_E_INVALID, "unknown action encoding");
+    if (sample && !ftl_sampler_attached(h)) return fail(FTL_E_STATE, "FTL_STEP_SAMPLE_RESET without a scenario sampler (ftl_set_scenario_sampler)");
     if (queue && !ftl_queue_attached(h)) return fail(FTL_E_STATE, "FTL_STEP_QUEUE_RESET without an episode queue (ftl_set_episode_queue)");
     if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
     if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
     int rc = check_out(h, out);
     if (rc) return rc;
     if (out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
-    const bool same_step = fin && (flags & (FTL_STEP_AUTO_RESET | FTL_STEP_QUEUE_RESET));      // the terminal rows are copied
+    const bool same_step = fin && (flags & (FTL_STEP_AUTO_RESET | FTL_STEP_QUEUE_RESET | FTL_STEP_SAMPLE_RESET));      // the terminal rows are copied
     if (fin && (!fin->ended || !fin->restarted)) return fail(FTL_E_INVALID, "ftl_final_outputs: ended / restarted missing");
     if (same_step && (!fin->obs_num || !fin->target || (h->P.lasers_len > 0 && !fin->lasers)))
-        return fail(FTL_E_INVALID, "ftl_final_outputs: obs_num / lasers / target missing (needed under FTL_STEP_AUTO_RESET / FTL_STEP_QUEUE_RESET)");
+        return fail(FTL_E_INVALID, "ftl_final_outputs: obs_num / lasers / target missing (needed under FTL_STEP_AUTO_RESET / FTL_STEP_QUEUE_RESET / FTL_STEP_SAMPLE_RESET)");
     if (same_step && fin->policy_obs && !out->policy_obs) return fail(FTL_E_INVALID, "ftl_final_outputs.policy_obs needs ftl_outputs.policy_obs");
     FtlCall call; call.mode = 0; call.action = (const double*)action; call.action_kind = encoding; call.out = *out; call.flags = flags; call.scen_idx = nullptr; call.mask = nullptr; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
     call.ended = fin ? fin->ended : nullptr; call.restarted = fin ? fin->restarted : nullptr;
@@ -609,6 +619,13 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
         call.flags = 0; call.ended = nullptr; call.restarted = nullptr;
         rc = launch(h, call, stream);
         return rc ? rc : ftl_queue_finish_step(h, call, out, fin, stream);
+    }
+    if (sample) {    // a plain step, then the sampler's kernel and the reset pass of the slots that finished (ftl_sampler.hpp)
+        rc = ftl_sampler_check_window(h);
+        if (rc) return rc;
+        call.flags = 0; call.ended = nullptr; call.restarted = nullptr;
+        rc = launch(h, call, stream);
+        return rc ? rc : ftl_sampler_finish_step(h, call, out, fin, stream);
     }
     if (!same_step) return launch(h, call, stream);
     // same-step: the step defers the reset of the envs that finish (their terminal state gets the usual sensor scans), their terminal rows
@@ -681,6 +698,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 #include "ftl_render.hpp"        // batched top-down RGB frames (ftl_render), same translation unit
 #include "ftl_snapshot.hpp"      // snapshot / clone / restore of env rows (ftl_pack_envs, ftl_unpack_envs), same translation unit
 #include "ftl_queue.hpp"         // the episode queue (ftl_set_episode_queue, ftl_queue_start, FTL_STEP_QUEUE_RESET), same translation unit
+#include "ftl_sampler.hpp"       // the scenario sampler (ftl_set_scenario_sampler, ftl_sampler_start, FTL_STEP_SAMPLE_RESET), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

@@ -9,6 +9,7 @@ import dataclasses
 import hashlib
 import math
 import uuid
+import weakref
 from contextlib import nullcontext as _nullcontext
 
 import numpy as np
@@ -220,6 +221,21 @@ class _BatchBase:
         if self.queue is None:
             raise _lib.FtlError("set_episode_queue() first")
 
+    def _need_sampler(self):
+        if getattr(self, "sampler", None) is None:
+            raise _lib.FtlError("set_scenario_sampler() first")
+
+    def _check_sampler(self, sampler):
+        """A ``ScenarioSampler`` that fits this batch: same device, window inside the pool."""
+        self._need_pool()
+        if not isinstance(sampler, ScenarioSampler):
+            raise TypeError("set_scenario_sampler() takes a ScenarioSampler or None")
+        if sampler.device != self.device:
+            raise ValueError("the sampler lives on %s, the batch on %s" % (sampler.device, self.device))
+        if sampler.base + sampler.count > self.pool.n:
+            raise ValueError("the sampler's window [%d, %d) lies outside the pool of %d scenarios"
+                             % (sampler.base, sampler.base + sampler.count, self.pool.n))
+
     def _reset_args(self, scen_idx, mask):
         """(scen_idx i32[N], mask u8[N] or None) of a ``reset`` call as contiguous device tensors, checked."""
         self._need_pool()
@@ -393,7 +409,10 @@ class VecGame(_BatchBase):
     the envs whose episode ended in the last step, ``restarted`` u8[N] the envs it re-initialised (``terminated_truncated()``).
 
     Evaluation: ``set_episode_queue`` / ``reset_from_queue`` / ``step(a, auto_reset="queue")`` play a list of scenarios exactly once
-    each, whichever slot is free, with one record per entry (``EpisodeQueue``); ``evaluate(policy, scen_ids)`` is the whole loop."""
+    each, whichever slot is free, with one record per entry (``EpisodeQueue``); ``evaluate(policy, scen_ids)`` is the whole loop.
+
+    Curricula: ``set_scenario_sampler`` / ``reset_from_sampler`` / ``step(a, auto_reset="sample")`` restart a finished env on a world drawn
+    from the weights of a ``ScenarioSampler`` and add the episode it ended to the sampler's per-scenario table, all on the device."""
 
     def __init__(self, n_envs, device="cuda:0", config: GameConfig = None, policy_obs=False, _outputs=None, final_obs=False, **game_kwargs):
         self.cfg = config if config is not None else make_config(**game_kwargs)
@@ -441,6 +460,7 @@ class VecGame(_BatchBase):
         self._tune = {}
         self.queue = None
         self.ticket = None
+        self.sampler = None
         self.env_bytes = int(self.lib.ftl_env_bytes(self.h))
         self.layout_id = int(self.lib.ftl_env_layout_id(self.h))
 
@@ -498,7 +518,10 @@ class VecGame(_BatchBase):
         observations in the final buffers (needs ``final_obs=True``); ``"next_step"`` -- this step returns the terminal observation, an env
         that is done on entry is re-initialised instead of stepped (its action ignored; reward 0, done 0, status 0: FTL_STEP_NEXT_RESET);
         ``"queue"`` -- a finished env records its episode and takes the next entry of the attached episode queue, or parks
-        (``set_episode_queue``; FTL_STEP_QUEUE_RESET; outputs as under True, the final buffers are filled when the batch has them).
+        (``set_episode_queue``; FTL_STEP_QUEUE_RESET; outputs as under True, the final buffers are filled when the batch has them);
+        ``"sample"`` -- a finished env adds its episode to the table of the attached ``ScenarioSampler`` and restarts on a world drawn from
+        its weights (``set_scenario_sampler``; FTL_STEP_SAMPLE_RESET; outputs as under True, the final buffers are filled when the batch has
+        them, ``ended`` = ``restarted`` = done).
         ``check_errors=True`` synchronises and raises what the reference would have raised in any env (``raise_on_errors``);
         the default leaves the per-env sticky error words for ``error_report()`` so that the step stays asynchronous."""
         action, enc = self._encode_action(action, self.n)
@@ -530,7 +553,11 @@ class VecGame(_BatchBase):
             if getattr(self, "queue", None) is None:
                 raise _lib.FtlError('auto_reset="queue" needs set_episode_queue() first')
             return abi.FTL_STEP_QUEUE_RESET, fin
-        raise ValueError('auto_reset must be False, True, "same_step", "next_step" or "queue" (got %r)' % (auto_reset,))
+        if auto_reset == "sample":
+            if getattr(self, "sampler", None) is None:
+                raise _lib.FtlError('auto_reset="sample" needs set_scenario_sampler() first')
+            return abi.FTL_STEP_SAMPLE_RESET, fin
+        raise ValueError('auto_reset must be False, True, "same_step", "next_step", "queue" or "sample" (got %r)' % (auto_reset,))
 
     # ------------------------------------------------------------------ episode queue (ftl_set_episode_queue, ftl_queue_start)
     def set_episode_queue(self, scen_ids, stream_ids=None, stream_base=0):
@@ -557,6 +584,39 @@ class VecGame(_BatchBase):
         first observations like ``reset``."""
         self._need_queue()
         _lib.check(self.lib.ftl_queue_start(self.h, C.byref(self._out), self._stream()), self.lib)
+        return self.obs_num, self.lasers
+
+    # ------------------------------------------------------------------ scenario sampler (ftl_set_scenario_sampler, ftl_sampler_start)
+    def set_scenario_sampler(self, sampler, _owner=None):
+        """Attach a ``ScenarioSampler`` (``None`` detaches: the batch is then exactly what it was before): ``step(a, auto_reset="sample")``
+        restarts every finished env on pool entry ``base + idx`` drawn from the sampler's weights and adds the episode it ended to the
+        sampler's table.  Builds the sampler's cdf on the current stream (``refresh_sampler``).  Follow with ``reset_from_sampler()`` or
+        keep the running episodes.  Snapshots, ``clone`` and ``state_dict`` work as without one: the sampler keeps no per-slot state (save
+        its weights and table with ``ScenarioSampler.state_dict``)."""
+        if sampler is None:
+            _lib.check(self.lib.ftl_set_scenario_sampler(self.h, None), self.lib)
+            self.sampler = self._sampler_c = None
+            return None
+        self._check_sampler(sampler)
+        c = sampler.c_struct()
+        _lib.check(self.lib.ftl_set_scenario_sampler(self.h, C.byref(c)), self.lib)
+        self.sampler, self._sampler_c = sampler, c
+        if _owner is None:                       # (the parts of a pipelined batch: the whole batch owns the sampler and refreshes once)
+            sampler._attach(self)
+            self.refresh_sampler()
+        return sampler
+
+    def refresh_sampler(self):
+        """Rebuild the sampler's cdf from its weights on the current stream (``ftl_sampler_refresh``); ``ScenarioSampler.set_weights``
+        calls it.  Steps enqueued later on this stream draw from the new cdf."""
+        self._need_sampler()
+        _lib.check(self.lib.ftl_sampler_refresh(self.h, self._stream()), self.lib)
+
+    def reset_from_sampler(self):
+        """The sampler's ``reset()``: every slot draws its world with the stream / reset-count words its state holds (no table update);
+        returns the first observations like ``reset``."""
+        self._need_sampler()
+        _lib.check(self.lib.ftl_sampler_start(self.h, C.byref(self._out), self._stream()), self.lib)
         return self.obs_num, self.lasers
 
     def _encode_action(self, action, n):
@@ -832,6 +892,119 @@ class EpisodeQueue:
         return self.n - self.finished()
 
 
+class ScenarioSampler:
+    """Weights over the pool entries ``[base, base + count)`` and the per-scenario outcome table, on the device (``ftl_scenario_sampler``).
+
+    Owns ``weight`` (uint32 bit patterns in an int32 tensor), ``cdf`` (int64, written by the library) and the table int64
+    ``[count, abi.FTL_N_SCEN_STATS]``.  Attach it with ``VecGame.set_scenario_sampler`` (or the pipelined batch's: its parts share ONE
+    sampler, one table, one cdf); a finished env then draws entry i with probability weight[i] / sum(weight) -- in integers: an entry of
+    weight 0 is never drawn; all weights 0 means uniform.  The class builds no curriculum: the caller turns ``table()`` into weights.
+    On a CPU device the class only holds and quantises weights (it cannot be attached)."""
+
+    def __init__(self, count, base=0, device="cuda:0"):
+        self.device = torch.device(device)
+        self.count, self.base = int(count), int(base)
+        if self.count <= 0 or self.base < 0:
+            raise ValueError("a scenario sampler needs count > 0 and base >= 0")
+        self.weight = torch.zeros(self.count, dtype=torch.int32, device=self.device)
+        self.cdf = torch.zeros(self.count, dtype=torch.int64, device=self.device)
+        self._table = torch.zeros(self.count, abi.FTL_N_SCEN_STATS, dtype=torch.int64, device=self.device)
+        self._owner = None
+
+    def c_struct(self):
+        c = abi.ScenarioSamplerC()
+        c.weight, c.cdf, c.base, c.count, c.table = self.weight.data_ptr(), self.cdf.data_ptr(), self.base, self.count, self._table.data_ptr()
+        return c
+
+    def _attach(self, batch):
+        self._owner = weakref.ref(batch)
+
+    def _batch(self):
+        b = self._owner() if self._owner is not None else None
+        return b if b is not None and getattr(b, "sampler", None) is self else None
+
+    @staticmethod
+    def quantise(w):
+        """int64 weights of a float tensor: ``rint(w / max(w) * 2**24)`` (ties to even), at least 1 where ``w > 0`` -- a positive weight
+        is never rounded away; all zero stays all zero (uniform).  Negative or non-finite values raise ValueError."""
+        w = torch.as_tensor(w)
+        if not w.dtype.is_floating_point:
+            w = w.to(torch.float64)
+        w = w.double().reshape(-1)
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("weights must be finite and not negative")
+        m = w.max() if w.numel() else w.new_zeros(())
+        if float(m) == 0.0:
+            return torch.zeros(w.shape, dtype=torch.int64, device=w.device)
+        q = torch.round(w / m * float(2 ** 24)).to(torch.int64)
+        return torch.where((w > 0) & (q < 1), torch.ones_like(q), q)
+
+    def set_weights(self, w):
+        """Weights from a float tensor of length ``count`` (``quantise``); rebuilds the cdf through the batch the sampler is attached to
+        -- on a pipelined batch a synchronisation point."""
+        w = torch.as_tensor(w)
+        if w.numel() != self.count:
+            raise ValueError("weights must have one entry per scenario of the window (%d)" % self.count)
+        self._store(self.quantise(w))
+
+    def set_raw_weights(self, w):
+        """Weights as integers 0 .. 2**32 - 1 (an int64 tensor of length ``count``), taken as they are."""
+        w = torch.as_tensor(w)
+        if w.dtype.is_floating_point or w.dtype == torch.bool:
+            raise ValueError("raw weights must be an integer tensor")
+        w = w.to(torch.int64).reshape(-1)
+        if w.numel() != self.count:
+            raise ValueError("weights must have one entry per scenario of the window (%d)" % self.count)
+        if bool((w < 0).any()) or bool((w > 2 ** 32 - 1).any()):
+            raise ValueError("raw weights must lie in 0 .. 2**32 - 1")
+        self._store(w)
+
+    def _store(self, q):
+        q = q.to(self.device)
+        self.weight.copy_(torch.where(q >= 2 ** 31, q - 2 ** 32, q).to(torch.int32))     # the uint32 bit pattern
+        b = self._batch()
+        if b is not None:
+            b.refresh_sampler()
+
+    def raw_weights(self):
+        """The weights as an int64 tensor of values 0 .. 2**32 - 1."""
+        return self.weight.to(torch.int64) & 0xFFFFFFFF
+
+    def table(self, clear=False):
+        """The outcome table as a dict of int64 ``[count]`` device tensors (a copy) -- ``abi.SS_NAMES``: episodes, frames_sum, success,
+        crash, low_reward, too_far, timeout, return_q16, done_at_reset, last_call (the 1-based ``auto_reset="sample"`` call since the attach
+        in which an episode on the scenario last ended; 0: never) -- plus float64 ``mean_return`` (return_q16 / 65536 / episodes) and
+        ``success_rate``, both 0 where no episode ended yet.  ``clear=True`` zeroes the table afterwards.  On a pipelined batch the parts
+        are joined first."""
+        b = self._batch()
+        if b is not None:
+            b._wait_parts()
+        t = self._table.clone()
+        if clear:
+            self._table.zero_()
+        out = {name: t[:, k] for k, name in enumerate(abi.SS_NAMES)}
+        ep = t[:, abi.SS_EPISODES].clamp(min=1).double()
+        out["mean_return"] = t[:, abi.SS_RETURN_Q16].double() / 65536.0 / ep
+        out["success_rate"] = t[:, abi.SS_SUCCESS].double() / ep
+        return out
+
+    def state_dict(self):
+        """Weights and table as plain CPU tensors (joins the parts of a pipelined batch; synchronises)."""
+        b = self._batch()
+        if b is not None:
+            b._wait_parts()
+        return dict(format=1, base=self.base, count=self.count, weight=self.raw_weights().cpu(), table=self._table.cpu())
+
+    def load_state_dict(self, sd):
+        if sd.get("format") != 1 or int(sd["count"]) != self.count or int(sd["base"]) != self.base:
+            raise ValueError("the checkpoint is of a sampler over another window")
+        b = self._batch()
+        if b is not None:
+            b._wait_parts()
+        self._table.copy_(sd["table"].to(self.device))
+        self.set_raw_weights(sd["weight"])
+
+
 def _refuse_with_queue(queue, what):
     if queue is not None:
         raise _lib.FtlError("%s with an episode queue attached: a half-drained queue cannot be saved -- drain it (evaluate) or detach it "
@@ -960,6 +1133,7 @@ class PipelinedVecGame(_BatchBase):
         self._set_outputs(outs, final_obs)
         self.pool = None
         self.queue = None
+        self.sampler = None
         self._serial = False
         self._metrics = torch.zeros(abi.FTL_N_METRICS, dtype=torch.float64, device=self.device)
         self._stream_ptrs = [C.c_void_p(s.cuda_stream) for s in self.streams]
@@ -1074,6 +1248,39 @@ class PipelinedVecGame(_BatchBase):
         for k, g in enumerate(self.games):
             with self._on(k):
                 g.reset_from_queue()
+        self.join()
+        return self.obs_num, self.lasers
+
+    def set_scenario_sampler(self, sampler):
+        """``VecGame.set_scenario_sampler`` for the whole batch: the parts share ONE sampler -- one table, one cdf -- and, their draws being
+        pure functions of each env's own words, play exactly what one ``VecGame`` plays.  Joins the parts."""
+        self.join()
+        if sampler is None:
+            for g in self.games:
+                g.set_scenario_sampler(None)
+            self.sampler = None
+            return None
+        self._check_sampler(sampler)
+        for g in self.games:
+            g.set_scenario_sampler(sampler, _owner=self)
+        self.sampler = sampler
+        sampler._attach(self)
+        self.refresh_sampler()
+        return sampler
+
+    def refresh_sampler(self):
+        """Rebuild the shared cdf once, on the current stream.  A synchronisation point like ``load_scenarios`` on a running batch: the
+        current stream first waits for every part (their steps in flight read the old cdf), and the parts' next steps wait for it."""
+        self._need_sampler()
+        self.join()
+        self.games[0].refresh_sampler()
+
+    def reset_from_sampler(self):
+        """``VecGame.reset_from_sampler`` of every part on its stream, then ``join()``."""
+        self._need_sampler()
+        for k, g in enumerate(self.games):
+            with self._on(k):
+                g.reset_from_sampler()
         self.join()
         return self.obs_num, self.lasers
 

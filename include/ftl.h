@@ -206,6 +206,29 @@ static inline int32_t ftl_rand_range(uint64_t rng_seed, uint64_t env_id, uint64_
     return start + 10 * (v < n ? v : n - 1);
 }
 
+/* The weighted scenario draw of the scenario sampler (ftl_scenario_sampler below) on the same counter stream, in a key range of its own
+ * (bit 42 of the frame key): the draw an env on stream `stream_id` makes when its episode number `resets` ends (ftl_sampler_start: before
+ * its first).  cdf[i] is the inclusive prefix sum of the uint32 weights 0 .. i, total = cdf[count - 1].  The raw 64 bits x of the mix
+ * (not the >> 11 double) are scaled to r = mulhi(x, total) in [0, total); the result is the number of cdf entries <= r, i.e. the first i
+ * with cdf[i] > r; total == 0 (every weight zero) gives mulhi(x, count): uniform over the window.  Integers throughout: an entry of
+ * weight 0 is never drawn, and the result is the same on any device, in any slot, in any order. */
+static inline uint64_t ftl_mulhi64(uint64_t a, uint64_t b) {
+    const uint64_t a0 = a & 0xFFFFFFFFULL, a1 = a >> 32, b0 = b & 0xFFFFFFFFULL, b1 = b >> 32;
+    const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const uint64_t mid = (p00 >> 32) + (p01 & 0xFFFFFFFFULL) + (p10 & 0xFFFFFFFFULL);
+    return p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+}
+static inline int32_t ftl_sample_scenario(uint64_t rng_seed, uint64_t stream_id, uint64_t resets, const uint64_t* cdf, int32_t count) {
+    uint64_t key = ftl_mix64(rng_seed + 0x9E3779B97F4A7C15ULL * (stream_id + 1)) ^ ftl_mix64(0xD1B54A32D192ED03ULL * (resets + 1));
+    const uint64_t x = ftl_mix64(key + 0x9E3779B97F4A7C15ULL * ((1ULL << 42) + 1));
+    const uint64_t total = cdf[count - 1];
+    if (total == 0) return (int32_t)ftl_mulhi64(x, (uint64_t)count);
+    const uint64_t r = ftl_mulhi64(x, total);
+    int32_t lo = 0, hi = count - 1;                  /* cdf[count - 1] = total > r */
+    while (lo < hi) { const int32_t mid = lo + (hi - lo) / 2; if (cdf[mid] <= r) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
 /* Scenario pool = output of the reference's reset() (ENV:434-543) for P episodes, device arrays.
  * Robots are ordered leader, follower, bear0.. (R = 2 + n_bears). */
 typedef struct ftl_scenarios {
@@ -604,6 +627,62 @@ size_t ftl_sizeof_episode_queue(void);
 
 int ftl_set_episode_queue(ftl_handle* h, const ftl_episode_queue* q);   /* NULL detaches */
 int ftl_queue_start(ftl_handle* h, const ftl_outputs* out, void* stream);
+
+/* ---- scenario sampler: a finished env draws its next world from caller-controlled weights; per-scenario outcome table (curricula,
+ * prioritised level replay, "more of what the policy fails on") ------------------------------------------------------------------------
+ * The fourth reset discipline.  FTL_STEP_AUTO_RESET / FTL_STEP_NEXT_RESET restart a finished env from a fixed arithmetic walk over the
+ * reset window, the episode queue plays a finite list once; here the caller attaches uint32 weights over the pool entries
+ * [base, base + count) and an int64 table of [count][FTL_N_SCEN_STATS], both in device memory it owns, and every env that finishes
+ *   - adds the episode it just ended to the table row of the scenario it ran on, and
+ *   - restarts on pool entry base + ftl_sample_scenario(rng_seed, its global stream id, its FTL_EI_RESETS word, cdf, count)
+ * inside the step call, without the host.  The draw is a pure function of state words (above), so a run is reproducible whatever the
+ * batch layout, and integer: a weight of 0 is never drawn.  Unlike the queue this is an ordinary auto-reset -- the bookkeeping of
+ * FTL_STEP_AUTO_RESET (FTL_EI_EPISODES + 1, error bits into the sticky word, FTL_EI_RESETS advanced by the reset): FTL_EI_RESETS, FTL_EI_FPS,
+ * FTL_EI_ACC_CONSUMED and FTL_EI_STREAM are left alone, the slot's random streams go on.
+ *
+ * Equivalence (the contract): a batch reset with ftl_sampler_start and stepped with FTL_STEP_SAMPLE_RESET gives, call for call, the
+ * outputs and the state of a batch that is stepped without auto-reset and whose host calls ftl_reset(scen, mask = done) after every step
+ * with scen = base + ftl_sample_scenario on the slot's own words -- except FTL_EI_EPISODES, which a plain ftl_reset does not count.
+ *
+ * Table columns, all int64 so that sums are exact and independent of order: FTL_SS_EPISODES; FTL_SS_FRAMES_SUM (step_count at done);
+ * FTL_SS_SUCCESS / CRASH / LOW_REWARD / TOO_FAR / TIMEOUT (the predicates of FTL_M_*); FTL_SS_RETURN_Q16 = sum of llrint(overall_reward *
+ * 65536), round to nearest even; FTL_SS_DONE_AT_RESET; FTL_SS_LAST_CALL = the largest value of the handle's sample-call counter (the number
+ * of FTL_STEP_SAMPLE_RESET calls since the sampler was attached, this one included) at which an episode on the scenario ended (0: none
+ * yet).  Rows are updated with agent-scope atomics (add / max on 64-bit integers), so several handles -- the parts of a pipelined batch --
+ * may share one table and one cdf and still get the same bits.  An episode whose scenario lies outside [base, base + count) is not
+ * recorded (it was drawn before the window moved).  A world that is done at reset (empty route, ENV:508-510) counts in FTL_SS_EPISODES and
+ * FTL_SS_DONE_AT_RESET only and as one episode in "ep_stats", as for the queue.  The caller zeroes the table; the library only adds.
+ *
+ * ftl_set_scenario_sampler copies the struct and touches no device memory (the arrays stay the caller's, alive while attached; cdf is
+ * written by the library only); it resets the sample-call counter.  NULL detaches: the handle is then exactly what it was before.
+ * FTL_E_INVALID: NULL weight / cdf / table, count <= 0, base < 0, cdf or table not 8-byte aligned.  base + count <= n_scenarios is checked
+ * against the pool when a sampling call is issued (FTL_E_INVALID there).
+ * ftl_sampler_refresh rebuilds cdf from weight on `stream` (ftl_sampler_scan_kernel): call it once after attach and after every change
+ * of the weights; a step issued later on the same stream sees the new cdf.  Handles that share a cdf on other streams must be ordered
+ * after it by the caller.
+ * ftl_sampler_start is the sampler's ftl_reset: every slot draws with the FTL_EI_RESETS / FTL_EI_STREAM words its state holds (0 in a fresh
+ * buffer) and ftl_reset runs on those indices.  No table update.
+ * FTL_STEP_SAMPLE_RESET (ftl_step / ftl_step_encoded / ftl_step_final): a step without auto-reset (the sensors scan the terminal state),
+ * then ftl_sampler_kernel -- every slot whose done byte is set after the step records its episode and draws --, then with `fin` the
+ * terminal-row copy as under FTL_STEP_AUTO_RESET, then the masked reset pass.  `out` keeps the terminal reward / done / status and gets
+ * the new episode's observation; fin->ended = fin->restarted = the slot's done byte was set after the step.  A slot that an earlier plain
+ * step (or a done-at-reset world) left done is recorded and restarted like any other: mixing reset disciplines on one handle is the
+ * caller's business.  Combined with another reset flag: FTL_E_INVALID; without a sampler attached: FTL_E_STATE. */
+#define FTL_STEP_SAMPLE_RESET 16u
+#define FTL_N_SCEN_STATS 10
+enum { FTL_SS_EPISODES = 0, FTL_SS_FRAMES_SUM, FTL_SS_SUCCESS, FTL_SS_CRASH, FTL_SS_LOW_REWARD, FTL_SS_TOO_FAR, FTL_SS_TIMEOUT,
+       FTL_SS_RETURN_Q16, FTL_SS_DONE_AT_RESET, FTL_SS_LAST_CALL };
+typedef struct ftl_scenario_sampler {   /* all pointers are DEVICE pointers the caller owns */
+    const uint32_t* weight;    /* [count] */
+    uint64_t* cdf;             /* [count] inclusive prefix sums of weight, written by the library only (ftl_sampler_refresh) */
+    int32_t  base, count;      /* the pool entries [base, base + count) the weights cover */
+    int64_t* table;            /* [count][FTL_N_SCEN_STATS]; may be SHARED by several handles */
+} ftl_scenario_sampler;
+size_t ftl_sizeof_scenario_sampler(void);
+
+int ftl_set_scenario_sampler(ftl_handle* h, const ftl_scenario_sampler* s);   /* NULL detaches */
+int ftl_sampler_refresh(ftl_handle* h, void* stream);
+int ftl_sampler_start(ftl_handle* h, const ftl_outputs* out, void* stream);
 
 const char* ftl_last_error(void);
 
