@@ -17,6 +17,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_crmath.hpp"),
            os.path.join(_PKG, "csrc", "ftl_render.hpp"),
            os.path.join(_PKG, "csrc", "ftl_snapshot.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_restart.hpp"),
            os.path.join(_PKG, "csrc", "ftl_queue.hpp"),
            os.path.join(_PKG, "csrc", "ftl_sampler.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]

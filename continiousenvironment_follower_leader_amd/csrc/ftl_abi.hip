@@ -26,8 +26,9 @@ constexpr int FTL_N_FIELDS = 15;
 
 }  // namespace
 
-struct FtlQueueState;        // ftl_queue.hpp
-struct FtlSamplerState;      // ftl_sampler.hpp
+// a restart source the caller attached (ftl_queue.hpp, ftl_sampler.hpp): its struct, and the ftl_step* calls that used it since the attach
+template <typename T> struct FtlAttached { T v; bool attached; int32_t calls; };
+struct FtlRestartScratch { int32_t* scen_idx; int32_t* list; uint8_t* ended; uint8_t* restarted; };   // [n_envs] each, one allocation: scen_idx is its base
 
 struct ftl_handle {
     FtlDevParams P;          // host copy of the frozen parameters
@@ -56,17 +57,10 @@ struct ftl_handle {
     int win_base, win_count, win_stride; // pool entries the auto-reset draws from (ftl_set_reset_window)
     size_t lds_pad;          // FTL_DEBUG_LDS_PAD (diagnostic: lowers the frame kernel's occupancy without touching the code), read once at create
     float* last_lasers;      // ftl_outputs.lasers of the last ftl_reset / ftl_step* call (ftl_render's hit points)
-    FtlQueueState* queue;    // the episode queue (ftl_set_episode_queue); null until one is attached
-    FtlSamplerState* sampler;  // the scenario sampler (ftl_set_scenario_sampler); null until one is attached
+    FtlAttached<ftl_episode_queue> queue;         // ftl_set_episode_queue
+    FtlAttached<ftl_scenario_sampler> sampler;    // ftl_set_scenario_sampler
+    FtlRestartScratch rs;    // what a queue or sampler call hands to the reset pass (library-owned, allocated by the first such call: ftl_restart.hpp)
 };
-
-static void ftl_queue_destroy(ftl_handle* h);
-static int ftl_queue_attached(const ftl_handle* h);
-static int ftl_queue_finish_step(ftl_handle* h, const FtlCall& step, const ftl_outputs* out, const ftl_final_outputs* fin, void* stream);
-static void ftl_sampler_destroy(ftl_handle* h);
-static int ftl_sampler_attached(const ftl_handle* h);
-static int ftl_sampler_check_window(const ftl_handle* h);
-static int ftl_sampler_finish_step(ftl_handle* h, const FtlCall& step, const ftl_outputs* out, const ftl_final_outputs* fin, void* stream);
 
 namespace {
 
@@ -172,7 +166,7 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
     h->device = device;
     h->bound = false; h->have_scen = false; h->dP = nullptr; h->dirty = true;
     h->rg_mem = nullptr; h->rg_tot = nullptr; h->rg_parity = 0; h->rg_launches = 0; h->mt_mem = nullptr; h->timing = false; h->tev_used = 0;
-    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->last_lasers = nullptr; h->queue = nullptr; h->sampler = nullptr;
+    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->last_lasers = nullptr; h->queue = {}; h->sampler = {}; h->rs = {};
     {   // measured: +9 % with random_frames_per_step (long frame kernels whose tails the other half's ray kernel fills), -1 % with a
         // fixed 10 frames per step -- so it is on for the former only; FTL_SPLIT=0/1 overrides
         const char* sp = getenv("FTL_SPLIT");
@@ -337,9 +331,8 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
 
 void ftl_destroy(ftl_handle* h) {
     if (!h) return;
-    if (h->dP || h->rg_mem || h->side || h->mt_mem) (void)hipSetDevice(h->device);
-    ftl_queue_destroy(h);
-    ftl_sampler_destroy(h);
+    if (h->dP || h->rg_mem || h->side || h->mt_mem || h->rs.scen_idx) (void)hipSetDevice(h->device);
+    if (h->rs.scen_idx) (void)hipFree(h->rs.scen_idx);
     if (h->dP) (void)hipFree(h->dP);
     if (h->mt_mem) (void)hipFree(h->mt_mem);
     for (hipEvent_t ev : h->tev) (void)hipEventDestroy(ev);
@@ -563,19 +556,29 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
     return FTL_OK;
 }
 
-static int check_out(const ftl_handle* h, const ftl_outputs* out) {
+}  // extern "C"
+
+// What a reset or a step needs before anything is launched: a bound state, a scenario pool, the output arrays and, with policy_obs, one
+// history length on every ray sensor
+static int check_ready(const ftl_handle* h, const ftl_outputs* out, bool policy_obs = true) {
+    if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
+    if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
     if (!out || !out->obs_num || !out->target || !out->reward || !out->done || !out->status || (h->P.lasers_len > 0 && !out->lasers))
         return fail(FTL_E_INVALID, "output arrays missing");
+    if (policy_obs && out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
     return FTL_OK;
 }
 
+#include "ftl_restart.hpp"       // what same-step, the queue and the sampler share: finish_step, start_chosen, the choosers' arguments
+#include "ftl_queue.hpp"         // the episode queue (ftl_set_episode_queue, ftl_queue_start, FTL_STEP_QUEUE_RESET), same translation unit
+#include "ftl_sampler.hpp"       // the scenario sampler (ftl_set_scenario_sampler, ftl_sampler_start, FTL_STEP_SAMPLE_RESET), same translation unit
+
+extern "C" {
+
 int ftl_reset(ftl_handle* h, const int32_t* scen_idx, const uint8_t* mask, const ftl_outputs* out, void* stream) {
     if (!h || !scen_idx) return fail(FTL_E_INVALID, "null argument");
-    if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
-    if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
-    int rc = check_out(h, out);
+    int rc = check_ready(h, out);
     if (rc) return rc;
-    if (out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
     FtlCall call; call.mode = 1; call.scen_idx = scen_idx; call.mask = mask; call.out = *out; call.action = nullptr; call.flags = 0; call.action_kind = FTL_ACTION_BOX2; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
     call.ended = nullptr; call.restarted = nullptr;
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
@@ -600,13 +603,10 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
     const bool sample = (flags & FTL_STEP_SAMPLE_RESET) != 0;
     if (sample && flags != FTL_STEP_SAMPLE_RESET) return fail(FTL_E_INVALID, "FTL_STEP_SAMPLE_RESET excludes the other reset flags");
     if (encoding < FTL_ACTION_BOX2 || encoding > FTL_ACTION_TURN) return fail(FTL_E_INVALID, "unknown action encoding");
-    if (sample && !ftl_sampler_attached(h)) return fail(FTL_E_STATE, "FTL_STEP_SAMPLE_RESET without a scenario sampler (ftl_set_scenario_sampler)");
-    if (queue && !ftl_queue_attached(h)) return fail(FTL_E_STATE, "FTL_STEP_QUEUE_RESET without an episode queue (ftl_set_episode_queue)");
-    if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
-    if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
-    int rc = check_out(h, out);
+    if (sample && !h->sampler.attached) return fail(FTL_E_STATE, "FTL_STEP_SAMPLE_RESET without a scenario sampler (ftl_set_scenario_sampler)");
+    if (queue && !h->queue.attached) return fail(FTL_E_STATE, "FTL_STEP_QUEUE_RESET without an episode queue (ftl_set_episode_queue)");
+    int rc = check_ready(h, out);
     if (rc) return rc;
-    if (out->policy_obs && h->P.pol_h <= 0) return fail(FTL_E_INVALID, "policy_obs needs the same max_prev_obs on every ray sensor");
     const bool same_step = fin && (flags & (FTL_STEP_AUTO_RESET | FTL_STEP_QUEUE_RESET | FTL_STEP_SAMPLE_RESET));      // the terminal rows are copied
     if (fin && (!fin->ended || !fin->restarted)) return fail(FTL_E_INVALID, "ftl_final_outputs: ended / restarted missing");
     if (same_step && (!fin->obs_num || !fin->target || (h->P.lasers_len > 0 && !fin->lasers)))
@@ -615,17 +615,14 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
     FtlCall call; call.mode = 0; call.action = (const double*)action; call.action_kind = encoding; call.out = *out; call.flags = flags; call.scen_idx = nullptr; call.mask = nullptr; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
     call.ended = fin ? fin->ended : nullptr; call.restarted = fin ? fin->restarted : nullptr;
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
-    if (queue) {     // a plain step, then the queue's kernel and the reset pass of the slots that took an entry (ftl_queue.hpp)
+    if (queue || sample) {   // a plain step, then the chooser's kernel and the reset pass of the slots it restarts (ftl_restart.hpp)
+        if (sample) { rc = ftl_sampler_check_window(h); if (rc) return rc; }
         call.flags = 0; call.ended = nullptr; call.restarted = nullptr;
         rc = launch(h, call, stream);
-        return rc ? rc : ftl_queue_finish_step(h, call, out, fin, stream);
-    }
-    if (sample) {    // a plain step, then the sampler's kernel and the reset pass of the slots that finished (ftl_sampler.hpp)
-        rc = ftl_sampler_check_window(h);
         if (rc) return rc;
-        call.flags = 0; call.ended = nullptr; call.restarted = nullptr;
-        rc = launch(h, call, stream);
-        return rc ? rc : ftl_sampler_finish_step(h, call, out, fin, stream);
+        ftlrs::Args a;
+        rc = (queue ? ftl_queue_choose : ftl_sampler_choose)(h, out, fin, ftlrs::MODE_STEP, stream, a);
+        return rc ? rc : finish_step(h, call, out, fin, a.scen_idx, a.restarted, stream);
     }
     if (!same_step) return launch(h, call, stream);
     // same-step: the step defers the reset of the envs that finish (their terminal state gets the usual sensor scans), their terminal rows
@@ -633,14 +630,7 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
     // the step's join when the handle runs two streams
     call.flags = (flags & ~(uint32_t)FTL_STEP_AUTO_RESET) | FTL_CALL_DEFER_RESET;
     rc = launch(h, call, stream);
-    if (rc) return rc;
-    const int n = h->P.n_envs, epb = FTL_FC_THREADS;                  // envs per workgroup (64 per wavefront)
-    const int pol_len = (fin->policy_obs && out->policy_obs) ? h->P.pol_h * h->P.pol_width : 0;
-    hipLaunchKernelGGL(ftl::ftl_final_copy_kernel, dim3((unsigned)((n + epb - 1) / epb)), dim3(FTL_FC_THREADS), 0, (hipStream_t)stream,
-                       *out, *fin, n, h->P.lasers_len, pol_len);
-    FtlCall rcall = call;
-    rcall.mode = 1; rcall.flags = FTL_CALL_FINISH; rcall.mask = fin->ended; rcall.action = nullptr; rcall.ended = nullptr; rcall.restarted = nullptr;
-    return launch(h, rcall, stream);
+    return rc ? rc : finish_step(h, call, out, fin, nullptr, fin->ended, stream);
 }
 
 int ftl_kernel_timing(ftl_handle* h, int32_t enable) {
@@ -697,8 +687,6 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 #include "ftl_scenario_dev.hpp"  // the scenario generator on the GPU (ftl_generate_scenarios_device), same translation unit
 #include "ftl_render.hpp"        // batched top-down RGB frames (ftl_render), same translation unit
 #include "ftl_snapshot.hpp"      // snapshot / clone / restore of env rows (ftl_pack_envs, ftl_unpack_envs), same translation unit
-#include "ftl_queue.hpp"         // the episode queue (ftl_set_episode_queue, ftl_queue_start, FTL_STEP_QUEUE_RESET), same translation unit
-#include "ftl_sampler.hpp"       // the scenario sampler (ftl_set_scenario_sampler, ftl_sampler_start, FTL_STEP_SAMPLE_RESET), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

@@ -104,7 +104,7 @@ struct FtlCall {
 #define FTL_CALL_DEFER_RESET (1u << 30)   // step: an env that finishes records its episode as under FTL_STEP_AUTO_RESET but is not re-initialised
 #define FTL_CALL_FINISH (1u << 29)        // reset pass after a deferring step: scenario from the reset window's walk, auto-reset bookkeeping,
                                           // reward / done / status left as the step wrote them
-#define FTL_CALL_QUEUE (1u << 28)         // with FTL_CALL_FINISH: the scenario comes from scen_idx (the episode queue's entry) instead of the walk
+#define FTL_CALL_SCEN_IDX (1u << 28)      // with FTL_CALL_FINISH: the scenario comes from scen_idx (the queue's entry, the sampler's draw) instead of the walk
 
 // field `f0` (its address inside record 0) of env `env`
 template <typename T>

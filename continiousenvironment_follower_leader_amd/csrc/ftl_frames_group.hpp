@@ -1451,7 +1451,7 @@ __global__ void __launch_bounds__(FTL_FC_THREADS) ftl_final_copy_kernel(const ft
 
 // XR = the instantiations that carry the restart of finished envs on a later call: FTL_STEP_NEXT_RESET (an env that is done on entry is
 // re-initialised instead of stepped), the deferred reset of ftl_step_final under FTL_STEP_AUTO_RESET (FTL_CALL_DEFER_RESET, then a
-// FTL_CALL_FINISH reset pass; with FTL_CALL_QUEUE that pass takes its scenarios from scen_idx -- the episode queue, ftl_queue.hpp) and the
+// FTL_CALL_FINISH reset pass; with FTL_CALL_SCEN_IDX that pass takes its scenarios from scen_idx -- the episode queue, ftl_queue.hpp) and the
 // ended / restarted masks.  XR = false compiles to the step / reset kernels of before.
 template <int G, bool REG, bool XR = false>
 __global__ void __launch_bounds__(FTL_WAVE, FTL_FRAMESG_WPE) ftl_frames_group_kernel(const FtlDevParams* __restrict__ Pp, const FtlCall C) {
@@ -1488,7 +1488,7 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_FRAMESG_WPE) ftl_frames_group_ke
         g_load<G>(P, E);                                 // keeps the state of masked-out envs intact (nothing is stored for them)
         if (E.valid) E.err_acc |= E.error;               // the episode being replaced may have raised error bits: they stay in the sticky word
         if (fin && E.valid) E.episodes += 1;             // the bookkeeping of the in-kernel auto-reset
-        g_reset<G>(P, E, E.valid ? ((fin && !(C.flags & FTL_CALL_QUEUE)) ? C.win_base + ((E.scen % C.win_count) + C.win_stride) % C.win_count : C.scen_idx[E.env]) : E.scen, E.valid);
+        g_reset<G>(P, E, E.valid ? ((fin && !(C.flags & FTL_CALL_SCEN_IDX)) ? C.win_base + ((E.scen % C.win_count) + C.win_stride) % C.win_count : C.scen_idx[E.env]) : E.scen, E.valid);
         if (E.valid && E.r == 0 && !fin) {
             C.out.reward[E.env] = 0.0; C.out.done[E.env] = (uint8_t)E.done;
             C.out.status[3 * (size_t)E.env] = 0; C.out.status[3 * (size_t)E.env + 1] = 0; C.out.status[3 * (size_t)E.env + 2] = 0;

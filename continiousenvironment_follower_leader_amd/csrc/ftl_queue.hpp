@@ -1,15 +1,16 @@
-// ftl_queue.hpp -- the episode queue (include/ftl.h: ftl_set_episode_queue, ftl_queue_start, FTL_STEP_QUEUE_RESET).  Included at the end
-// of ftl_abi.hip (same translation unit: it reads the handle).
+// ftl_queue.hpp -- the episode queue (include/ftl.h: ftl_set_episode_queue, ftl_queue_start, FTL_STEP_QUEUE_RESET).  Included by
+// ftl_abi.hip after ftl_restart.hpp (same translation unit: it reads the handle).
 //
-// ftl_queue_kernel runs between a step without auto-reset and the masked reset pass of ftl_step_final.  It is ONE workgroup: the hand-out
-// order (ascending slot order within a call) needs a rank over all finishing slots, and there are few of them (about 0.5 % of the envs per
-// step).  Wavefront w owns the contiguous slots [w * span, (w + 1) * span), in rows of 64; a lane looks at one done byte per row, sixteen
-// rows in flight.  Sweep 1 counts the finishing slots of every wavefront with ballots; one pass over the wavefronts' totals in LDS gives
-// every wavefront its offset, and one lane takes `total` entries with a single agent-scope fetch-add on the queue's head.  Sweep 2 ranks
-// the finishing slots of a row with the same ballots and writes them, in ascending order, to a list; then every lane does the work of one
-// list entry (rank = list index): the record of the entry that ended, the next entry, the scenario index / mask byte of the reset pass,
-// the random-stream words of a fresh env.  (Doing that work inside sweep 2 serialised its dependent loads row by row: 90 us a call at
-// 65,536 envs with 280 finishing slots.)  Every write is an ordinary vector store.
+// ftl_queue_kernel is the queue's chooser (ftl_restart.hpp): it runs between a step without auto-reset and the masked reset pass of
+// ftl_step_final.  It is ONE workgroup: the hand-out order (ascending slot order within a call) needs a rank over all finishing slots, and
+// there are few of them (about 0.5 % of the envs per step).  Wavefront w owns the contiguous slots [w * span, (w + 1) * span), in rows of
+// 64; a lane looks at one done byte per row, sixteen rows in flight.  Sweep 1 counts the finishing slots of every wavefront with ballots;
+// one pass over the wavefronts' totals in LDS gives every wavefront its offset, and one lane takes `total` entries with a single
+// agent-scope fetch-add on the queue's head.  Sweep 2 ranks the finishing slots of a row with the same ballots and writes them, in
+// ascending order, to a list; then every lane does the work of one list entry (rank = list index): the record of the entry that ended, the
+// next entry, the scenario index / mask byte of the reset pass, the random-stream words of a fresh env.  (Doing that work inside sweep 2
+// serialised its dependent loads row by row: 90 us a call at 65,536 envs with 280 finishing slots.)  Every write is an ordinary vector
+// store.
 #include <hip/hip_runtime.h>
 
 #define FTL_QK_THREADS 1024       // 16 wavefronts
@@ -17,18 +18,13 @@
 
 namespace ftlq {
 
-enum { MODE_STEP = 0, MODE_START = 1 };
+using ftlrs::MODE_STEP;
+using ftlrs::MODE_START;
 
-struct Args {
+struct Args : ftlrs::Args {
     ftl_episode_queue q;
-    int32_t* env_int; double* env_dbl; double* ep_stats;   // state fields (record 0 / env 0), as in FtlDevParams
-    const int32_t* route_len;       // of the scenario pool: 0 = the world is done at reset
-    uint8_t* done; const uint8_t* status;                  // ftl_outputs of the step
-    int32_t* scen_idx;              // [n_envs] out: pool index of the entry a slot took (the reset pass's scen_idx)
     int32_t* list;                  // [n_envs] scratch: the finishing slots of this call in ascending order
-    uint8_t* ended; uint8_t* restarted;                    // [n_envs] out, every slot
-    int32_t rec_stride, n_envs, env_id_base, mode;
-    int32_t now, span;              // the handle's call counter; slots per wavefront (a multiple of 64)
+    int32_t span;                   // slots per wavefront (a multiple of 64)
 };
 
 __device__ __forceinline__ bool finishing(const Args& a, int e) {      // (the ticket is read only where the done byte is set)
@@ -37,23 +33,19 @@ __device__ __forceinline__ bool finishing(const Args& a, int e) {      // (the t
 
 // slot e ended the episode of its ticket (MODE_STEP) and takes entry `next`
 __device__ __forceinline__ void hand_over(const Args& a, int e, int next) {
-    int* ei = reinterpret_cast<int*>(reinterpret_cast<char*>(a.env_int) + (size_t)e * a.rec_stride);
+    int* ei = ftlrs::env_words(a, e);
     if (a.mode == MODE_STEP) {
-        const double* ed = reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.env_dbl) + (size_t)e * a.rec_stride);
+        const ftlrs::Ended v = ftlrs::end_episode(a, e);
         ftl_episode_record* r = a.q.records + a.q.ticket[e];
-        const int scen = ei[FTL_EI_SCEN];
-        const bool at_reset = a.route_len[scen] == 0;          // the only world g_reset leaves done (ENV:508-510)
-        r->scenario = scen; r->env = e;
-        r->frames = at_reset ? 0 : ei[FTL_EI_STEP_COUNT];
-        r->calls = at_reset ? 0 : a.now - r->calls;
-        r->status[0] = at_reset ? 0 : a.status[3 * (size_t)e]; r->status[1] = at_reset ? 0 : a.status[3 * (size_t)e + 1];
-        r->status[2] = at_reset ? 0 : a.status[3 * (size_t)e + 2];
-        r->errors = (uint32_t)ei[FTL_EI_ERROR];
-        r->flags = at_reset ? FTL_EPISODE_DONE_AT_RESET : 0u;
-        r->ret = at_reset ? 0.0 : ed[FTL_ED_OVERALL_REWARD];
+        r->scenario = v.scen; r->env = e;
+        r->frames = v.frames;
+        r->calls = v.at_reset ? 0 : a.now - r->calls;
+        r->status[0] = v.status[0]; r->status[1] = v.status[1]; r->status[2] = v.status[2];
+        r->errors = v.errors;
+        r->flags = v.at_reset ? FTL_EPISODE_DONE_AT_RESET : 0u;
+        r->ret = v.ret;
         r->stream = (int64_t)a.env_id_base + e + ei[FTL_EI_STREAM];
         r->state = 2;
-        if (at_reset) a.ep_stats[(size_t)e * FTL_N_METRICS + FTL_M_EPISODES] += 1.0;      // (the step records the others when it raises done)
     }
     const bool take = next < a.q.n;
     if (take) {
@@ -125,42 +117,25 @@ __global__ __launch_bounds__(FTL_QK_THREADS) void ftl_queue_kernel(const Args a)
 __global__ void ftl_queue_park_kernel(const Args a) {
     const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (e >= a.n_envs || a.q.ticket[e] >= 0) return;
-    reinterpret_cast<int*>(reinterpret_cast<char*>(a.env_int) + (size_t)e * a.rec_stride)[FTL_EI_DONE] = 1;
+    ftlrs::env_words(a, e)[FTL_EI_DONE] = 1;
     a.done[e] = 1;
 }
 
 }  // namespace ftlq
 
-struct FtlQueueState {
-    ftl_episode_queue q;
-    bool attached;
-    int32_t calls;               // ftl_step* calls with FTL_STEP_QUEUE_RESET on this handle (the records' call stamps)
-    void* mem;                   // scen_idx | list | ended | restarted (library-owned, allocated by the first launch)
-};
-
-namespace ftlq {
-
-static int prepare(ftl_handle* h, Args& a, const ftl_outputs* out, int mode) {
-    FtlQueueState& Q = *h->queue;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    const size_t n = (size_t)h->P.n_envs, o_list = align_up(n * 4, 256), o_ended = 2 * o_list, o_rest = o_ended + align_up(n, 256);
-    if (!Q.mem) {
-        e = hipMalloc(&Q.mem, o_rest + align_up(n, 256));
-        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(queue): ") + hipGetErrorString(e));
-    }
-    memset(&a, 0, sizeof a);
-    a.q = Q.q;
-    a.env_int = h->P.env_int; a.env_dbl = h->P.env_dbl; a.ep_stats = h->P.ep_stats; a.route_len = h->P.scen.route_len;
-    a.done = out->done; a.status = out->status;
-    a.scen_idx = (int32_t*)Q.mem; a.list = (int32_t*)((char*)Q.mem + o_list); a.ended = (uint8_t*)Q.mem + o_ended; a.restarted = (uint8_t*)Q.mem + o_rest;
-    a.rec_stride = h->P.rec_stride; a.n_envs = h->P.n_envs; a.env_id_base = h->P.cfg.env_id_base; a.mode = mode; a.now = Q.calls;
-    const int waves = FTL_QK_THREADS / FTL_WAVE;
-    a.span = (int)align_up((n + waves - 1) / waves, FTL_WAVE);
-    return FTL_OK;
+// the kernels' arguments of one call: the shared ones and the queue's own
+static ftlq::Args ftl_queue_args(const ftl_handle* h, const ftlrs::Args& r) {
+    const size_t waves = FTL_QK_THREADS / FTL_WAVE;
+    return ftlq::Args{r, h->queue.v, h->rs.list, (int32_t)align_up(((size_t)h->P.n_envs + waves - 1) / waves, FTL_WAVE)};
 }
 
-}  // namespace ftlq
+// FtlChoose of the queue: records and hand-out (MODE_START: every slot takes an entry)
+static int ftl_queue_choose(ftl_handle* h, const ftl_outputs* out, const ftl_final_outputs* fin, int mode, void* stream, ftlrs::Args& r) {
+    int rc = restart_args(h, r, out, fin, mode, h->queue.calls);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ftlq::ftl_queue_kernel, dim3(1), dim3(FTL_QK_THREADS), 0, (hipStream_t)stream, ftl_queue_args(h, r));
+    return FTL_OK;
+}
 
 extern "C" {
 
@@ -169,67 +144,26 @@ size_t ftl_sizeof_episode_queue(void) { return sizeof(ftl_episode_queue); }
 
 int ftl_set_episode_queue(ftl_handle* h, const ftl_episode_queue* q) {
     if (!h) return fail(FTL_E_INVALID, "null argument");
-    if (!q) { if (h->queue) h->queue->attached = false; return FTL_OK; }
+    if (!q) { h->queue.attached = false; return FTL_OK; }
     if (!q->scenario || !q->head || !q->records || !q->ticket) return fail(FTL_E_INVALID, "ftl_episode_queue: scenario / head / records / ticket missing");
     if (q->n <= 0) return fail(FTL_E_INVALID, "ftl_episode_queue: n must be positive");
     if (((uintptr_t)q->records) & 7) return fail(FTL_E_INVALID, "ftl_episode_queue: records must be 8-byte aligned");
     if (!q->stream && (q->stream_base < 0 || q->stream_base + (int64_t)q->n - 1 > 0x7fffffffLL))
         return fail(FTL_E_INVALID, "ftl_episode_queue: stream ids stream_base .. stream_base + n - 1 must lie in 0 .. INT32_MAX");
-    if (!h->queue) {
-        h->queue = new (std::nothrow) FtlQueueState();
-        if (!h->queue) return fail(FTL_E_DEVICE, "out of host memory");
-        h->queue->mem = nullptr;
-    }
-    h->queue->q = *q; h->queue->attached = true; h->queue->calls = 0;
+    h->queue = {*q, true, 0};
     return FTL_OK;
 }
 
 int ftl_queue_start(ftl_handle* h, const ftl_outputs* out, void* stream) {
     if (!h) return fail(FTL_E_INVALID, "null argument");
-    if (!h->queue || !h->queue->attached) return fail(FTL_E_STATE, "ftl_set_episode_queue has not been called");
-    if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
-    if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
-    int rc = check_out(h, out);
+    if (!h->queue.attached) return fail(FTL_E_STATE, "ftl_set_episode_queue has not been called");
+    ftlrs::Args r;
+    int rc = start_chosen(h, out, stream, ftl_queue_choose, r);
     if (rc) return rc;
-    ftlq::Args a;
-    rc = ftlq::prepare(h, a, out, ftlq::MODE_START);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ftlq::ftl_queue_kernel, dim3(1), dim3(FTL_QK_THREADS), 0, (hipStream_t)stream, a);
-    rc = ftl_reset(h, a.scen_idx, nullptr, out, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ftlq::ftl_queue_park_kernel, dim3((unsigned)((a.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ftlq::ftl_queue_park_kernel, dim3((unsigned)((r.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ftl_queue_args(h, r));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
     return FTL_OK;
 }
 
 }  // extern "C"
-
-static void ftl_queue_destroy(ftl_handle* h) {
-    if (!h->queue) return;
-    if (h->queue->mem) { (void)hipSetDevice(h->device); (void)hipFree(h->queue->mem); }
-    delete h->queue; h->queue = nullptr;
-}
-
-static int ftl_queue_attached(const ftl_handle* h) { return h->queue && h->queue->attached; }
-
-// FTL_STEP_QUEUE_RESET of ftl_step_final, after the step (a plain one: no flag) was launched on `stream`: records and hand-out, the terminal
-// rows, the reset pass over the slots that took an entry
-static int ftl_queue_finish_step(ftl_handle* h, const FtlCall& step, const ftl_outputs* out, const ftl_final_outputs* fin, void* stream) {
-    h->queue->calls += 1;
-    ftlq::Args a;
-    int rc = ftlq::prepare(h, a, out, ftlq::MODE_STEP);
-    if (rc) return rc;
-    if (fin) { a.ended = fin->ended; a.restarted = fin->restarted; }
-    hipLaunchKernelGGL(ftlq::ftl_queue_kernel, dim3(1), dim3(FTL_QK_THREADS), 0, (hipStream_t)stream, a);
-    if (fin) {
-        const int n = h->P.n_envs, epb = FTL_FC_THREADS;
-        const int pol_len = (fin->policy_obs && out->policy_obs) ? h->P.pol_h * h->P.pol_width : 0;
-        hipLaunchKernelGGL(ftl::ftl_final_copy_kernel, dim3((unsigned)((n + epb - 1) / epb)), dim3(FTL_FC_THREADS), 0, (hipStream_t)stream,
-                           *out, *fin, n, h->P.lasers_len, pol_len);
-    }
-    FtlCall rcall = step;
-    rcall.mode = 1; rcall.flags = FTL_CALL_FINISH | FTL_CALL_QUEUE; rcall.scen_idx = a.scen_idx; rcall.mask = a.restarted; rcall.action = nullptr;
-    rcall.ended = nullptr; rcall.restarted = nullptr;
-    return launch(h, rcall, stream);
-}

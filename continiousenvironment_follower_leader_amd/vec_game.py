@@ -222,7 +222,7 @@ class _BatchBase:
             raise _lib.FtlError("set_episode_queue() first")
 
     def _need_sampler(self):
-        if getattr(self, "sampler", None) is None:
+        if self.sampler is None:
             raise _lib.FtlError("set_scenario_sampler() first")
 
     def _check_sampler(self, sampler):
@@ -550,11 +550,11 @@ class VecGame(_BatchBase):
         if auto_reset == "next_step":
             return abi.FTL_STEP_NEXT_RESET, fin
         if auto_reset == "queue":
-            if getattr(self, "queue", None) is None:
+            if self.queue is None:
                 raise _lib.FtlError('auto_reset="queue" needs set_episode_queue() first')
             return abi.FTL_STEP_QUEUE_RESET, fin
         if auto_reset == "sample":
-            if getattr(self, "sampler", None) is None:
+            if self.sampler is None:
                 raise _lib.FtlError('auto_reset="sample" needs set_scenario_sampler() first')
             return abi.FTL_STEP_SAMPLE_RESET, fin
         raise ValueError('auto_reset must be False, True, "same_step", "next_step", "queue" or "sample" (got %r)' % (auto_reset,))
@@ -1188,13 +1188,17 @@ class PipelinedVecGame(_BatchBase):
         self.join()
         return torch.cat([g.state_field(name) for g in self.games], 0)
 
-    def reset(self, scen_idx=None, mask=None):
-        scen_idx, mask = self._reset_args(scen_idx, mask)
+    def _reset_parts(self, reset):
+        """``reset(game, shard)`` of every part on its stream, then ``join()``; returns the first observations like ``reset``."""
         for k, (g, sh) in enumerate(zip(self.games, self.shards)):
             with self._on(k):
-                g.reset(scen_idx[sh.lo:sh.hi], None if mask is None else mask[sh.lo:sh.hi])
+                reset(g, sh)
         self.join()
         return self.obs_num, self.lasers
+
+    def reset(self, scen_idx=None, mask=None):
+        scen_idx, mask = self._reset_args(scen_idx, mask)
+        return self._reset_parts(lambda g, sh: g.reset(scen_idx[sh.lo:sh.hi], None if mask is None else mask[sh.lo:sh.hi]))
 
     def step_part(self, k, action, auto_reset=False):
         """One step of part k on its stream; ``action`` = the rows of part k (any layout ``VecGame.step`` takes); ``auto_reset`` as
@@ -1245,11 +1249,7 @@ class PipelinedVecGame(_BatchBase):
     def reset_from_queue(self):
         """``VecGame.reset_from_queue`` of every part on its stream, then ``join()``."""
         self._need_queue()
-        for k, g in enumerate(self.games):
-            with self._on(k):
-                g.reset_from_queue()
-        self.join()
-        return self.obs_num, self.lasers
+        return self._reset_parts(lambda g, sh: g.reset_from_queue())
 
     def set_scenario_sampler(self, sampler):
         """``VecGame.set_scenario_sampler`` for the whole batch: the parts share ONE sampler -- one table, one cdf -- and, their draws being
@@ -1278,11 +1278,7 @@ class PipelinedVecGame(_BatchBase):
     def reset_from_sampler(self):
         """``VecGame.reset_from_sampler`` of every part on its stream, then ``join()``."""
         self._need_sampler()
-        for k, g in enumerate(self.games):
-            with self._on(k):
-                g.reset_from_sampler()
-        self.join()
-        return self.obs_num, self.lasers
+        return self._reset_parts(lambda g, sh: g.reset_from_sampler())
 
     def episode_metrics(self, clear=False):
         self.join()

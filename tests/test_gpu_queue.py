@@ -460,6 +460,59 @@ def test_old_flags_after_attach_and_detach(name):
     b.close()
 
 
+# ---------------------------------------------------------------- 10. queue, sampler and same-step on one handle
+def _same_rows(a, b, what):
+    for k, row in a.output_rows().items():
+        assert torch.equal(row, b.output_rows()[k]), (what, k)
+
+
+@pytest.mark.parametrize("final", [True, False], ids=["final buffers", "no final buffers"])
+def test_three_restart_sources_on_one_handle(final, lanes_per_env):
+    """A sampler stays attached to batch A while A plays a queue and while it steps in the other auto-reset modes: the handle's one
+    restart scratch and its two call counters serve all of them.  B (a sampler of its own, never a queue) and C (never a sampler) are
+    the yardsticks.  130 envs: three populated wavefronts of the queue's kernel, the last with a partial row, and a partial workgroup of
+    the sampler's.  Without the final buffers the masks of both choosers live in the handle's scratch, and same-step, which needs
+    the buffers, gives its turns to the in-kernel auto-reset."""
+    from test_gpu_sampler import FIELDS, _new_sampler
+    cfg, pool = _cfg_pool("B")
+    n, q_len = 130, 200
+    pol = _policy("hashed", cfg)
+    A, B, C = (_vec(cfg, pool, n, final_obs=final) for _ in range(3))
+    sa, sb = _new_sampler(pool), _new_sampler(pool)
+    A.set_scenario_sampler(sa)
+    B.set_scenario_sampler(sb)
+    A.reset_from_sampler()
+    B.reset_from_sampler()
+    for t in range(20):
+        A.step(pol((A.obs_num, A.lasers)), auto_reset="sample")
+        B.step(pol((B.obs_num, B.lasers)), auto_reset="sample")
+        _same_rows(A, B, ("sample", t))
+    snap = A.snapshot()
+    scen, streams = _queue_scen(pool, q_len), S0 + torch.arange(q_len)
+    rec_a = A.evaluate(pol, scen, stream_ids=streams)
+    assert A.sampler is sa and A.queue is None
+    rec_c = C.evaluate(pol, scen, stream_ids=streams)
+    assert (rec_a["state"] == 2).all()
+    for c in (col[0] for col in abi.RECORD_DTYPE):
+        assert np.array_equal(rec_a[c], rec_c[c]), c
+    A.restore(snap, slot_stats=True)
+    modes = ("sample", "same_step" if final else True, "sample", True, "next_step", "sample")
+    for t in range(24):
+        act = pol((B.obs_num, B.lasers))
+        A.step(act, auto_reset=modes[t % len(modes)])
+        B.step(act, auto_reset=modes[t % len(modes)])
+        _same_rows(A, B, (modes[t % len(modes)], t))
+    for f in FIELDS:
+        assert torch.equal(A.state_field(f), B.state_field(f)), f
+    assert torch.equal(A.episode_metrics(), B.episode_metrics())
+    ta, tb = sa.table(), sb.table()
+    assert int(ta["episodes"].sum()) > n
+    for k in ta:
+        assert torch.equal(ta[k], tb[k]), k
+    for e in (A, B, C):
+        e.close()
+
+
 def test_snapshot_and_state_dict_are_refused_with_a_queue():
     cfg, pool = _cfg_pool("B")
     env = _vec(cfg, pool, 8)

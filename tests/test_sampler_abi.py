@@ -8,6 +8,7 @@ import math
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -143,6 +144,66 @@ def test_call_order_with_a_sampler_attached(lib, handle):
     assert b"ftl_bind_state" in lib.ftl_last_error()
     assert lib.ftl_sampler_start(handle, C.byref(out), None) == abi.FTL_E_STATE
     assert b"ftl_bind_state" in lib.ftl_last_error()
+
+
+def _attach_both(lib, handle):
+    from test_queue_abi import _queue
+    assert lib.ftl_set_episode_queue(handle, C.byref(_queue())) == 0, lib.ftl_last_error()
+    assert lib.ftl_set_scenario_sampler(handle, C.byref(_sampler())) == 0, lib.ftl_last_error()
+
+
+def test_queue_and_sampler_on_one_handle_are_detached_one_by_one(lib, handle):
+    """Both attached to one handle; detaching either leaves the other attached: its step and start calls pass the attachment check and
+    fail on ftl_bind_state (as test_call_order_with_a_sampler_attached), those of the detached one fail with their own message."""
+    out, act = abi.Outputs(), C.c_void_p(FAKE)
+    queue = (lib.ftl_set_episode_queue, abi.FTL_STEP_QUEUE_RESET, lib.ftl_queue_start,
+             b"FTL_STEP_QUEUE_RESET without an episode queue (ftl_set_episode_queue)", b"ftl_set_episode_queue has not been called")
+    sampler = (lib.ftl_set_scenario_sampler, abi.FTL_STEP_SAMPLE_RESET, lib.ftl_sampler_start,
+               b"FTL_STEP_SAMPLE_RESET without a scenario sampler (ftl_set_scenario_sampler)", b"ftl_set_scenario_sampler has not been called")
+    for gone, kept in ((queue, sampler), (sampler, queue)):
+        _attach_both(lib, handle)
+        assert gone[0](handle, None) == 0
+        assert lib.ftl_step_final(handle, act, abi.FTL_ACTION_BOX2, C.byref(out), None, gone[1], None) == abi.FTL_E_STATE
+        assert lib.ftl_last_error() == gone[3]
+        assert gone[2](handle, C.byref(out), None) == abi.FTL_E_STATE
+        assert lib.ftl_last_error() == gone[4]
+        assert lib.ftl_step_final(handle, act, abi.FTL_ACTION_BOX2, C.byref(out), None, kept[1], None) == abi.FTL_E_STATE
+        assert b"ftl_bind_state" in lib.ftl_last_error()
+        assert kept[2](handle, C.byref(out), None) == abi.FTL_E_STATE
+        assert b"ftl_bind_state" in lib.ftl_last_error()
+
+
+_DEVICE_STUB = """
+static int calls;
+int hipSetDevice(int device) { (void)device; calls++; return 100; }
+int hipFree(void* p) { (void)p; calls++; return 100; }
+int device_calls(void) { return calls; }
+"""
+
+_DESTROY_SCRIPT = """
+import ctypes as C, sys
+stub = C.CDLL(sys.argv[1], mode=C.RTLD_GLOBAL)      # loaded first, so the library's hipSetDevice / hipFree resolve to the counting ones
+from continiousenvironment_follower_leader_amd import _lib, abi, make_config
+lib = C.CDLL(_lib.SO_PATH)
+cfg, h = make_config(bear_number=1), C.c_void_p()
+assert lib.ftl_create(C.byref(cfg.c), 4, 0, C.byref(h)) == 0
+q, s = abi.EpisodeQueueC(), abi.ScenarioSamplerC()
+q.scenario = q.head = q.records = q.ticket = s.weight = s.cdf = s.table = 4096
+q.n = s.count = 8
+assert lib.ftl_set_episode_queue(h, C.byref(q)) == 0 and lib.ftl_set_scenario_sampler(h, C.byref(s)) == 0
+before = stub.device_calls()
+assert lib.ftl_sampler_refresh(h, None) == abi.FTL_E_DEVICE and stub.device_calls() == before + 1      # the stub is what the library calls
+lib.ftl_destroy(h)
+assert stub.device_calls() == before + 1, "ftl_destroy touched the device"
+"""
+
+
+def test_destroy_with_both_attached_and_nothing_launched_leaves_the_device_alone(lib, tmp_path):
+    """A process of its own, in which a counting hipSetDevice / hipFree stands in front of the runtime's."""
+    (tmp_path / "stub.c").write_text(_DEVICE_STUB)
+    so = str(tmp_path / "libstub.so")
+    subprocess.check_call([_lib.HIPCC, "-x", "c", "-shared", "-fPIC", str(tmp_path / "stub.c"), "-o", so])
+    subprocess.check_call([sys.executable, "-c", _DESTROY_SCRIPT, so], cwd=ROOT)
 
 
 def test_python_mode_needs_no_device():
