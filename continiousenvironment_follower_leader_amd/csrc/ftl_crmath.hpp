@@ -1,5 +1,5 @@
 // ftl_crmath.hpp -- atan, sin and cos of a double, correctly rounded: evaluated in double-double (about 104 bits) and rounded once.
-// The scenario generator on the GPU (ftl_scenario_dev.hpp) calls them where generate_one (ftl_scenario.cpp) calls glibc's atan / sin / cos:
+// The scenario generator on the GPU calls them (DevicePolicy of ftl_scenario_core.hpp) where the host's (HostPolicy) calls glibc's atan / sin / cos:
 // glibc's results are within a fraction of an ulp of the exact value and equal the correctly rounded ones on every input the generator
 // produced for the seeds tested (not on every double: on random doubles about once in 1,000-2,000 calls they differ), while the device
 // math library's differ often enough to change the start direction of 2-12 % of the worlds.  A few calls per scenario, on one lane: speed does not matter here.

@@ -7,6 +7,9 @@ several equal-cost routes dstar.py returns depends on CPython object ids (set it
 route is checked statistically (>= 99 % here) and a scenario whose route differs is compared up to the route."""
 import ctypes as C
 import json
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +17,9 @@ import pytest
 from continiousenvironment_follower_leader_amd import _lib, abi
 from continiousenvironment_follower_leader_amd.scenario import generate_scenarios, scen_params
 from golden_util import GOLDEN, config_for, episode_names, load_episode, scenario_arrays
+from test_scenario_gen_device import SEEDS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _route_cost(r, sg=10):
@@ -113,6 +119,48 @@ def test_generator_route_properties_and_threads():
         d = np.linalg.norm(a["robot_pos"][i, 1] - a["robot_pos"][i, 0])
         assert sp.min_distance * 1.1 - 1e-3 <= d <= sp.max_distance * 0.9
         assert a["init_traj_len"][i] == int(np.float32(d) / (sp.trajectory_saving_period * sp.leader_max_speed)) or True
+
+
+@pytest.fixture(scope="module")
+def policy_program(tmp_path_factory):
+    """tests/host/scenario_policy_main.cpp + csrc/ftl_scenario.cpp built with FTL_SCEN_DEVICE_POLICY under AddressSanitizer and UBSan: the
+    sequential program as the device generator instantiates it (ftl_crmath, the draw cap) around the host planner, as a stand-alone program."""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(_lib.HIPCC)))
+    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("clang++", path=os.path.join(rocm, "llvm", "bin") + os.pathsep + os.path.join(rocm, "lib", "llvm", "bin"))
+    assert cxx, "no host C++ compiler (g++ / clang++) for the sanitizer build"
+    exe = str(tmp_path_factory.mktemp("policy") / "scenario_policy_main")
+    # the sanitizer runtimes inside the program (clang's default): it does not depend on the order in which shared libraries get loaded
+    static = ["-static-libasan", "-static-libubsan"] if os.path.basename(cxx).startswith("g++") else ["-static-libsan"]
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + static +
+                          ["-DFTL_SCEN_DEVICE_POLICY", "-pthread", "-o", exe, os.path.join(ROOT, "tests", "host", "scenario_policy_main.cpp"),
+                           os.path.join(ROOT, "continiousenvironment_follower_leader_amd", "csrc", "ftl_scenario.cpp")])
+    return exe
+
+
+@pytest.mark.parametrize("name", ["B_s1_chase", "Bmep_s2_chase", "Btraj_s3_chase"])     # one finish point, three, a caller's route
+def test_device_policy_matches_product_on_cpu(policy_program, tmp_path, name):
+    """What lane 0 of the device generator computes (csrc/ftl_scenario_core.hpp with DevicePolicy) equals the product's host generator
+    (HostPolicy: glibc, no cap) on the seeds of test_scenario_gen_device.py -- every array, every status byte, no FTL_SCEN_GEN_LIMIT --
+    and runs clean under AddressSanitizer / UBSan."""
+    _, meta = load_episode(name)
+    cfg = config_for(meta, scen_route_len=256)
+    sp = scen_params(cfg)
+    seeds = np.ascontiguousarray(SEEDS, np.int64)
+    fixed = np.ctypeslib.as_array(C.cast(sp.fixed_route, C.POINTER(C.c_double)), (sp.fixed_route_len * 2,)) if sp.planner == 2 else np.zeros(0)
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+    src.write_bytes(bytes(cfg.c) + bytes(sp) + np.int64(len(seeds)).tobytes() + seeds.tobytes() + fixed.astype(np.float64).tobytes())
+    run = subprocess.run([policy_program, str(src), str(dst), "8"], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-4000:]
+    h = generate_scenarios(cfg, seeds, n_threads=8)
+    raw, at = dst.read_bytes(), 0
+    for k in ("static_rects", "robot_pos", "robot_dir", "robot_rect", "route", "route_len", "init_traj", "init_traj_len", "status"):
+        got = np.frombuffer(raw, h[k].dtype, h[k].size, at).reshape(h[k].shape)
+        at += h[k].nbytes
+        assert np.array_equal(got, h[k]), (k, np.nonzero((got != h[k]).reshape(len(seeds), -1).any(1))[0][:10])
+        if k == "status":
+            assert not (got & abi.SCEN_GEN_LIMIT).any()
+    assert at == len(raw)
+    assert h["usable"].sum() > 0.3 * len(seeds)
 
 
 @pytest.mark.gpu
