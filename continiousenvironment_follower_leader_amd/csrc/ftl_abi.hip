@@ -50,6 +50,7 @@ struct ftl_handle {
     int G;                   // lanes per env in the frame kernel (set_lanes)
     int co_envs, cus;        // envs stepped on the device at the same time (ftl_tune; default: this handle's), CUs of the device
     bool g_env;              // FTL_DEBUG_G8 was given
+    bool one_pass;           // the ray kernel's one-pass form is launched (all ray sensors on one side of the tracker; FTL_RAYS_ONE_PASS=0: never)
     int rg_slots, rg_epw;    // frame-kernel wavefronts one round holds on this device / envs per wavefront (the cost sort's auto rule)
     // optionally the slot groups are stepped as two interleaved halves on two streams (the caller's stream waits for the side
     // stream): the ray kernel of one half fills the tail of the other half's frame kernel
@@ -254,6 +255,11 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
             }
             P.pass_rays[which] = g - P.pass_base[which];
         }
+        // Every shipped config scans all its ray sensors on one side of the tracker: the other pass has nothing to do, and the kernels
+        // compiled without the loop over the passes run the one that has.  FTL_RAYS_ONE_PASS=0/1 overrides (1 is the default where it applies).
+        P.pass_single = P.pass_rays[0] > 0 && P.pass_rays[1] > 0 ? -1 : (P.pass_rays[1] > 0 ? 1 : 0);
+        const char* op = getenv("FTL_RAYS_ONE_PASS");
+        h->one_pass = P.pass_single >= 0 && !(op && op[0] == '0');
     }
     if (rays > 1023) { delete h; return fail(FTL_E_INVALID, "more than 1023 rays per env (the candidate list of the ray kernel packs a ray index into 10 bits)"); }
     if (hmax * (P.R - 1) > FTL_WAVE) { delete h; return fail(FTL_E_INVALID, "max_prev_obs x (1 + bears) exceeds one wavefront of snapshot rects"); }
@@ -507,9 +513,12 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
             const dim3 rgrid(count);
             // CAPPED: the LDS copy of the corridor ring is smaller than the ring (corr_cap > 128, the configs with regimes or the v1 tracker):
             // the instantiations that carry the unstaged path
-#define FTL_LAUNCH_RAYS(HM_, EXPL_, SPLIT_) do { \
-                if (capped) hipLaunchKernelGGL((ftl_rays_kernel<HM_, EXPL_, SPLIT_, true>), rgrid, block, h->P.lds_rays, s, h->dP, c2); \
-                else hipLaunchKernelGGL((ftl_rays_kernel<HM_, EXPL_, SPLIT_, false>), rgrid, block, h->P.lds_rays, s, h->dP, c2); } while (0)
+#define FTL_LAUNCH_RAYS_P(HM_, EXPL_, SPLIT_, ONE_) do { \
+                if (capped) hipLaunchKernelGGL((ftl_rays_kernel<HM_, EXPL_, SPLIT_, true, ONE_>), rgrid, block, h->P.lds_rays, s, h->dP, c2); \
+                else hipLaunchKernelGGL((ftl_rays_kernel<HM_, EXPL_, SPLIT_, false, ONE_>), rgrid, block, h->P.lds_rays, s, h->dP, c2); } while (0)
+#define FTL_LAUNCH_RAYS(HM_, EXPL_, SPLIT_) FTL_LAUNCH_RAYS_P(HM_, EXPL_, SPLIT_, false)
+            // the one-stream kernels of the common sensors also exist without the loop over the passes (ONE_PASS, ftl_device.hpp)
+#define FTL_LAUNCH_RAYS_1(HM_) do { if (h->one_pass) FTL_LAUNCH_RAYS_P(HM_, false, false, true); else FTL_LAUNCH_RAYS_P(HM_, false, false, false); } while (0)
             const bool capped = h->P.corr_lds_cap < h->P.cfg.corr_cap;
             if (parts > 1) {   // two-stream mode: the instantiations that map blocks to one half of the slot groups
                 if (!expl && h->P.hmax > 5 && h->P.hmax <= 10) FTL_LAUNCH_RAYS(10, false, true);
@@ -518,11 +527,13 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
             } else if (expl) {        // LeaderCorridor_lasers or pad_sectors somewhere in the config: the two instantiations that carry that code
                 if (h->P.hmax <= 5) FTL_LAUNCH_RAYS(5, true, false);
                 else FTL_LAUNCH_RAYS(FTL_HMAX, true, false);
-            } else if (h->P.hmax <= 5) FTL_LAUNCH_RAYS(5, false, false);
-            else if (h->P.hmax <= 8) FTL_LAUNCH_RAYS(8, false, false);
-            else if (h->P.hmax <= 10) FTL_LAUNCH_RAYS(10, false, false);   // the shipped training configs
-            else FTL_LAUNCH_RAYS(FTL_HMAX, false, false);
+            } else if (h->P.hmax <= 5) FTL_LAUNCH_RAYS_1(5);
+            else if (h->P.hmax <= 8) FTL_LAUNCH_RAYS_1(8);
+            else if (h->P.hmax <= 10) FTL_LAUNCH_RAYS_1(10);   // the shipped training configs
+            else FTL_LAUNCH_RAYS_1(FTL_HMAX);
+#undef FTL_LAUNCH_RAYS_1
 #undef FTL_LAUNCH_RAYS
+#undef FTL_LAUNCH_RAYS_P
         }
         if (tev) (void)hipEventRecord(tev[2], s);
     };

@@ -56,7 +56,8 @@ struct FtlDevParams {
     int32_t n_envs, R, lasers_len, total_rays, hmax, lds_rays;
     int32_t pass_rays[2], pass_base[2];   // rays of the sensors scanned before / after the tracker, and where they start in ray_dir
     float pass_lmax[2];               // longest laser_length of the pass (float32)
-    int32_t _pad_pass[2];             // (keeps ray_dir below on a 32-byte boundary: static_assert behind the struct)
+    int32_t pass_single;              // the only pass that has rays (0 / 1), or -1 when both have: what the ONE_PASS ray kernels run
+    int32_t _pad_pass;                // (keeps ray_dir below on a 32-byte boundary: static_assert behind the struct)
     int32_t fr_rec_off, fr_rec_stride, fr_pend_off, fr_env_off, fr_defer, fr_lds;   // frame kernel: LDS offsets of the frame records / pending items / slot -> env table
                                       // (+ the item counter), "the later frames' position searches wait for the end of the step", total dynamic LDS
     int32_t corr_lds_cap;             // corridor points the ray kernel stages in LDS (a power of two <= cfg.corr_cap; a longer window is read in place)
@@ -422,15 +423,21 @@ __device__ __forceinline__ bool hit_segment(float cx, float cy, double ex, doubl
 // atan2 for the candidate-ray arc of phase 3 only: |error| <= 2e-5 rad (Abramowitz-Stegun 4.4.47 polynomial on [0,1] +
 // octant folding), two orders of magnitude inside the arc slack (>= 0.01 rad) that absorbs it.  Never used for a value
 // that reaches an output.
+// The quotient is lo * v_rcp_f32(hi) (two instructions; the correctly rounded division is eleven): v_rcp_f32 is good to 1 ulp and the
+// product adds half of one, so the quotient <= 1 is off by < 2e-7 and the angle (|d atan / da| <= 1) by < 2e-7 rad -- a hundredth of the
+// polynomial's own error.  v_rcp_f32 takes a denormal hi for zero: the quotient may then be inf or NaN, but a segment end that close to
+// the follower has dmin2 = 0, and phase 3 lists every ray of the sensor for dmin2 < 4 without looking at the arc.
+// (ftl_aux_kernel and ftl_gz_kernel select their candidate rays with the same function, the same slack and the same near-origin rule.)
 __device__ __forceinline__ float arc_atan2(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
-    const float hi = fmaxf(ax, ay), lo = fminf(ax, ay);
-    const float a = hi > 0.0f ? __fdividef(lo, hi) : 0.0f;
+    const bool steep = ay > ax;                         // (selects, not fminf / fmaxf: those quiet NaNs first, an instruction per operand)
+    const float hi = steep ? ay : ax, lo = steep ? ax : ay;
+    const float a = hi > 0.0f ? lo * __builtin_amdgcn_rcpf(hi) : 0.0f;
     const float t = a * a;
     // (explicit fma: the translation unit is compiled with -ffp-contract=off for the code that follows the reference operation by
     //  operation; this value only selects candidate rays, see above)
     float r = a * __builtin_fmaf(t, __builtin_fmaf(t, __builtin_fmaf(t, __builtin_fmaf(t, 0.0208351f, -0.0851330f), 0.1801410f), -0.3302995f), 0.9998660f);
-    r = ay > ax ? 1.5707963267948966f - r : r;
+    r = steep ? 1.5707963267948966f - r : r;
     r = x < 0.0f ? 3.141592653589793f - r : r;
     return y < 0.0f ? -r : r;
 }
@@ -454,7 +461,12 @@ __shared__ unsigned long long s_rcyc[16];
 
 // SPLIT = the launch covers one of the interleaved halves of the slot groups (two-stream mode) instead of all envs
 // CAPPED = the LDS copy of the corridor ring is smaller than the ring itself: a window that does not fit is read in place (below)
-template <int HM, bool EXPL = false, bool SPLIT = false, bool CAPPED = false>
+// ONE_PASS = all ray sensors sit on one side of the tracker (P.pass_single says which; every shipped config): the pass body runs once,
+// straight-line.  In the two-trip loop of the other form the back edge keeps everything the prologue computed -- LDS array bases,
+// pointers, per-env scalars, the snapshot windows -- alive to the end of phase 4, and at 80 VGPRs the compiler holds them in the lanes
+// of a VGPR: 48 v_writelane in the prologue and 73 v_readlane in the pass of <5>, executed by every env-step (a tenth of its VALU issue)
+// although the second trip only finds pass_rays == 0.  `which` stays a run-time, wave-uniform value: what pays is the missing back edge.
+template <int HM, bool EXPL = false, bool SPLIT = false, bool CAPPED = false, bool ONE_PASS = false>
 __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const FtlDevParams* __restrict__ Pp, const FtlCall C) {
     extern __shared__ __align__(16) unsigned char lds[];
     using namespace ftl;
@@ -528,8 +540,10 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
     const unsigned all_snaps = (1u << nsnap) - 1u;                  // bit a = age a (nsnap <= hmax <= FTL_HMAX = 12)
     const int4* stp = reinterpret_cast<const int4*>(P.scen.static_rects) + (size_t)scen * c.n_static;
 
-#pragma nounroll
-    for (int which = 0; which < 2; which++) {
+    // One trip = one pass: the scan of the ray sensors listed before (0) / after (1) the tracker.  ONE_PASS: the condition at the bottom
+    // is a compile-time false, so there is no loop -- one trip for the pass that has rays (`continue` leaves it).
+    int which = ONE_PASS ? P.pass_single : 0;
+    do {
         // The lane index is made opaque once per pass (it shadows the kernel's `lane` from here on): left visible, every per-lane address of
         // the pass -- LDS slots, the lane's rects -- is formed once before this loop and kept alive across it, and at the 80 registers that
         // six wavefronts per SIMD allow the compiler paid for that with a register pair in scratch (512 B of scratch writes per env-step in
@@ -610,12 +624,17 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
             int at = (cls == SEG_STATIC ? 0 : 4 * cap_rs) + atomicAdd(&s_ecnt[cls], __popc(em));
             while (em) { const int e = __ffs(em) - 1; em &= em - 1; s_edge[at++] = (unsigned short)((slot << 2) | e); }
         };
+        // both ends beyond one side of the reach box.  Plain comparisons: fminf / fmaxf first quiet a NaN in each operand (a v_max_f32 of
+        // the value with itself), and these are finite coordinates from LDS
+        auto outside_box = [&](float ax, float ay, float bx, float by) {
+            return (ax < bx0 && bx < bx0) || (ax > bx1 && bx > bx1) || (ay < by0 && by < by0) || (ay > by1 && by > by1);
+        };
         auto push_corr = [&](int p, int side, float ax, float ay, float bx, float by, unsigned sm) {
-            if (fmaxf(ax, bx) < bx0 || fminf(ax, bx) > bx1 || fmaxf(ay, by) < by0 || fminf(ay, by) > by1) return;
+            if (outside_box(ax, ay, bx, by)) return;
             s_cref[atomicAdd(&s_cnt[SEG_CORRIDOR], 1)] = (unsigned)(p & cmask) | ((unsigned)side << 15) | (sm << 16);
         };
         auto push_green = [&](float ax, float ay, float bx, float by, unsigned sm) {
-            if (fmaxf(ax, bx) < bx0 || fminf(ax, bx) > bx1 || fmaxf(ay, by) < by0 || fminf(ay, by) > by1) return;
+            if (outside_box(ax, ay, bx, by)) return;
             int at = atomicAdd(&s_cnt[SEG_GREEN], 1);
             s_green[at] = make_float4(ax, ay, bx, by); s_gmask[at] = sm;
         };
@@ -766,10 +785,14 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
                     a0 = angA; wd = diff;
                     if (diff > 3.141592653589793f) { a0 = angB; wd = 6.283185307179586f - diff; }
                     a0 -= fdir_rad;
-                    // closest approach of the segment to the follower (culling only: 2 px of slack in the records' reach)
+                    // closest approach of the segment to the follower (culling only: 2 px of slack in the records' reach).  tt is
+                    // -dot * v_rcp_f32(l2): 1.5 ulp, < 2e-7 of a value in [0, 1], which moves the point (nx, ny) along the segment by
+                    // < 2e-7 of its length (< 3000 px: 6e-4 px) and the distance by no more -- against 2 px of slack in reach2 and a
+                    // "next to the origin" radius (dmin2 < 4) on either side of which the candidate lists are complete.  (An l2 too
+                    // small for v_rcp_f32 is a segment shorter than 1e-19 px: inf or NaN clamps to an end point, the same point.)
                     const float ex_ = bx - ax, ey_ = by - ay;
                     const float l2 = __builtin_fmaf(ex_, ex_, ey_ * ey_);
-                    const float tt = l2 > 0.0f ? fminf(fmaxf(__fdividef(-__builtin_fmaf(ax, ex_, ay * ey_), l2), 0.0f), 1.0f) : 0.0f;
+                    const float tt = l2 > 0.0f ? fminf(fmaxf(-__builtin_fmaf(ax, ex_, ay * ey_) * __builtin_amdgcn_rcpf(l2), 0.0f), 1.0f) : 0.0f;
                     const float nx = __builtin_fmaf(tt, ex_, ax), ny = __builtin_fmaf(tt, ey_, ay);
                     dmin2 = __builtin_fmaf(nx, nx, ny * ny);
                 }
@@ -933,7 +956,7 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
             }
         }
         FTL_RTIC(6);
-    }
+    } while (!ONE_PASS && ++which < 2);
 #ifdef FTL_PROFILE_RAYS
     __syncthreads();
     if (lane < 16) atomicAdd(&g_rcyc[lane], s_rcyc[lane]);
