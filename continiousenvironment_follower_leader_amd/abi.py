@@ -11,6 +11,7 @@ FTL_MAX_AUX = 8
 AUX_LIDAR, AUX_TRACK_VECTOR, AUX_TRACK_RADAR = 1, 2, 3
 FTL_MAX_REGIME = 16
 FTL_OBS_NUM = 10
+FTL_MAX_CORR_CAP = 512
 
 FTL_OK = 0
 FTL_E_INVALID, FTL_E_UNSUPPORTED, FTL_E_DEVICE, FTL_E_STATE = -1, -2, -3, -4

@@ -465,6 +465,20 @@ def make_config(game_width=1500, game_height=1000, framerate=500, frames_per_ste
     def pow2(v):
         return 1 << max(3, (int(v) - 1).bit_length())
 
+    # ftl_create takes rings of FTL_MAX_CORR_CAP points at most.  A capacity that a rule below would put beyond it is clamped to that
+    # limit -- make_config never returns a config that ftl_create refuses for a capacity it chose itself; an explicit corr_cap= is passed
+    # on as it is, and ftl_create names the field, its value and the limit when it refuses.  What the clamp leaves: at one frame per step
+    # the rule for a leader at full speed asks for 2.5 x 250 points on the shipped tracker and gets 512, 2.05x ("Ring capacity
+    # at the frame-count edges", has the measured count); a capacity without any head-room left is warned about.
+    def ring(want, points, what):
+        cap = pow2(want)
+        if cap > abi.FTL_MAX_CORR_CAP:
+            cap = abi.FTL_MAX_CORR_CAP
+            if points > cap:
+                warn("corr_cap: {} can hold about {} points, the tracker rings end at {} (FTL_MAX_CORR_CAP): an episode that gets there "
+                     "raises FTL_ERR_CORR_OVERFLOW".format(what, int(points), cap))
+        return cap
+
     if corr_cap:
         c.corr_cap = pow2(corr_cap)       # the tracker rings are indexed with a mask
     elif c.has_tracker:
@@ -476,11 +490,12 @@ def make_config(game_width=1500, game_height=1000, framerate=500, frames_per_ste
         # The ray kernel keeps a float32 copy of the ring in LDS, where 1.5 KB decide about a wavefront per SIMD: hence
         # no flat 4x for everybody.
         if c.n_speed_regime >= 0 or c.n_acc_regime >= 0:
-            c.corr_cap = pow2(max(32, int(4 * c.corridor_length / max(c.tracker_saving_period * 5 * l_max, 1e-9))))
+            gap = max(c.tracker_saving_period * 5 * l_max, 1e-9)
+            c.corr_cap = ring(max(32, int(4 * c.corridor_length / gap)), c.corridor_length / gap, "a corridor of seeded spacing")
         else:
             fps_min = c.rand_fps_lo if c.rand_fps_hi > 0 else c.frames_per_step
-            gap = c.tracker_saving_period * min(5.0, fps_min / 2.0) * l_max
-            c.corr_cap = pow2(max(32, int(2.5 * c.corridor_length / max(gap, 1e-9))))
+            gap = max(c.tracker_saving_period * min(5.0, fps_min / 2.0) * l_max, 1e-9)
+            c.corr_cap = ring(max(32, int(2.5 * c.corridor_length / gap)), c.corridor_length / gap, "the corridor of a leader at full speed")
     else:
         c.corr_cap = 16
     c.route_cap = int(route_cap)
@@ -488,7 +503,9 @@ def make_config(game_width=1500, game_height=1000, framerate=500, frames_per_ste
     steps_max = c.max_steps // max(1, min(c.frames_per_step, c.rand_fps_lo or c.frames_per_step)) + 2
     c.hist1_cap = ((steps_max // max(c.tracker_saving_period, 1) + 8 + 7) // 8) * 8 if c.has_tracker == 1 else 8
     if c.has_tracker == 1 and not corr_cap:
-        c.corr_cap = pow2(c.hist1_cap)      # the corridor gets one pair per saved point and is never trimmed either
+        # the corridor gets one pair per saved point and is never trimmed either: beyond the limit (the default max_steps at 1 or 2 frames
+        # per step) an episode that runs to its end overflows the ring, and is told so
+        c.corr_cap = ring(c.hist1_cap, c.hist1_cap - 8, "the untrimmed corridor of the v1 tracker over max_steps")
 
     cfg = GameConfig(kwargs=all_kwargs, c=c, lasers=lasers, tracker_name=tracker_name, sensor_order=order, follower_info=follower_info, aux=aux,
                      discrete_action_space=bool(discrete_action_space),

@@ -79,7 +79,11 @@ int validate(const ftl_config& c, std::string& why) {
     REQ(c.n_bears >= 0 && c.n_bears <= FTL_MAX_BEARS, "n_bears out of range (0..%d)", FTL_MAX_BEARS);
     REQ(c.n_lasers >= 0 && c.n_lasers <= FTL_MAX_LASERS, "n_lasers out of range");
     REQ(c.n_lasers == 0 || c.has_tracker, "ray sensors need the tracker (classes.py:280 would raise NameError)");
-    REQ(c.traj_cap >= 8 && c.corr_cap >= 8 && c.corr_cap <= 512 && c.route_cap >= 2 && c.init_traj_cap >= 1, "bad capacities");
+    REQ(c.traj_cap >= 8, "traj_cap %d is below 8", c.traj_cap);
+    REQ(c.corr_cap >= 8, "corr_cap %d is below 8", c.corr_cap);
+    REQ(c.corr_cap <= FTL_MAX_CORR_CAP, "corr_cap %d is above the limit of %d points (FTL_MAX_CORR_CAP)", c.corr_cap, FTL_MAX_CORR_CAP);
+    REQ(c.route_cap >= 2, "route_cap %d is below 2", c.route_cap);
+    REQ(c.init_traj_cap >= 1, "init_traj_cap %d is below 1", c.init_traj_cap);
     REQ((c.corr_cap & (c.corr_cap - 1)) == 0, "corr_cap must be a power of two (the tracker rings are indexed with a mask)");
     REQ(c.init_traj_cap <= c.traj_cap, "init_traj_cap > traj_cap");
     REQ(c.traj_cap % FTL_TRAJ_BLOCK == 0, "traj_cap must be a multiple of FTL_TRAJ_BLOCK");
@@ -324,6 +328,7 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
         P.fr_defer = (cfg->rand_fps_hi == 0 && f_max >= 2 && f_max <= 16 && cfg->traj_cap <= 65535 && !(dv && dv[0] == '0')) ? 1 : 0;
         if (cfg->traj_cap > 65535 || f_max > 4095) { delete h; return fail(FTL_E_INVALID, "traj_cap above 65535 or more than 4095 frames per step"); }
         if (set_lanes(h)) { delete h; return fail(FTL_E_INVALID, "the frame kernel needs more than 64 KiB of LDS per wavefront (static rects x frames per step)"); }
+        if (getenv("FTL_DEBUG_PRINT_LDS")) fprintf(stderr, "ftl: frame kernel LDS %d B per wavefront, %d lanes per env, %d frames at most, searches %s\n", P.fr_lds, h->G, f_max, P.fr_defer ? "deferred" : "in frame");
     }
     auto debug_pad = [](const char* name) { const char* v = getenv(name); const int p = v ? atoi(v) : 0; return p < 0 ? 0 : (p > 48 * 1024 ? 48 * 1024 : p); };
     P.lds_rays += debug_pad("FTL_DEBUG_LDS_PAD_RAYS");      // diagnostic: occupancy of the ray kernel without touching the code

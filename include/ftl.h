@@ -37,6 +37,7 @@ extern "C" {
 #define FTL_MAX_REGIME 16 /* entries of leader_speed_regime / leader_acceleration_regime */
 #define FTL_OBS_NUM 10    /* numerical_features, ENV:1793-1802 */
 #define FTL_TRAJ_BLOCK 32 /* trajectory points per bounding-box block (state field "traj_bb"; traj_cap is a multiple) */
+#define FTL_MAX_CORR_CAP 512 /* largest ftl_config.corr_cap that ftl_create accepts */
 
 /* error codes */
 #define FTL_OK 0

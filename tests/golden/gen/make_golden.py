@@ -220,6 +220,21 @@ CONFIGS = {
 }
 
 
+def _with(base, **kw):
+    return dict(kwargs=dict(CONFIGS[base]["kwargs"], **kw), post=CONFIGS[base]["post"])
+
+
+# ---- the edges of the frame count: the frame kernel defers the searches of frames 1.. exactly for fixed counts 2..16 (ftl_create); 1, 17
+# and 40 frames run every frame's searches at once, 2 and 16 are the ends of the deferring schedule, [1, 2] is one frame per step drawn
+# from the per-env stream.  Each is the named config plus the one key.
+CONFIGS.update({
+    "B_fps1": _with("B", frames_per_step=1), "B_fps2": _with("B", frames_per_step=2), "B_fps16": _with("B", frames_per_step=16),
+    "B_fps17": _with("B", frames_per_step=17), "B_fps40": _with("B", frames_per_step=40), "B3_fps17": _with("B3", frames_per_step=17),
+    "L_fps1": _with("L", frames_per_step=1), "L_fps40": _with("L", frames_per_step=40),
+    "B_rf12": _with("B", random_frames_per_step=[1, 2]),
+})
+
+
 def import_reference():
     import pygame  # stand-in
     with contextlib.redirect_stdout(io.StringIO()):
@@ -650,6 +665,15 @@ EPISODES = [
     ("Bmep_s11_noisy", "B_mep", 11, "chase_noisy", 200),
     ("Btraj_s3_chase", "B_traj", 3, "chase", 400),
     ("Btraj_s6_random", "B_traj", 6, "random", 150),
+    ("Bfps1_s3_chase", "B_fps1", 3, "chase", 150),
+    ("Bfps2_s3_chase", "B_fps2", 3, "chase", 120),
+    ("Bfps16_s3_chase", "B_fps16", 3, "chase", 60),
+    ("Bfps17_s3_chase", "B_fps17", 3, "chase", 60),
+    ("Bfps40_s3_chase", "B_fps40", 3, "chase", 60),
+    ("B3fps17_s8_random", "B3_fps17", 8, "random", 60),
+    ("Lfps1_s2_chase", "L_fps1", 2, "chase", 100),
+    ("Lfps40_s2_chase", "L_fps40", 2, "chase", 40),
+    ("Brf12_s5_chase", "B_rf12", 5, "chase", 80),
 ]
 
 

@@ -187,3 +187,137 @@ def test_ray_sensor_without_edges_warns(cls, extra):
         config(True, add_bear=False)
         config(False, corridor=True)
         config("dynamic", green=True, add_bear=False)
+
+
+# ---- frame counts: make_config -> ftl_create (pure host work, as tests/test_abi.py shows) ----------------------------------------------------
+FRAME_COUNTS = (1, 2, 3, 16, 17, 40, 300, 4095)
+RANDOM_FRAME_COUNTS = ([1, 2], [1, 3], [2, 4], [30, 70])
+FRAME_COUNT_EPISODES = ("A_s0_chase", "B_s1_chase", "D_s2_chase", "E_s3_chase", "L_s2_chase", "T_s3_chase")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from continiousenvironment_follower_leader_amd import _lib
+    _lib.build()
+    return _lib.load()
+
+
+def _create(lib, cfg, n=64):
+    """ftl_create on device 0 (no device call needs to succeed for it): (return code, message, handle or None)."""
+    import ctypes as C
+    h = C.c_void_p()
+    rc = lib.ftl_create(C.byref(cfg.c), n, 0, C.byref(h))
+    return rc, ("" if rc == 0 else lib.ftl_last_error().decode()), (h if rc == 0 else None)
+
+
+def _quiet_config(meta, **over):
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")         # both frame settings given (ENV:399-401); the clamp's own warning has its test below
+        return config_for(meta, **over)
+
+
+@pytest.mark.parametrize("ep", FRAME_COUNT_EPISODES)
+def test_every_frame_count_round_trips_through_create(lib, ep):
+    """A, B, D, E (regimes), L (lidar, detectors) and T (the v1 tracker) at the edges of the frame count: whatever make_config sizes,
+    ftl_create accepts, and the handle keeps the frame settings and capacities it was given."""
+    import ctypes as C
+    from continiousenvironment_follower_leader_amd import abi
+    _, meta = load_episode(ep)
+    overs = [dict(frames_per_step=f) for f in FRAME_COUNTS] + [dict(random_frames_per_step=r) for r in RANDOM_FRAME_COUNTS]
+    for over in overs:
+        cfg = _quiet_config(meta, **over)
+        c = cfg.c
+        assert 8 <= c.corr_cap <= abi.FTL_MAX_CORR_CAP and c.corr_cap & (c.corr_cap - 1) == 0, (ep, over, c.corr_cap)
+        rc, why, h = _create(lib, cfg)
+        assert rc == 0, (ep, over, why)
+        got = abi.Config()
+        assert lib.ftl_get_config(h, C.byref(got)) == 0
+        assert (got.frames_per_step, got.rand_fps_lo, got.rand_fps_hi) == (c.frames_per_step, c.rand_fps_lo, c.rand_fps_hi)
+        assert (got.corr_cap, got.traj_cap, got.hist1_cap) == (c.corr_cap, c.traj_cap, c.hist1_cap)
+        assert lib.ftl_state_bytes(h) > 0
+        lib.ftl_destroy(h)
+    rc, why, _ = _create(lib, _quiet_config(meta, frames_per_step=4096))
+    assert rc == abi.FTL_E_INVALID and "frames per step" in why, (ep, why)
+    rc, why, _ = _create(lib, _quiet_config(meta, random_frames_per_step=[4000, 4097]))      # draws 4000 .. 4096
+    assert rc == abi.FTL_E_INVALID and "frames per step" in why, (ep, why)
+
+
+def test_corridor_ring_is_clamped_to_the_library_limit(lib):
+    """The sizing rule reaches 1024 points as soon as a point is saved every frame or two; make_config stops at FTL_MAX_CORR_CAP, which
+    still leaves twice the 250 points of config B's corridor at one frame per step (DESIGN.md has the measured count).  Where the clamp
+    leaves no head-room at all -- the v1 tracker's corridor, never trimmed, over the default max_steps -- make_config says so."""
+    import warnings
+    from continiousenvironment_follower_leader_amd import abi
+    _, mb = load_episode("B_s1_chase")
+    _, mt = load_episode("T_s3_chase")
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        for over in (dict(frames_per_step=1), dict(frames_per_step=2)):
+            b = config_for(mb, **over).c
+            points = b.corridor_length / (b.tracker_saving_period / 2 * b.frames_per_step * b.leader.max_speed)
+            assert b.corr_cap == abi.FTL_MAX_CORR_CAP == 512 and b.corr_cap >= 2 * points >= 250, (over, points)
+        assert config_for(mb, frames_per_step=3).c.corr_cap == 256           # the rule itself is untouched below the limit
+        assert config_for(mt, frames_per_step=3).c.corr_cap == 512 and config_for(mt).c.corr_cap == 256
+    for over in (dict(frames_per_step=1), dict(frames_per_step=2)):
+        with pytest.warns(UserWarning, match="FTL_ERR_CORR_OVERFLOW"):
+            t = config_for(mt, **over).c
+        assert t.corr_cap == 512 < t.hist1_cap - 8
+        rc, why, h = _create(lib, _quiet_config(mt, **over))
+        assert rc == 0, why
+        lib.ftl_destroy(h)
+
+
+def test_create_names_the_capacity_it_refuses(lib):
+    """validate() names the field, its value and the limit; an explicit corr_cap= is handed on unclamped and gets that message."""
+    from continiousenvironment_follower_leader_amd import abi
+    _, mb = load_episode("B_s1_chase")
+    for asked, got in ((513, 1024), (1024, 1024), (2000, 2048)):
+        cfg = config_for(mb, corr_cap=asked)
+        assert cfg.c.corr_cap == got
+        rc, why, _ = _create(lib, cfg)
+        assert rc == abi.FTL_E_INVALID and "corr_cap %d" % got in why and "limit of 512" in why, why
+    rc, why, h = _create(lib, config_for(mb, corr_cap=512))
+    assert rc == 0, why
+    lib.ftl_destroy(h)
+    for field, value, text in (("corr_cap", 4, "corr_cap 4 is below 8"), ("traj_cap", 0, "traj_cap 0 is below 8"),
+                               ("route_cap", 1, "route_cap 1 is below 2"), ("init_traj_cap", 0, "init_traj_cap 0 is below 1")):
+        cfg = config_for(mb)
+        setattr(cfg.c, field, value)
+        rc, why, _ = _create(lib, cfg)
+        assert rc == abi.FTL_E_INVALID and text in why, (field, why)
+
+
+def test_searches_are_deferred_exactly_for_fixed_counts_2_to_16(lib, monkeypatch, capfd):
+    """ftl_create's choice between the two schedules of the frame kernel, as its FTL_DEBUG_PRINT_LDS report states it: the searches of
+    frames 1.. wait for the end of the step exactly when the frame count is fixed and 2 <= frames <= 16; FTL_DEFER=0 turns that off."""
+    import re
+    _, mb = load_episode("B_s1_chase")
+    monkeypatch.setenv("FTL_DEBUG_PRINT_LDS", "1")
+    monkeypatch.delenv("FTL_DEFER", raising=False)
+    monkeypatch.delenv("FTL_DEBUG_G8", raising=False)
+
+    def report(**over):
+        capfd.readouterr()
+        rc, why, h = _create(lib, _quiet_config(mb, **over))
+        assert rc == 0, why
+        lib.ftl_destroy(h)
+        m = re.search(r"ftl: frame kernel LDS (\d+) B per wavefront, (\d+) lanes per env, (\d+) frames at most, searches (deferred|in frame)",
+                      capfd.readouterr().err)
+        assert m, over
+        return int(m.group(1)), int(m.group(2)), int(m.group(3)), m.group(4) == "deferred"
+
+    for f in (1, 2, 3, 5, 10, 15, 16, 17, 18, 40, 300, 4095):
+        lds, lanes, f_max, deferred = report(frames_per_step=f)
+        assert (lanes, f_max) == (8, f) and deferred == (2 <= f <= 16), f
+        # frame records (one byte per env and frame, rows of 16) + the pending items: one per env, or one per env and deferred frame
+        base = report(frames_per_step=1)[0]
+        assert lds - base == 8 * ((f + 15) // 16 * 16 - 16) + 8 * 16 * ((f - 2) if deferred else 0), f
+    for r in RANDOM_FRAME_COUNTS + ([2, 3], [5, 17]):
+        _, _, f_max, deferred = report(random_frames_per_step=r)
+        assert f_max == r[1] - 1 and not deferred, r
+    monkeypatch.setenv("FTL_DEFER", "0")
+    for f in (2, 10, 16):
+        assert not report(frames_per_step=f)[3], f
+    monkeypatch.setenv("FTL_DEFER", "1")
+    assert report(frames_per_step=10)[3] and not report(frames_per_step=17)[3]

@@ -201,7 +201,8 @@ def _ending(z):
     return int(d[0])
 
 
-@pytest.mark.parametrize("ep", ["B_s5_random", "L_s7_random", "B_s1_chase", "Bshort_s4_chase", "Bes_s2_random", "F_s1_chase", "Btraj_s6_random"])
+@pytest.mark.parametrize("ep", ["B_s5_random", "L_s7_random", "B_s1_chase", "Bshort_s4_chase", "Bes_s2_random", "F_s1_chase", "Btraj_s6_random",
+                                "B3fps17_s8_random", "Lfps40_s2_chase"])       # (the last two: 17 and 40 frames per step, every frame resolving its own searches)
 @pytest.mark.parametrize("mode", ["same_step", "next_step"])
 def test_reference_episode_terminal_observation(ep, mode):
     """A golden episode replayed to its end in a pool where another entry follows it: the terminal observation (final buffers under
