@@ -22,7 +22,49 @@ thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 struct Field { const char* name; size_t offset, per_env; int dtype; size_t stride; };     // stride: bytes from one env's row to the next
-constexpr int FTL_N_FIELDS = 15;
+
+// The state fields, one row each: name (= the pointer member of FtlDevParams), dtype (0 int32, 1 float32, 2 float64), element size, "part
+// of the per-env record".  The order is that of ftl_state_field, of the snapshot rows and of ftl_env_layout_id: new fields go to the end.
+#define FTL_FIELDS(X) \
+    X(rb_pos, 1, 4, true) X(rb_dbl, 2, 8, true) X(rb_int, 0, 4, true) X(env_int, 0, 4, true) X(env_dbl, 2, 8, true) \
+    X(traj, 1, 4, false) X(hist, 2, 8, false) X(corr, 2, 8, false) X(snap_rects, 0, 4, true) X(snap_win, 0, 4, true) \
+    X(traj_bb, 1, 4, false) X(ep_stats, 2, 8, false) X(hist1, 1, 4, false) X(fol_cs, 2, 8, true) X(corr32, 1, 4, false)
+#define X(n, dtype, esz, rec) F_##n,
+enum { FTL_FIELDS(X) FTL_N_FIELDS };
+#undef X
+struct FieldSpec { const char* name; int dtype; size_t esz; bool rec; size_t ptr; };      // ptr: where FtlDevParams keeps the field's pointer
+#define X(n, dtype, esz, rec) {#n, dtype, esz, rec, offsetof(FtlDevParams, n)},
+constexpr FieldSpec kFields[FTL_N_FIELDS] = {FTL_FIELDS(X)};
+#undef X
+// the per-env record, the ray kernel's inputs first
+constexpr int kRecOrder[] = {F_env_int, F_fol_cs, F_rb_pos, F_rb_dbl, F_snap_win, F_snap_rects, F_env_dbl, F_rb_int};
+
+// The environment switches, read once by ftl_create.  -1 = not given: a given 0 / 1 wins over the library's rule and over ftl_tune.
+struct Switches {
+    int split, no_regroup, g8, one_pass, defer;                       // FTL_SPLIT, FTL_NO_REGROUP, FTL_DEBUG_G8, FTL_RAYS_ONE_PASS, FTL_DEFER
+    int regroup_every, corr_lds_cap, lds_pad, lds_pad_rays;            // FTL_REGROUP_EVERY, FTL_DEBUG_CORR_LDS_CAP, FTL_DEBUG_LDS_PAD[_RAYS] (0: not given)
+    bool print_lds;                                                   // FTL_DEBUG_PRINT_LDS
+};
+
+Switches read_switches() {
+    auto tri = [](const char* name, int other) { const char* v = getenv(name); return !v ? -1 : v[0] == '1' ? 1 : v[0] == '0' ? 0 : other; };
+    auto num = [](const char* name, int hi) { const char* v = getenv(name); const int p = v ? atoi(v) : 0; return p < 0 ? 0 : (p > hi ? hi : p); };
+    return Switches{tri("FTL_SPLIT", 0), tri("FTL_NO_REGROUP", 0), tri("FTL_DEBUG_G8", 0), tri("FTL_RAYS_ONE_PASS", 1), tri("FTL_DEFER", 1),
+                    num("FTL_REGROUP_EVERY", INT32_MAX), num("FTL_DEBUG_CORR_LDS_CAP", INT32_MAX), num("FTL_DEBUG_LDS_PAD", 48 * 1024),
+                    num("FTL_DEBUG_LDS_PAD_RAYS", 48 * 1024), getenv("FTL_DEBUG_PRINT_LDS") != nullptr};
+}
+
+// What ftl_create and ftl_tune decide about the frame kernel and the cost sort: plan_schedule()
+struct Schedule {
+    int G, epw, rg_slots;    // lanes per env (4 or 8), envs per wavefront, frame-kernel wavefronts one round holds on this device
+    int32_t fr_rec_off, fr_rec_stride, fr_pend_off, fr_env_off, fr_defer, fr_lds;   // the kernel's LDS layout (FtlDevParams has the meanings)
+    bool regroup, fits;      // envs are regrouped by expected cost after every rg_every-th launch; fr_lds is within the 64 KiB of a workgroup
+};
+
+// The template arguments of the kernels a handle launches, as values: frame_inst(), rays_inst()
+struct FrameInst { int G; bool reg, xr; };
+struct RaysInst { int hm; bool expl, split, capped, one_pass; };
+typedef void (*FtlKernel)(const FtlDevParams*, const FtlCall);
 
 }  // namespace
 
@@ -42,21 +84,21 @@ struct ftl_handle {
     std::vector<hipEvent_t> tev;   // 5 per timed step: before frames | after frames | after rays | after aux | after regroup
     size_t tev_used;
     bool bound, have_scen;
-    bool regroup;            // envs are regrouped by expected cost after every launch (off: FTL_NO_REGROUP=1, or too many envs)
+    Switches sw;             // the environment switches as ftl_create found them
+    Schedule sched;          // the committed plan_schedule() of (co_envs, cus): P.fr_* are its copy for the kernel
+    int co_envs, cus;        // envs stepped on the device at the same time (ftl_tune; default: this handle's), CUs of the device
+    bool one_pass;           // all ray sensors sit on one side of the tracker, and FTL_RAYS_ONE_PASS=0 is not set
+    // what launch() launches (apply_plan): the frame kernel without / with XR, the ray kernel of one-stream / two-stream launches
+    // (null: no ray sensors), "the config has a compas / lidar / detector sensor", "the config has the v1 tracker"
+    FtlKernel k_frames[2], k_rays[2]; RaysInst rays[2];
+    bool has_aux, has_trk1;
     void* rg_mem;            // perm | bh | rank | keys | two key-total buffers (library-owned)
     int* rg_tot;             // [2][FTL_NKEYS]
     unsigned rg_parity, rg_launches, rg_every;
-    bool rg_env, rg_every_env, split_env;   // the environment switch was given: it wins over ftl_tune
-    int G;                   // lanes per env in the frame kernel (set_lanes)
-    int co_envs, cus;        // envs stepped on the device at the same time (ftl_tune; default: this handle's), CUs of the device
-    bool g_env;              // FTL_DEBUG_G8 was given
-    bool one_pass;           // the ray kernel's one-pass form is launched (all ray sensors on one side of the tracker; FTL_RAYS_ONE_PASS=0: never)
-    int rg_slots, rg_epw;    // frame-kernel wavefronts one round holds on this device / envs per wavefront (the cost sort's auto rule)
     // optionally the slot groups are stepped as two interleaved halves on two streams (the caller's stream waits for the side
     // stream): the ray kernel of one half fills the tail of the other half's frame kernel
     hipStream_t side; hipEvent_t ev_fork, ev_join; bool split;
     int win_base, win_count, win_stride; // pool entries the auto-reset draws from (ftl_set_reset_window)
-    size_t lds_pad;          // FTL_DEBUG_LDS_PAD (diagnostic: lowers the frame kernel's occupancy without touching the code), read once at create
     float* last_lasers;      // ftl_outputs.lasers of the last ftl_reset / ftl_step* call (ftl_render's hit points)
     FtlAttached<ftl_episode_queue> queue;         // ftl_set_episode_queue
     FtlAttached<ftl_scenario_sampler> sampler;    // ftl_set_scenario_sampler
@@ -120,6 +162,111 @@ int validate(const ftl_config& c, std::string& why) {
     return FTL_OK;
 }
 
+int frames_max(const ftl_config& c) { return c.rand_fps_hi > 0 ? c.rand_fps_hi - 1 : c.frames_per_step; }      // frames of the longest step
+
+// The schedule of a handle of n_envs envs that shares a device of `cus` CUs with co_envs envs in all.  Pure: ftl_create and ftl_tune
+// commit what it returns (apply_plan).
+// Lanes per env (G): configs with more than 2 dynamic obstacles need 8.  The others take 8 as well -- 8 envs per wavefront, five lanes of
+// a group idle -- when the batch is small enough for every such wavefront to have a SIMD of its own: the launch then takes as long as its
+// slowest wavefront, and a wavefront with half the envs meets half the rare paths (resets, searches, walks): config B at 8,192 envs +3 %,
+// config D +4 %, nothing from 16,384 envs on.  FTL_DEBUG_G8=0/1 overrides.
+// Cost sort (regroup): it pays when the frame kernel runs in more than one round of wavefronts (the long ones start first, the short ones
+// fill in behind them: +10 % on config B at 65,536 envs).  When every wavefront is resident from the start the launch takes as long as its
+// slowest wavefront, and a wavefront that holds ALL the expensive envs is slower than any wavefront of an unsorted batch: config E at
+// 32,768 envs -9 %, config D at 4,096 envs -16 % with the sort.  So it is on only beyond one round -- or with random frame counts, whose
+// keys make the wavefronts uniform in length.  FTL_NO_REGROUP=0/1 overrides.  (The scatter pass reads one histogram row per block of
+// 1024 envs: fine up to a few hundred blocks.)
+Schedule plan_schedule(const ftl_config& cfg, int R, int n_envs, int co_envs, int cus, const Switches& sw) {
+    Schedule s;
+    s.G = (R > 4 || (sw.g8 >= 0 ? sw.g8 == 1 : co_envs <= cus * 4 * 8)) ? 8 : 4;
+    s.epw = FTL_WAVE / s.G;
+    const int f_max = frames_max(cfg);
+    // The searches of frames 1.. wait for the end of the step when the step is short enough for their items to sit in LDS and the frame
+    // count is the same for every env; otherwise every frame's searches run right after it (one item per env at most).  FTL_DEFER=0: never.
+    s.fr_defer = (cfg.rand_fps_hi == 0 && f_max >= 2 && f_max <= 16 && cfg.traj_cap <= 65535 && sw.defer != 0) ? 1 : 0;
+    // LDS: near lists + their counters | frame records (one byte per env and frame) | pending position checks | slot -> env, item counter,
+    // box of the trajectory block being filled
+    size_t o = align_up((size_t)s.epw * cfg.n_static * 16 + (size_t)s.epw * 4 + 32, 16);
+    s.fr_rec_stride = (int)align_up((size_t)f_max, 16);
+    s.fr_rec_off = (int)o; o += (size_t)s.fr_rec_stride * s.epw;
+    s.fr_pend_off = (int)o; o += (size_t)s.epw * (s.fr_defer ? f_max - 1 : 1) * 16;
+    s.fr_env_off = (int)o; o += (size_t)s.epw * 4 + 16 + (size_t)s.epw * 16;
+    s.fr_lds = (int)o;
+    s.fits = o <= 64 * 1024;
+    s.rg_slots = cus * 4 * FTL_FRAMESG_WPE;
+    s.regroup = (sw.no_regroup >= 0 ? sw.no_regroup == 0 : ((co_envs + s.epw - 1) / s.epw > s.rg_slots || cfg.rand_fps_hi > 0))
+                && (n_envs + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK <= 512;
+    return s;
+}
+
+// Which instantiation of the frame kernel runs: G lanes per env, REG = the config has leader regimes or random frame counts, XR = the call
+// restarts finished envs on a later call or writes the masks (ftl_frames_group.hpp)
+FrameInst frame_inst(const ftl_config& c, int G, bool xr) { return FrameInst{G, c.n_speed_regime >= 0 || c.n_acc_regime >= 0 || c.rand_fps_hi > 0, xr}; }
+
+bool call_xr(const FtlCall& c) { return (c.flags & (FTL_STEP_NEXT_RESET | FTL_CALL_DEFER_RESET | FTL_CALL_FINISH)) != 0 || c.ended || c.restarted; }
+
+// Which instantiation of the ray kernel runs (DESIGN.md has the table).  expl: a sensor with explicit angles, padded sectors or a compas
+// is in the config; capped: the LDS copy of the corridor ring is smaller than the ring; two_streams: the launch covers one half of the slot
+// groups.  Only the one-stream kernels of the common sensors exist in every HM and without the loop over the passes.
+RaysInst rays_inst(int hmax, bool expl, bool capped, bool two_streams, bool one_pass) {
+    const int wide = hmax <= 5 ? 5 : FTL_HMAX;
+    if (two_streams) return (!expl && hmax > 5 && hmax <= 10) ? RaysInst{10, false, true, capped, false} : RaysInst{wide, true, true, capped, false};
+    if (expl) return RaysInst{wide, true, false, capped, false};
+    return RaysInst{hmax <= 5 ? 5 : hmax <= 8 ? 8 : hmax <= 10 ? 10 : FTL_HMAX, false, false, capped, one_pass};
+}
+
+// The instantiations: 2 x 2 x 2 of the frame kernel, and of the ray kernel the 3 + 2 + 4 x 2 (HM, EXPL, SPLIT, ONE_PASS) rows that
+// rays_inst can return, each with and without CAPPED
+template <bool XR> FtlKernel frame_kernel_x(int G, bool reg) {
+    if (G == 4) return reg ? ftl_frames_group_kernel<4, true, XR> : ftl_frames_group_kernel<4, false, XR>;
+    return reg ? ftl_frames_group_kernel<8, true, XR> : ftl_frames_group_kernel<8, false, XR>;
+}
+FtlKernel frame_kernel(const FrameInst& f) { return f.xr ? frame_kernel_x<true>(f.G, f.reg) : frame_kernel_x<false>(f.G, f.reg); }
+
+template <int HM, bool EXPL, bool SPLIT, bool ONE> FtlKernel rays_kernel_c(bool capped) {
+    return capped ? ftl_rays_kernel<HM, EXPL, SPLIT, true, ONE> : ftl_rays_kernel<HM, EXPL, SPLIT, false, ONE>;
+}
+template <int HM> FtlKernel rays_kernel_1(const RaysInst& r) { return r.one_pass ? rays_kernel_c<HM, false, false, true>(r.capped) : rays_kernel_c<HM, false, false, false>(r.capped); }
+FtlKernel rays_kernel(const RaysInst& r) {
+    if (r.split) return r.hm == 10 ? rays_kernel_c<10, false, true, false>(r.capped) : r.hm == 5 ? rays_kernel_c<5, true, true, false>(r.capped) : rays_kernel_c<FTL_HMAX, true, true, false>(r.capped);
+    if (r.expl) return r.hm == 5 ? rays_kernel_c<5, true, false, false>(r.capped) : rays_kernel_c<FTL_HMAX, true, false, false>(r.capped);
+    return r.hm == 5 ? rays_kernel_1<5>(r) : r.hm == 8 ? rays_kernel_1<8>(r) : r.hm == 10 ? rays_kernel_1<10>(r) : rays_kernel_1<FTL_HMAX>(r);
+}
+
+// Plans for co_envs co-scheduled envs.  A plan whose LDS layout fits is committed, with the kernels that go with it and what the config
+// says about the other launches; otherwise the handle stays exactly as it was.
+int apply_plan(ftl_handle* h, int co_envs) {
+    FtlDevParams& P = h->P;
+    const ftl_config& c = P.cfg;
+    const Schedule s = plan_schedule(c, P.R, P.n_envs, co_envs, h->cus, h->sw);
+    if (!s.fits) return fail(FTL_E_INVALID, "the frame kernel needs more than 64 KiB of LDS per wavefront (static rects x frames per step)");
+    h->sched = s; h->co_envs = co_envs; h->dirty = true;
+    P.fr_rec_off = s.fr_rec_off; P.fr_rec_stride = s.fr_rec_stride; P.fr_pend_off = s.fr_pend_off; P.fr_env_off = s.fr_env_off;
+    P.fr_defer = s.fr_defer; P.fr_lds = s.fr_lds;
+    bool expl = false, compas = false;
+    for (int k = 0; k < c.n_lasers; k++) { compas = compas || c.lasers[k].compas != 0; expl = expl || c.lasers[k].explicit_angles != 0 || c.lasers[k].pad_sectors != 0; }
+    for (int i = 0; i < 2; i++) {
+        h->k_frames[i] = frame_kernel(frame_inst(c, s.G, i == 1));
+        h->rays[i] = rays_inst(P.hmax, expl || compas, P.corr_lds_cap < c.corr_cap, i == 1, h->one_pass);
+        h->k_rays[i] = c.n_lasers > 0 ? rays_kernel(h->rays[i]) : nullptr;
+    }
+    h->has_aux = c.n_aux > 0 || compas; h->has_trk1 = c.has_tracker == 1;
+    return FTL_OK;
+}
+
+// The FTL_DEBUG_PRINT_LDS report: what ftl_create, and every ftl_tune that succeeded, left on the handle
+void report_plan(const ftl_handle* h) {
+    if (!h->sw.print_lds) return;
+    const FtlDevParams& P = h->P;
+    fprintf(stderr, "ftl: frame kernel LDS %d B per wavefront, %d lanes per env, %d frames at most, searches %s\n", P.fr_lds, h->sched.G, frames_max(P.cfg), P.fr_defer ? "deferred" : "in frame");
+    fprintf(stderr, "ftl: ray kernel LDS %d B per env\n", P.lds_rays);
+    char r[2][40] = {"no rays", "no rays"};
+    for (int i = 0; i < 2; i++)
+        if (h->k_rays[i]) snprintf(r[i], sizeof r[i], "rays<%d,%d,%d,%d,%d>", h->rays[i].hm, h->rays[i].expl, h->rays[i].split, h->rays[i].capped, h->rays[i].one_pass);
+    fprintf(stderr, "ftl: kernels frames<%d,%d>, %s on one stream, %s on two; regroup %s every %u, two streams %s\n", h->sched.G, frame_inst(P.cfg, h->sched.G, false).reg,
+            r[0], r[1], h->sched.regroup ? "on" : "off", h->rg_every, h->split ? "on" : "off");
+}
+
 }  // namespace
 
 extern "C" {
@@ -132,72 +279,27 @@ size_t ftl_sizeof_outputs(void) { return sizeof(ftl_outputs); }
 size_t ftl_sizeof_scen_params(void) { return sizeof(ftl_scen_params); }
 size_t ftl_sizeof_final_outputs(void) { return sizeof(ftl_final_outputs); }
 
-// Lanes per env of the frame kernel (4 or 8) and everything that follows from the envs per wavefront: the LDS layout of the kernel and the
-// slot count of the cost sort's rule.  Configs with more than 2 dynamic obstacles need 8 lanes.  The others take 8 as well -- 8 envs per
-// wavefront, five lanes of a group idle -- when the batch is small enough for every such wavefront to have a SIMD of its own: the launch
-// then takes as long as its slowest wavefront, and a wavefront with half the envs meets half the rare paths (resets, searches, walks):
-// config B at 8,192 envs +3 %, config D +4 %, nothing from 16,384 envs on.  FTL_DEBUG_G8=0/1 overrides.  0 on success.
-static int set_lanes(ftl_handle* h) {
-    FtlDevParams& P = h->P;
-    const ftl_config* cfg = &P.cfg;
-    if (!h->g_env) h->G = (P.R > 4 || h->co_envs <= h->cus * 4 * 8) ? 8 : 4;
-    if (P.R > 4) h->G = 8;
-    const int epw = FTL_WAVE / h->G;
-    h->rg_epw = epw;
-    const int f_max = cfg->rand_fps_hi > 0 ? cfg->rand_fps_hi - 1 : cfg->frames_per_step;
-    size_t o = align_up((size_t)epw * cfg->n_static * 16 + (size_t)epw * 4 + 32, 16);
-    P.fr_rec_stride = (int)align_up((size_t)f_max, 16);
-    P.fr_rec_off = (int)o; o += (size_t)P.fr_rec_stride * epw;
-    P.fr_pend_off = (int)o; o += (size_t)epw * (P.fr_defer ? f_max - 1 : 1) * 16;
-    P.fr_env_off = (int)o; o += (size_t)epw * 4 + 16 + (size_t)epw * 16;      // slot -> env, item counter, box of the trajectory block being filled
-    P.fr_lds = (int)o;
-    h->dirty = true;
-    return o > 64 * 1024 ? 1 : 0;
-}
-
 int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle** out) {
     if (!cfg || !out) return fail(FTL_E_INVALID, "null argument");
     if (n_envs <= 0) return fail(FTL_E_INVALID, "n_envs must be positive");
     if (device < 0) return fail(FTL_E_INVALID, "device < 0: this library has no CPU path");
     std::string why;
-    int rc = validate(*cfg, why);
-    if (rc) return fail(rc, why);
-    ftl_handle* h = new (std::nothrow) ftl_handle();
+    if (int rc = validate(*cfg, why)) return fail(rc, why);
+    ftl_handle* h = new (std::nothrow) ftl_handle();       // value-initialised: every member, P and its padding included, starts as zero
     if (!h) return fail(FTL_E_DEVICE, "out of host memory");
-    memset(&h->P, 0, sizeof h->P);
     h->P.cfg = *cfg;
     // (which pass a sensor belongs to is a flag: the host tables and the kernels compare it with 0 / 1)
     for (int k = 0; k < FTL_MAX_LASERS; k++) h->P.cfg.lasers[k].after_tracker = cfg->lasers[k].after_tracker ? 1 : 0;
-    h->device = device;
-    h->bound = false; h->have_scen = false; h->dP = nullptr; h->dirty = true;
-    h->rg_mem = nullptr; h->rg_tot = nullptr; h->rg_parity = 0; h->rg_launches = 0; h->mt_mem = nullptr; h->timing = false; h->tev_used = 0;
-    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->last_lasers = nullptr; h->queue = {}; h->sampler = {}; h->rs = {};
-    {   // measured: +9 % with random_frames_per_step (long frame kernels whose tails the other half's ray kernel fills), -1 % with a
-        // fixed 10 frames per step -- so it is on for the former only; FTL_SPLIT=0/1 overrides
-        const char* sp = getenv("FTL_SPLIT");
-        h->split = n_envs >= 8192 && (sp ? sp[0] == '1' : cfg->rand_fps_hi > 0) && cfg->has_tracker != 1;   // (the v1 tracker kernel covers all envs at once)
-        h->split_env = sp != nullptr;
-    }
-    {   // the scatter pass reads one histogram row per block of 1024 envs: fine up to a few hundred blocks
-        const char* off = getenv("FTL_NO_REGROUP");
-        const char* ev = getenv("FTL_REGROUP_EVERY");      // tuning knob: rebuild the permutation every k-th launch (default 4)
-        h->rg_every = (ev && atoi(ev) > 0) ? (unsigned)atoi(ev) : 4u;       // (round 3: every 4th launch, 212 against 209 M env-steps/s at every 2nd -- with the
-                                                                            //  later frames' searches deferred the frame kernel is as fast on a staler order)
-        // Sorting the envs by expected cost pays when the frame kernel runs in more than one round of wavefronts (the long ones start
-        // first, the short ones fill in behind them: +10 % on config B at 65,536 envs).  When every wavefront is resident from the start
-        // the launch takes as long as its slowest wavefront, and a wavefront that holds ALL the expensive envs is slower than any
-        // wavefront of an unsorted batch: config E at 32,768 envs -9 %, config D at 4,096 envs -16 % with the sort.  So it is on only
-        // beyond one round -- or with random frame counts, whose keys make the wavefronts uniform in length.  FTL_NO_REGROUP=0/1 overrides.
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        const char* g8 = getenv("FTL_DEBUG_G8");
-        h->g_env = g8 != nullptr; h->cus = cus; h->co_envs = n_envs;
-        h->G = (2 + cfg->n_bears > 4 || (g8 ? g8[0] == '1' : n_envs <= cus * 4 * 8)) ? 8 : 4;       // (set_lanes)
-        const int epw_f = FTL_WAVE / h->G;
-        const bool beyond_one_round = (n_envs + epw_f - 1) / epw_f > cus * 4 * FTL_FRAMESG_WPE;
-        h->regroup = (off ? off[0] != '1' : (beyond_one_round || cfg->rand_fps_hi > 0)) && (n_envs + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK <= 512;
-        h->rg_env = off != nullptr; h->rg_every_env = ev && atoi(ev) > 0; h->rg_slots = cus * 4 * FTL_FRAMESG_WPE; h->rg_epw = epw_f;
-    }
+    h->device = device; h->dirty = true;
+    h->sw = read_switches();
+    // two streams: measured +9 % with random_frames_per_step (long frame kernels whose tails the other half's ray kernel fills), -1 % with a
+    // fixed 10 frames per step -- so it is on for the former only; FTL_SPLIT=0/1 overrides.  (The v1 tracker kernel covers all envs at once.)
+    h->split = n_envs >= 8192 && (h->sw.split >= 0 ? h->sw.split == 1 : cfg->rand_fps_hi > 0) && cfg->has_tracker != 1;
+    // the permutation of the cost sort is rebuilt every k-th launch (round 3: every 4th launch, 212 against 209 M env-steps/s at every
+    // 2nd -- with the later frames' searches deferred the frame kernel is as fast on a staler order); FTL_REGROUP_EVERY is the tuning knob
+    h->rg_every = h->sw.regroup_every > 0 ? (unsigned)h->sw.regroup_every : 4u;
+    h->cus = 256;
+    (void)hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device);
     FtlDevParams& P = h->P;
     P.n_envs = n_envs;
     P.R = 2 + cfg->n_bears;
@@ -262,8 +364,7 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
         // Every shipped config scans all its ray sensors on one side of the tracker: the other pass has nothing to do, and the kernels
         // compiled without the loop over the passes run the one that has.  FTL_RAYS_ONE_PASS=0/1 overrides (1 is the default where it applies).
         P.pass_single = P.pass_rays[0] > 0 && P.pass_rays[1] > 0 ? -1 : (P.pass_rays[1] > 0 ? 1 : 0);
-        const char* op = getenv("FTL_RAYS_ONE_PASS");
-        h->one_pass = P.pass_single >= 0 && !(op && op[0] == '0');
+        h->one_pass = P.pass_single >= 0 && h->sw.one_pass != 0;
     }
     if (rays > 1023) { delete h; return fail(FTL_E_INVALID, "more than 1023 rays per env (the candidate list of the ray kernel packs a ray index into 10 bits)"); }
     if (hmax * (P.R - 1) > FTL_WAVE) { delete h; return fail(FTL_E_INVALID, "max_prev_obs x (1 + bears) exceeds one wavefront of snapshot rects"); }
@@ -281,31 +382,28 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
     // State layout.  The small fields of an env form one record (fields in the order below, the ray kernel's inputs first; 16-byte aligned
     // fields, a stride that is a multiple of 128 bytes); the long ones are [n_envs][per_env] arrays in 256-byte aligned regions.
     const size_t n = (size_t)n_envs;
-    struct { const char* name; size_t per_env; int dtype; size_t esz; bool rec; } spec[FTL_N_FIELDS] = {
-        {"rb_pos", (size_t)P.R * 2, 1, 4, true}, {"rb_dbl", (size_t)P.R * FTL_RD_COUNT, 2, 8, true}, {"rb_int", (size_t)P.R * FTL_RI_COUNT, 0, 4, true},
-        {"env_int", FTL_EI_COUNT, 0, 4, true}, {"env_dbl", FTL_ED_COUNT, 2, 8, true}, {"traj", (size_t)cfg->traj_cap * 2, 1, 4, false},
-        {"hist", (size_t)cfg->corr_cap * 2, 2, 8, false}, {"corr", (size_t)cfg->corr_cap * 4, 2, 8, false},
-        {"snap_rects", (size_t)hmax * (P.R - 1) * 4, 0, 4, true}, {"snap_win", (size_t)hmax * 4, 0, 4, true},
-        {"traj_bb", (size_t)(cfg->traj_cap / FTL_TRAJ_BLOCK) * 4, 1, 4, false}, {"ep_stats", FTL_N_METRICS, 2, 8, false},
-        {"hist1", (size_t)(cfg->has_tracker == 1 ? cfg->hist1_cap : 0) * 2, 1, 4, false}, {"fol_cs", 2, 2, 8, true},
-        {"corr32", (size_t)cfg->corr_cap * 4, 1, 4, false}};
-    static const int rec_order[8] = {3 /*env_int*/, 13 /*fol_cs*/, 0 /*rb_pos*/, 1 /*rb_dbl*/, 9 /*snap_win*/, 8 /*snap_rects*/, 4 /*env_dbl*/, 2 /*rb_int*/};
+    size_t per_env[FTL_N_FIELDS];
+    per_env[F_rb_pos] = (size_t)P.R * 2; per_env[F_rb_dbl] = (size_t)P.R * FTL_RD_COUNT; per_env[F_rb_int] = (size_t)P.R * FTL_RI_COUNT;
+    per_env[F_env_int] = FTL_EI_COUNT; per_env[F_env_dbl] = FTL_ED_COUNT; per_env[F_fol_cs] = 2;
+    per_env[F_snap_rects] = (size_t)hmax * (P.R - 1) * 4; per_env[F_snap_win] = (size_t)hmax * 4;
+    per_env[F_traj] = (size_t)cfg->traj_cap * 2; per_env[F_traj_bb] = (size_t)(cfg->traj_cap / FTL_TRAJ_BLOCK) * 4;
+    per_env[F_hist] = (size_t)cfg->corr_cap * 2; per_env[F_corr] = (size_t)cfg->corr_cap * 4; per_env[F_corr32] = (size_t)cfg->corr_cap * 4;
+    per_env[F_hist1] = (size_t)(cfg->has_tracker == 1 ? cfg->hist1_cap : 0) * 2; per_env[F_ep_stats] = FTL_N_METRICS;
     size_t ro = 0;
-    for (int k = 0; k < 8; k++) {
-        const int i = rec_order[k];
+    for (int i : kRecOrder) {
         ro = align_up(ro, 16);
-        h->fields[i] = Field{spec[i].name, ro, spec[i].per_env, spec[i].dtype, 0};
-        ro += spec[i].per_env * spec[i].esz;
+        h->fields[i] = Field{kFields[i].name, ro, per_env[i], kFields[i].dtype, 0};
+        ro += per_env[i] * kFields[i].esz;
     }
     const size_t rec_stride = align_up(ro, 128);
     P.rec_stride = (int32_t)rec_stride;
-    for (int k = 0; k < 8; k++) h->fields[rec_order[k]].stride = rec_stride;
+    for (int i : kRecOrder) h->fields[i].stride = rec_stride;
     size_t cur = rec_stride * n;
     for (int i = 0; i < FTL_N_FIELDS; i++) {
-        if (spec[i].rec) continue;
+        if (kFields[i].rec) continue;
         cur = align_up(cur, 256);
-        h->fields[i] = Field{spec[i].name, cur, spec[i].per_env, spec[i].dtype, spec[i].per_env * spec[i].esz};
-        cur += spec[i].per_env * spec[i].esz * n;
+        h->fields[i] = Field{kFields[i].name, cur, per_env[i], kFields[i].dtype, per_env[i] * kFields[i].esz};
+        cur += per_env[i] * kFields[i].esz * n;
     }
     h->state_bytes = align_up(cur, 256);
     {   // corridor ring (f32x4) + near rects (int4 + u32) + corridor refs (u32) + green caps (f32x4 + u32) + counters
@@ -314,26 +412,19 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
         // LDS copy of the corridor ring: up to 128 points (the windows of the snapshots span a few dozen; the ring itself is sized
         // for a crawling leader); FTL_DEBUG_CORR_LDS_CAP forces a smaller copy (tests of the unstaged path)
         P.corr_lds_cap = cfg->corr_cap < 128 ? cfg->corr_cap : 128;
-        if (const char* lc = getenv("FTL_DEBUG_CORR_LDS_CAP")) { int v = atoi(lc); if (v >= 2 && v <= cfg->corr_cap && (v & (v - 1)) == 0) P.corr_lds_cap = v; }
+        if (const int v = h->sw.corr_lds_cap; v >= 2 && v <= cfg->corr_cap && (v & (v - 1)) == 0) P.corr_lds_cap = v;
+        // the float32 minima are sized by the EXPL rows of rays_inst(), which have the widest HM for any hmax (5 or FTL_HMAX accumulators
+        // per ray), whichever instantiation the handle launches.  (The occupancy every profile was taken at depends on this size.)
+        const int hm_lds = rays_inst(hmax, true, false, false, false).hm;
         P.lds_rays = (int)((size_t)P.corr_lds_cap * 16 + rects * 20 + (size_t)2 * P.corr_lds_cap * 4 + (size_t)2 * hmax * 20 + 64
-                           + (size_t)rays * 16 + (size_t)rays * (hmax <= 5 ? 5 : FTL_HMAX) * 4      /* float32 minima, >= the HM of whichever instantiation launch() picks */ + (size_t)rays * 4
+                           + (size_t)rays * 16 + (size_t)rays * hm_lds * 4 + (size_t)rays * 4
                            + rects * 8 + 32                   /* facing-edge list (u16 x 4 per rect) + edge counters */
                            + (size_t)FTL_PAIR_CAP * 2 + 16);  /* candidate list of phase 3 */
     }
-    {   // frame kernel LDS: near lists + their counters | frame records (one byte per env and frame) | pending position checks | slot -> env | block boxes
-        const int f_max = cfg->rand_fps_hi > 0 ? cfg->rand_fps_hi - 1 : cfg->frames_per_step;
-        // The searches of frames 1.. wait for the end of the step when the step is short enough for their items to sit in LDS and the frame
-        // count is the same for every env; otherwise every frame's searches run right after it (one item per env at most).
-        const char* dv = getenv("FTL_DEFER");
-        P.fr_defer = (cfg->rand_fps_hi == 0 && f_max >= 2 && f_max <= 16 && cfg->traj_cap <= 65535 && !(dv && dv[0] == '0')) ? 1 : 0;
-        if (cfg->traj_cap > 65535 || f_max > 4095) { delete h; return fail(FTL_E_INVALID, "traj_cap above 65535 or more than 4095 frames per step"); }
-        if (set_lanes(h)) { delete h; return fail(FTL_E_INVALID, "the frame kernel needs more than 64 KiB of LDS per wavefront (static rects x frames per step)"); }
-        if (getenv("FTL_DEBUG_PRINT_LDS")) fprintf(stderr, "ftl: frame kernel LDS %d B per wavefront, %d lanes per env, %d frames at most, searches %s\n", P.fr_lds, h->G, f_max, P.fr_defer ? "deferred" : "in frame");
-    }
-    auto debug_pad = [](const char* name) { const char* v = getenv(name); const int p = v ? atoi(v) : 0; return p < 0 ? 0 : (p > 48 * 1024 ? 48 * 1024 : p); };
-    P.lds_rays += debug_pad("FTL_DEBUG_LDS_PAD_RAYS");      // diagnostic: occupancy of the ray kernel without touching the code
-    h->lds_pad = (size_t)debug_pad("FTL_DEBUG_LDS_PAD");
-    if (getenv("FTL_DEBUG_PRINT_LDS")) fprintf(stderr, "ftl: ray kernel LDS %d B per env\n", P.lds_rays);
+    P.lds_rays += h->sw.lds_pad_rays;      // diagnostic: occupancy of the ray kernel without touching the code
+    if (cfg->traj_cap > 65535 || frames_max(*cfg) > 4095) { delete h; return fail(FTL_E_INVALID, "traj_cap above 65535 or more than 4095 frames per step"); }
+    if (apply_plan(h, n_envs)) { delete h; return FTL_E_INVALID; }
+    report_plan(h);
     if (P.lds_rays > 64 * 1024) { delete h; return fail(FTL_E_INVALID, "config needs more than 64 KiB of LDS per env"); }
     if (ftl_aux_lds_bytes(*cfg) > 64 * 1024) { delete h; return fail(FTL_E_INVALID, "the compas / lidar / radar sensors of this config need more than 64 KiB of LDS per env"); }
     *out = h;
@@ -381,14 +472,7 @@ int ftl_bind_state(ftl_handle* h, void* dev_state, size_t bytes) {
     if (!h || !dev_state) return fail(FTL_E_INVALID, "null argument");
     if (bytes < h->state_bytes) return fail(FTL_E_INVALID, "state buffer too small");
     if (((uintptr_t)dev_state) & 255) return fail(FTL_E_INVALID, "state buffer must be 256-byte aligned");
-    unsigned char* b = (unsigned char*)dev_state;
-    FtlDevParams& P = h->P;
-    P.rb_pos = (float*)(b + h->fields[0].offset); P.rb_dbl = (double*)(b + h->fields[1].offset); P.rb_int = (int32_t*)(b + h->fields[2].offset);
-    P.env_int = (int32_t*)(b + h->fields[3].offset); P.env_dbl = (double*)(b + h->fields[4].offset); P.traj = (float*)(b + h->fields[5].offset);
-    P.hist = (double*)(b + h->fields[6].offset); P.corr = (double*)(b + h->fields[7].offset);
-    P.snap_rects = (int32_t*)(b + h->fields[8].offset); P.snap_win = (int32_t*)(b + h->fields[9].offset);
-    P.traj_bb = (float*)(b + h->fields[10].offset); P.ep_stats = (double*)(b + h->fields[11].offset);
-    P.hist1 = (float*)(b + h->fields[12].offset); P.fol_cs = (double*)(b + h->fields[13].offset); P.corr32 = (float*)(b + h->fields[14].offset);
+    for (int i = 0; i < FTL_N_FIELDS; i++) *(void**)((char*)&h->P + kFields[i].ptr) = (unsigned char*)dev_state + h->fields[i].offset;
     h->bound = true; h->dirty = true;
     return FTL_OK;
 }
@@ -415,23 +499,17 @@ int ftl_set_reset_window(ftl_handle* h, int32_t base, int32_t count, int32_t str
 
 int ftl_tune(ftl_handle* h, int32_t what, int32_t value) {
     if (!h) return fail(FTL_E_INVALID, "null argument");
-    switch (what) {
-    case FTL_TUNE_COSCHEDULED_ENVS:
+    if (what == FTL_TUNE_COSCHEDULED_ENVS) {
         if (value < h->P.n_envs) return fail(FTL_E_INVALID, "co-scheduled envs below this handle's own");
-        h->co_envs = value;
-        if (set_lanes(h)) return fail(FTL_E_INVALID, "the frame kernel needs more than 64 KiB of LDS per wavefront (static rects x frames per step)");
-        if (!h->rg_env)
-            h->regroup = ((value + h->rg_epw - 1) / h->rg_epw > h->rg_slots || h->P.cfg.rand_fps_hi > 0) && (h->P.n_envs + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK <= 512;
-        return FTL_OK;
-    case FTL_TUNE_REGROUP_EVERY:
+        if (int rc = apply_plan(h, value)) return rc;
+    } else if (what == FTL_TUNE_REGROUP_EVERY) {
         if (value < 1) return fail(FTL_E_INVALID, "regroup interval below 1");
-        if (!h->rg_every_env) h->rg_every = (unsigned)value;
-        return FTL_OK;
-    case FTL_TUNE_TWO_STREAMS:
-        if (!h->split_env) h->split = value != 0 && h->P.n_envs >= 8192 && h->P.cfg.has_tracker != 1;
-        return FTL_OK;
-    }
-    return fail(FTL_E_INVALID, "unknown tuning key");
+        if (h->sw.regroup_every <= 0) h->rg_every = (unsigned)value;
+    } else if (what == FTL_TUNE_TWO_STREAMS) {
+        if (h->sw.split < 0) h->split = value != 0 && h->P.n_envs >= 8192 && h->P.cfg.has_tracker != 1;
+    } else return fail(FTL_E_INVALID, "unknown tuning key");
+    report_plan(h);
+    return FTL_OK;
 }
 
 // device copy of the frozen parameters: (re)uploaded only after bind_state / load_scenarios, never on the steady-state step path
@@ -453,7 +531,7 @@ static int sync_params(ftl_handle* h) {
 static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    if (h->regroup && !h->rg_mem) {
+    if (h->sched.regroup && !h->rg_mem) {
         const size_t n = (size_t)h->P.n_envs, nb = (n + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK;
         const size_t o_bh = align_up(n * 4, 256), o_rank = o_bh + align_up(nb * FTL_NKEYS * 4, 256), o_keys = o_rank + align_up(n * 2, 256), o_tot = o_keys + align_up(n, 256);
         e = hipMalloc(&h->rg_mem, o_tot + 2 * FTL_NKEYS * sizeof(int));
@@ -482,64 +560,19 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
         while (h->tev.size() < h->tev_used + 5) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) return fail(FTL_E_DEVICE, "hipEventCreate"); h->tev.push_back(ev); }
         tev = h->tev.data() + h->tev_used; h->tev_used += 5;
     }
-    const bool xr = (call.flags & (FTL_STEP_NEXT_RESET | FTL_CALL_DEFER_RESET | FTL_CALL_FINISH)) != 0 || call.ended || call.restarted;
+    const FtlKernel frames = h->k_frames[call_xr(call) ? 1 : 0];
     auto launch_range = [&](int part, int parts, hipStream_t s) {
-        const int epw0 = FTL_WAVE / h->G;
-        const int n_groups = (h->P.n_envs + epw0 - 1) / epw0;
+        const int epw = h->sched.epw;
+        const int n_groups = (h->P.n_envs + epw - 1) / epw;
         const int my_groups = (n_groups - part + parts - 1) / parts;
-        FtlCall c2 = call; c2.part = part; c2.parts = parts; c2.epw = epw0;
-        const int count = my_groups * epw0;              // slots of this launch (the tail of the last group may be idle)
-        const bool reg = h->P.cfg.n_speed_regime >= 0 || h->P.cfg.n_acc_regime >= 0 || h->P.cfg.rand_fps_hi > 0;
-        const int epw = FTL_WAVE / h->G;
-        size_t lds = (size_t)h->P.fr_lds + h->lds_pad;
-        const dim3 grid((count + epw - 1) / epw), block(FTL_WAVE);
+        FtlCall c2 = call; c2.part = part; c2.parts = parts; c2.epw = epw;
         if (tev) (void)hipEventRecord(tev[0], s);
-        if (xr) {           // next-step restarts, the deferred reset of ftl_step_final and its masks: the instantiations that carry them
-            if (h->G == 4) {
-                if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<4, true, true>), grid, block, lds, s, h->dP, c2);
-                else hipLaunchKernelGGL((ftl_frames_group_kernel<4, false, true>), grid, block, lds, s, h->dP, c2);
-            } else {
-                if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<8, true, true>), grid, block, lds, s, h->dP, c2);
-                else hipLaunchKernelGGL((ftl_frames_group_kernel<8, false, true>), grid, block, lds, s, h->dP, c2);
-            }
-        } else if (h->G == 4) {
-            if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<4, true>), grid, block, lds, s, h->dP, c2);
-            else hipLaunchKernelGGL((ftl_frames_group_kernel<4, false>), grid, block, lds, s, h->dP, c2);
-        } else {
-            if (reg) hipLaunchKernelGGL((ftl_frames_group_kernel<8, true>), grid, block, lds, s, h->dP, c2);
-            else hipLaunchKernelGGL((ftl_frames_group_kernel<8, false>), grid, block, lds, s, h->dP, c2);
-        }
-        if (h->P.cfg.has_tracker == 1 && part == 0)      // the v1 tracker's scan + snapshot bookkeeping for ALL envs (one thread per env)
+        hipLaunchKernelGGL(frames, dim3(my_groups), dim3(FTL_WAVE), (size_t)h->P.fr_lds + h->sw.lds_pad, s, h->dP, c2);
+        if (h->has_trk1 && part == 0)      // the v1 tracker's scan + snapshot bookkeeping for ALL envs (one thread per env)
             hipLaunchKernelGGL(ftl::ftl_tracker1_kernel, dim3((unsigned)((h->P.n_envs + 255) / 256)), dim3(256), 0, s, h->dP, c2);
         if (tev) (void)hipEventRecord(tev[1], s);
-        if (h->P.cfg.n_lasers > 0) {
-            bool expl = false;
-            for (int k = 0; k < h->P.cfg.n_lasers; k++) expl = expl || h->P.cfg.lasers[k].explicit_angles != 0 || h->P.cfg.lasers[k].pad_sectors != 0 || h->P.cfg.lasers[k].compas != 0;
-            const dim3 rgrid(count);
-            // CAPPED: the LDS copy of the corridor ring is smaller than the ring (corr_cap > 128, the configs with regimes or the v1 tracker):
-            // the instantiations that carry the unstaged path
-#define FTL_LAUNCH_RAYS_P(HM_, EXPL_, SPLIT_, ONE_) do { \
-                if (capped) hipLaunchKernelGGL((ftl_rays_kernel<HM_, EXPL_, SPLIT_, true, ONE_>), rgrid, block, h->P.lds_rays, s, h->dP, c2); \
-                else hipLaunchKernelGGL((ftl_rays_kernel<HM_, EXPL_, SPLIT_, false, ONE_>), rgrid, block, h->P.lds_rays, s, h->dP, c2); } while (0)
-#define FTL_LAUNCH_RAYS(HM_, EXPL_, SPLIT_) FTL_LAUNCH_RAYS_P(HM_, EXPL_, SPLIT_, false)
-            // the one-stream kernels of the common sensors also exist without the loop over the passes (ONE_PASS, ftl_device.hpp)
-#define FTL_LAUNCH_RAYS_1(HM_) do { if (h->one_pass) FTL_LAUNCH_RAYS_P(HM_, false, false, true); else FTL_LAUNCH_RAYS_P(HM_, false, false, false); } while (0)
-            const bool capped = h->P.corr_lds_cap < h->P.cfg.corr_cap;
-            if (parts > 1) {   // two-stream mode: the instantiations that map blocks to one half of the slot groups
-                if (!expl && h->P.hmax > 5 && h->P.hmax <= 10) FTL_LAUNCH_RAYS(10, false, true);
-                else if (h->P.hmax <= 5) FTL_LAUNCH_RAYS(5, true, true);
-                else FTL_LAUNCH_RAYS(FTL_HMAX, true, true);
-            } else if (expl) {        // LeaderCorridor_lasers or pad_sectors somewhere in the config: the two instantiations that carry that code
-                if (h->P.hmax <= 5) FTL_LAUNCH_RAYS(5, true, false);
-                else FTL_LAUNCH_RAYS(FTL_HMAX, true, false);
-            } else if (h->P.hmax <= 5) FTL_LAUNCH_RAYS_1(5);
-            else if (h->P.hmax <= 8) FTL_LAUNCH_RAYS_1(8);
-            else if (h->P.hmax <= 10) FTL_LAUNCH_RAYS_1(10);   // the shipped training configs
-            else FTL_LAUNCH_RAYS_1(FTL_HMAX);
-#undef FTL_LAUNCH_RAYS_1
-#undef FTL_LAUNCH_RAYS
-#undef FTL_LAUNCH_RAYS_P
-        }
+        // one block per slot of this launch (the tail of the last group may be idle)
+        if (const FtlKernel rays = h->k_rays[parts > 1 ? 1 : 0]) hipLaunchKernelGGL(rays, dim3(my_groups * epw), dim3(FTL_WAVE), h->P.lds_rays, s, h->dP, c2);
         if (tev) (void)hipEventRecord(tev[2], s);
     };
     if (h->split) {
@@ -550,16 +583,13 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
         (void)hipEventRecord(h->ev_join, h->side);
         (void)hipStreamWaitEvent((hipStream_t)stream, h->ev_join, 0);        // the caller's stream sees the whole step
     } else launch_range(0, 1, (hipStream_t)stream);
-    {   // compas / lidar / leader-track detectors: one more launch, only for configs that have such a sensor
-        bool aux = h->P.cfg.n_aux > 0;
-        for (int k = 0; k < h->P.cfg.n_lasers; k++) aux = aux || h->P.cfg.lasers[k].compas != 0;
-        if (aux) hipLaunchKernelGGL(ftl_aux_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), ftl_aux_lds_bytes(h->P.cfg), (hipStream_t)stream, h->dP, call);
-    }
+    // compas / lidar / leader-track detectors: one more launch, only for configs that have such a sensor
+    if (h->has_aux) hipLaunchKernelGGL(ftl_aux_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), ftl_aux_lds_bytes(h->P.cfg), (hipStream_t)stream, h->dP, call);
     if (tev) (void)hipEventRecord(tev[3], (hipStream_t)stream);
     // the frame kernel left every env's cost class for its next step: rebuild the slot -> env map.  The classes are stable
     // from step to step unless the frame count is random, so every second launch is enough then.  (The reset pass of ftl_step_final
     // follows a step that has just rebuilt or kept the map: the few envs it re-initialises move with the next rebuild.)
-    if (h->regroup && !(call.flags & FTL_CALL_FINISH) && (h->P.cfg.rand_fps_hi > 0 || call.mode == 1 || (h->rg_launches++ % h->rg_every) == 0)) {
+    if (h->sched.regroup && !(call.flags & FTL_CALL_FINISH) && (h->P.cfg.rand_fps_hi > 0 || call.mode == 1 || (h->rg_launches++ % h->rg_every) == 0)) {
         const unsigned nb = (unsigned)((h->P.n_envs + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK);
         int* tot = h->rg_tot + (h->rg_parity & 1u) * FTL_NKEYS, *tot_next = h->rg_tot + ((h->rg_parity + 1u) & 1u) * FTL_NKEYS;
         h->rg_parity++;
@@ -576,6 +606,13 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
 
 // What a reset or a step needs before anything is launched: a bound state, a scenario pool, the output arrays and, with policy_obs, one
 // history length on every ray sensor
+// the arguments of a call that restarts nothing and asks for no masks
+static FtlCall make_call(const ftl_handle* h, int mode, const ftl_outputs* out) {
+    FtlCall c = {};
+    c.mode = mode; c.out = *out; c.action_kind = FTL_ACTION_BOX2; c.win_base = h->win_base; c.win_count = h->win_count; c.win_stride = h->win_stride;
+    return c;
+}
+
 static int check_ready(const ftl_handle* h, const ftl_outputs* out, bool policy_obs = true) {
     if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
     if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
@@ -595,8 +632,8 @@ int ftl_reset(ftl_handle* h, const int32_t* scen_idx, const uint8_t* mask, const
     if (!h || !scen_idx) return fail(FTL_E_INVALID, "null argument");
     int rc = check_ready(h, out);
     if (rc) return rc;
-    FtlCall call; call.mode = 1; call.scen_idx = scen_idx; call.mask = mask; call.out = *out; call.action = nullptr; call.flags = 0; call.action_kind = FTL_ACTION_BOX2; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
-    call.ended = nullptr; call.restarted = nullptr;
+    FtlCall call = make_call(h, 1, out);
+    call.scen_idx = scen_idx; call.mask = mask;
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     return launch(h, call, stream);
 }
@@ -628,8 +665,9 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
     if (same_step && (!fin->obs_num || !fin->target || (h->P.lasers_len > 0 && !fin->lasers)))
         return fail(FTL_E_INVALID, "ftl_final_outputs: obs_num / lasers / target missing (needed under FTL_STEP_AUTO_RESET / FTL_STEP_QUEUE_RESET / FTL_STEP_SAMPLE_RESET)");
     if (same_step && fin->policy_obs && !out->policy_obs) return fail(FTL_E_INVALID, "ftl_final_outputs.policy_obs needs ftl_outputs.policy_obs");
-    FtlCall call; call.mode = 0; call.action = (const double*)action; call.action_kind = encoding; call.out = *out; call.flags = flags; call.scen_idx = nullptr; call.mask = nullptr; call.win_base = h->win_base; call.win_count = h->win_count; call.win_stride = h->win_stride;
-    call.ended = fin ? fin->ended : nullptr; call.restarted = fin ? fin->restarted : nullptr;
+    FtlCall call = make_call(h, 0, out);
+    call.action = (const double*)action; call.action_kind = encoding; call.flags = flags;
+    if (fin) { call.ended = fin->ended; call.restarted = fin->restarted; }
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     if (queue || sample) {   // a plain step, then the chooser's kernel and the reset pass of the slots it restarts (ftl_restart.hpp)
         if (sample) { rc = ftl_sampler_check_window(h); if (rc) return rc; }

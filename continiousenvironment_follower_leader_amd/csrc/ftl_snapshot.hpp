@@ -148,7 +148,7 @@ static Args make_args(const ftl_handle* h) {
     a.row_bytes = align_up(row, 256);
     a.row16 = (int32_t)(a.row_bytes / 16);
     a.env_id_base = h->P.cfg.env_id_base;
-    const size_t w0 = h->fields[3].offset / 4;                 // env_int (record-relative: record 0 sits at offset 0)
+    const size_t w0 = h->fields[F_env_int].offset / 4;                 // env_int (record-relative: record 0 sits at offset 0)
     a.w_episodes = (int32_t)(w0 + FTL_EI_EPISODES); a.w_sticky = (int32_t)(w0 + FTL_EI_ERROR_STICKY); a.w_stream = (int32_t)(w0 + FTL_EI_STREAM);
     return a;
 }
@@ -197,7 +197,7 @@ int ftl_pack_envs(const ftl_handle* h, const int32_t* env_ids, int32_t k, void* 
     int rc = ftls::snap_check(h, env_ids, k, rows, 0u);
     if (rc || k == 0) return rc;
     ftls::Args a = ftls::make_args(h);
-    a.blob = (unsigned char*)h->P.env_int - h->fields[3].offset; a.rows = (unsigned char*)rows; a.ids = env_ids; a.k = k;
+    a.blob = (unsigned char*)h->P.env_int - h->fields[F_env_int].offset; a.rows = (unsigned char*)rows; a.ids = env_ids; a.k = k;
     return ftls::snap_launch(h, a, false, stream);
 }
 
@@ -205,7 +205,7 @@ int ftl_unpack_envs(ftl_handle* h, const void* rows, const int32_t* env_ids, int
     int rc = ftls::snap_check(h, env_ids, k, rows, flags);
     if (rc || k == 0) return rc;
     ftls::Args a = ftls::make_args(h);
-    a.blob = (unsigned char*)h->P.env_int - h->fields[3].offset; a.rows = (unsigned char*)rows; a.ids = env_ids; a.k = k; a.flags = flags;
+    a.blob = (unsigned char*)h->P.env_int - h->fields[F_env_int].offset; a.rows = (unsigned char*)rows; a.ids = env_ids; a.k = k; a.flags = flags;
     if (flags & FTL_ENV_SLOT_STATS) a.skip_seg = -1;
     return ftls::snap_launch(h, a, true, stream);
 }
