@@ -43,6 +43,7 @@ constexpr int kRecOrder[] = {F_env_int, F_fol_cs, F_rb_pos, F_rb_dbl, F_snap_win
 struct Switches {
     int split, no_regroup, g8, one_pass, defer;                       // FTL_SPLIT, FTL_NO_REGROUP, FTL_DEBUG_G8, FTL_RAYS_ONE_PASS, FTL_DEFER
     int regroup_every, corr_lds_cap, lds_pad, lds_pad_rays;            // FTL_REGROUP_EVERY, FTL_DEBUG_CORR_LDS_CAP, FTL_DEBUG_LDS_PAD[_RAYS] (0: not given)
+    int pair_window;                                                  // FTL_DEBUG_PAIR_WINDOW (0: not given)
     bool print_lds;                                                   // FTL_DEBUG_PRINT_LDS
 };
 
@@ -51,7 +52,7 @@ Switches read_switches() {
     auto num = [](const char* name, int hi) { const char* v = getenv(name); const int p = v ? atoi(v) : 0; return p < 0 ? 0 : (p > hi ? hi : p); };
     return Switches{tri("FTL_SPLIT", 0), tri("FTL_NO_REGROUP", 0), tri("FTL_DEBUG_G8", 0), tri("FTL_RAYS_ONE_PASS", 1), tri("FTL_DEFER", 1),
                     num("FTL_REGROUP_EVERY", INT32_MAX), num("FTL_DEBUG_CORR_LDS_CAP", INT32_MAX), num("FTL_DEBUG_LDS_PAD", 48 * 1024),
-                    num("FTL_DEBUG_LDS_PAD_RAYS", 48 * 1024), getenv("FTL_DEBUG_PRINT_LDS") != nullptr};
+                    num("FTL_DEBUG_LDS_PAD_RAYS", 48 * 1024), num("FTL_DEBUG_PAIR_WINDOW", FTL_PAIR_CAP), getenv("FTL_DEBUG_PRINT_LDS") != nullptr};
 }
 
 // What ftl_create and ftl_tune decide about the frame kernel and the cost sort: plan_schedule()
@@ -63,7 +64,7 @@ struct Schedule {
 
 // The template arguments of the kernels a handle launches, as values: frame_inst(), rays_inst()
 struct FrameInst { int G; bool reg, xr; };
-struct RaysInst { int hm; bool expl, split, capped, one_pass; };
+struct RaysInst { int hm; bool expl, split, capped, one_pass, mask; };
 typedef void (*FtlKernel)(const FtlDevParams*, const FtlCall);
 
 }  // namespace
@@ -207,15 +208,16 @@ bool call_xr(const FtlCall& c) { return (c.flags & (FTL_STEP_NEXT_RESET | FTL_CA
 
 // Which instantiation of the ray kernel runs (DESIGN.md has the table).  expl: a sensor with explicit angles, padded sectors or a compas
 // is in the config; capped: the LDS copy of the corridor ring is smaller than the ring; two_streams: the launch covers one half of the slot
-// groups.  Only the one-stream kernels of the common sensors exist in every HM and without the loop over the passes.
-RaysInst rays_inst(int hmax, bool expl, bool capped, bool two_streams, bool one_pass) {
+// groups.  Only the one-stream kernels of the common sensors exist in every HM and without the loop over the passes; of those, the
+// one-pass ones also exist in the mask form of phase 3, which a pass of at most 64 rays (pass_rays) runs.
+RaysInst rays_inst(int hmax, bool expl, bool capped, bool two_streams, bool one_pass, int pass_rays) {
     const int wide = hmax <= 5 ? 5 : FTL_HMAX;
-    if (two_streams) return (!expl && hmax > 5 && hmax <= 10) ? RaysInst{10, false, true, capped, false} : RaysInst{wide, true, true, capped, false};
-    if (expl) return RaysInst{wide, true, false, capped, false};
-    return RaysInst{hmax <= 5 ? 5 : hmax <= 8 ? 8 : hmax <= 10 ? 10 : FTL_HMAX, false, false, capped, one_pass};
+    if (two_streams) return (!expl && hmax > 5 && hmax <= 10) ? RaysInst{10, false, true, capped, false, false} : RaysInst{wide, true, true, capped, false, false};
+    if (expl) return RaysInst{wide, true, false, capped, false, false};
+    return RaysInst{hmax <= 5 ? 5 : hmax <= 8 ? 8 : hmax <= 10 ? 10 : FTL_HMAX, false, false, capped, one_pass, one_pass && pass_rays <= 64};
 }
 
-// The instantiations: 2 x 2 x 2 of the frame kernel, and of the ray kernel the 3 + 2 + 4 x 2 (HM, EXPL, SPLIT, ONE_PASS) rows that
+// The instantiations: 2 x 2 x 2 of the frame kernel, and of the ray kernel the 3 + 2 + 4 x 3 (HM, EXPL, SPLIT, ONE_PASS, MASK) rows that
 // rays_inst can return, each with and without CAPPED
 template <bool XR> FtlKernel frame_kernel_x(int G, bool reg) {
     if (G == 4) return reg ? ftl_frames_group_kernel<4, true, XR> : ftl_frames_group_kernel<4, false, XR>;
@@ -223,10 +225,13 @@ template <bool XR> FtlKernel frame_kernel_x(int G, bool reg) {
 }
 FtlKernel frame_kernel(const FrameInst& f) { return f.xr ? frame_kernel_x<true>(f.G, f.reg) : frame_kernel_x<false>(f.G, f.reg); }
 
-template <int HM, bool EXPL, bool SPLIT, bool ONE> FtlKernel rays_kernel_c(bool capped) {
-    return capped ? ftl_rays_kernel<HM, EXPL, SPLIT, true, ONE> : ftl_rays_kernel<HM, EXPL, SPLIT, false, ONE>;
+template <int HM, bool EXPL, bool SPLIT, bool ONE, bool MASK = false> FtlKernel rays_kernel_c(bool capped) {
+    return capped ? ftl_rays_kernel<HM, EXPL, SPLIT, true, ONE, MASK> : ftl_rays_kernel<HM, EXPL, SPLIT, false, ONE, MASK>;
 }
-template <int HM> FtlKernel rays_kernel_1(const RaysInst& r) { return r.one_pass ? rays_kernel_c<HM, false, false, true>(r.capped) : rays_kernel_c<HM, false, false, false>(r.capped); }
+template <int HM> FtlKernel rays_kernel_1(const RaysInst& r) {
+    if (r.mask) return rays_kernel_c<HM, false, false, true, true>(r.capped);
+    return r.one_pass ? rays_kernel_c<HM, false, false, true>(r.capped) : rays_kernel_c<HM, false, false, false>(r.capped);
+}
 FtlKernel rays_kernel(const RaysInst& r) {
     if (r.split) return r.hm == 10 ? rays_kernel_c<10, false, true, false>(r.capped) : r.hm == 5 ? rays_kernel_c<5, true, true, false>(r.capped) : rays_kernel_c<FTL_HMAX, true, true, false>(r.capped);
     if (r.expl) return r.hm == 5 ? rays_kernel_c<5, true, false, false>(r.capped) : rays_kernel_c<FTL_HMAX, true, false, false>(r.capped);
@@ -247,7 +252,7 @@ int apply_plan(ftl_handle* h, int co_envs) {
     for (int k = 0; k < c.n_lasers; k++) { compas = compas || c.lasers[k].compas != 0; expl = expl || c.lasers[k].explicit_angles != 0 || c.lasers[k].pad_sectors != 0; }
     for (int i = 0; i < 2; i++) {
         h->k_frames[i] = frame_kernel(frame_inst(c, s.G, i == 1));
-        h->rays[i] = rays_inst(P.hmax, expl || compas, P.corr_lds_cap < c.corr_cap, i == 1, h->one_pass);
+        h->rays[i] = rays_inst(P.hmax, expl || compas, P.corr_lds_cap < c.corr_cap, i == 1, h->one_pass, h->one_pass ? P.pass_rays[P.pass_single] : 0);
         h->k_rays[i] = c.n_lasers > 0 ? rays_kernel(h->rays[i]) : nullptr;
     }
     h->has_aux = c.n_aux > 0 || compas; h->has_trk1 = c.has_tracker == 1;
@@ -265,6 +270,8 @@ void report_plan(const ftl_handle* h) {
         if (h->k_rays[i]) snprintf(r[i], sizeof r[i], "rays<%d,%d,%d,%d,%d>", h->rays[i].hm, h->rays[i].expl, h->rays[i].split, h->rays[i].capped, h->rays[i].one_pass);
     fprintf(stderr, "ftl: kernels frames<%d,%d>, %s on one stream, %s on two; regroup %s every %u, two streams %s\n", h->sched.G, frame_inst(P.cfg, h->sched.G, false).reg,
             r[0], r[1], h->sched.regroup ? "on" : "off", h->rg_every, h->split ? "on" : "off");
+    // (a continuation line: the three lines above are parsed as they stand)
+    if (h->k_rays[0]) fprintf(stderr, "     ray candidates: %s form on one stream, %s form on two, window %d\n", h->rays[0].mask ? "mask" : "list", h->rays[1].mask ? "mask" : "list", P.pair_window);
 }
 
 }  // namespace
@@ -365,6 +372,9 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
         // compiled without the loop over the passes run the one that has.  FTL_RAYS_ONE_PASS=0/1 overrides (1 is the default where it applies).
         P.pass_single = P.pass_rays[0] > 0 && P.pass_rays[1] > 0 ? -1 : (P.pass_rays[1] > 0 ? 1 : 0);
         h->one_pass = P.pass_single >= 0 && h->sw.one_pass != 0;
+        // pairs per window of the mask form's candidate list: all of it, or what FTL_DEBUG_PAIR_WINDOW asks for (tests of the multi-window path)
+        P.pair_window = FTL_PAIR_CAP;
+        if (const int v = h->sw.pair_window; v >= 16 && v <= FTL_PAIR_CAP && v % 16 == 0) P.pair_window = v;
     }
     if (rays > 1023) { delete h; return fail(FTL_E_INVALID, "more than 1023 rays per env (the candidate list of the ray kernel packs a ray index into 10 bits)"); }
     if (hmax * (P.R - 1) > FTL_WAVE) { delete h; return fail(FTL_E_INVALID, "max_prev_obs x (1 + bears) exceeds one wavefront of snapshot rects"); }
@@ -415,7 +425,7 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
         if (const int v = h->sw.corr_lds_cap; v >= 2 && v <= cfg->corr_cap && (v & (v - 1)) == 0) P.corr_lds_cap = v;
         // the float32 minima are sized by the EXPL rows of rays_inst(), which have the widest HM for any hmax (5 or FTL_HMAX accumulators
         // per ray), whichever instantiation the handle launches.  (The occupancy every profile was taken at depends on this size.)
-        const int hm_lds = rays_inst(hmax, true, false, false, false).hm;
+        const int hm_lds = rays_inst(hmax, true, false, false, false, 0).hm;
         P.lds_rays = (int)((size_t)P.corr_lds_cap * 16 + rects * 20 + (size_t)2 * P.corr_lds_cap * 4 + (size_t)2 * hmax * 20 + 64
                            + (size_t)rays * 16 + (size_t)rays * hm_lds * 4 + (size_t)rays * 4
                            + rects * 8 + 32                   /* facing-edge list (u16 x 4 per rect) + edge counters */

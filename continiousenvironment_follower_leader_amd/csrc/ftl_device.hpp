@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/ftl.h"
+#include "ftl_raymask.hpp"
 
 #define FTL_WAVE 64
 #define FTL_HMAX 12         // compile-time cap on max_prev_obs (the shipped training configs use 10)
@@ -57,7 +58,8 @@ struct FtlDevParams {
     int32_t pass_rays[2], pass_base[2];   // rays of the sensors scanned before / after the tracker, and where they start in ray_dir
     float pass_lmax[2];               // longest laser_length of the pass (float32)
     int32_t pass_single;              // the only pass that has rays (0 / 1), or -1 when both have: what the ONE_PASS ray kernels run
-    int32_t _pad_pass;                // (keeps ray_dir below on a 32-byte boundary: static_assert behind the struct)
+    int32_t pair_window;              // mask form of phase 3: pairs per window of a chunk's candidate list (FTL_PAIR_CAP; FTL_DEBUG_PAIR_WINDOW
+                                      // makes it smaller).  (Also keeps ray_dir below on a 32-byte boundary: static_assert behind the struct)
     int32_t fr_rec_off, fr_rec_stride, fr_pend_off, fr_env_off, fr_defer, fr_lds;   // frame kernel: LDS offsets of the frame records / pending items / slot -> env table
                                       // (+ the item counter), "the later frames' position searches wait for the end of the step", total dynamic LDS
     int32_t corr_lds_cap;             // corridor points the ray kernel stages in LDS (a power of two <= cfg.corr_cap; a longer window is read in place)
@@ -466,8 +468,12 @@ __shared__ unsigned long long s_rcyc[16];
 // pointers, per-env scalars, the snapshot windows -- alive to the end of phase 4, and at 80 VGPRs the compiler holds them in the lanes
 // of a VGPR: 48 v_writelane in the prologue and 73 v_readlane in the pass of <5>, executed by every env-step (a tenth of its VALU issue)
 // although the second trip only finds pass_rays == 0.  `which` stays a run-time, wave-uniform value: what pays is the missing back edge.
-template <int HM, bool EXPL = false, bool SPLIT = false, bool CAPPED = false, bool ONE_PASS = false>
+// MASK = the pass has at most 64 rays in all (decided on the host from pass_rays: rays_inst): phase 3 collects a segment's candidate rays
+// of ALL sensors in one 64-bit word per lane and emits the pairs of a chunk with one scan and one store loop, instead of one emission
+// sequence per sensor.  Only the one-pass, one-stream kernels of the common sensors have it; every other launch runs the list form.
+template <int HM, bool EXPL = false, bool SPLIT = false, bool CAPPED = false, bool ONE_PASS = false, bool MASK = false>
 __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const FtlDevParams* __restrict__ Pp, const FtlCall C) {
+    static_assert(!MASK || (ONE_PASS && !EXPL && !SPLIT), "the mask form of phase 3 exists for the one-pass, one-stream kernels of the common sensors");
     extern __shared__ __align__(16) unsigned char lds[];
     using namespace ftl;
     const FtlDevParams& P = *Pp;
@@ -757,6 +763,8 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
             // candidates of a chunk -- all sensors -- go to a list of (lane that holds the segment, ray) pairs instead; the list is
             // tested densely, 64 pairs at a time, the segment coming from its lane by a cross-lane read.
             int np_u = 0;                                  // entries in the list (wave-uniform)
+            // mask form: pairs per window of the list, FTL_PAIR_CAP unless FTL_DEBUG_PAIR_WINDOW asked for less
+            const int win = MASK ? min(max(P.pair_window, 16), FTL_PAIR_CAP) : FTL_PAIR_CAP;
             for (int w0 = 0; w0 < n_items; w0 += FTL_WAVE) {
                 const int w = w0 + lane;
                 int m = -1, mq = 0;
@@ -809,76 +817,140 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
                     }
                     __syncthreads();                                     // read before the next pairs overwrite them
                 };
+                if constexpr (MASK) {
+                    // Mask form.  Per sensor only the mapping of the arc to (first ray, count) is left -- the same expressions, slack and
+                    // "every ray" rules as in the list form below, written out in both: shared through a lambda, the list form no longer
+                    // compiled to the code it had before the mask form existed (same place) -- and the rays go into the lane's mask at the sensor's place in the
+                    // pass's index space (ftl_raymask.hpp).  Then, once per chunk for all sensors: the number of pairs per lane, one
+                    // wave-wide prefix sum, and one store loop in which every lane peels its own bits into the list.  A chunk with more
+                    // pairs than a window holds (P.pair_window <= FTL_PAIR_CAP) is worked off window by window: a lane writes the part of
+                    // its range [pos, pos + count) that falls into the window, the window is tested, the next one follows.  The set of
+                    // (segment, ray) pairs is the list form's; only their order differs, and a minimum does not depend on it.
+                    unsigned long long mk = 0ull;
 #pragma nounroll
-                for (int k = 0; k < c.n_lasers; k++) {
-                    const FtlRaySensor rs = P.ray_sens[k];                 // wave-uniform: two scalar loads
-                    if ((int)((rs.flags >> 5) & 1u) != which || (rs.flags & 64u)) continue;
-                    const int N = rs.count, rbase = rs.rbase;
-                    int i0 = 0, cnt = 0;
-                    if (m >= 0 && ((rs.flags >> mq) & 1u) && !(dmin2 > rs.reach2)) {      // the sensor reacts to this class and can reach the segment
-                        // candidate rays: the arc in units of this sensor's ray spacing from its ray 0.  The slack (>= 0.01 rad, and 0.022
-                        // spacings on top) dwarfs what the arc can be off by -- 2e-5 rad per arc_atan2 and a few float32 roundings of values
-                        // below 2 N -- so the rays listed here always include every ray the reference's test can accept.
-                        const float fN = (float)N;
-                        const float wu = wd * rs.inv_step;
-                        if ((rs.flags & 16u) || dmin2 < 4.0f || wu > 0.5f * fN - 0.05f) { i0 = 0; cnt = N; }   // through / next to the origin, or rays
-                                                                                              // at explicit angles (<= 7 of them): every ray
-                        else {
-                            float st = __builtin_fmaf(a0, rs.inv_step, -rs.off_u);
-                            st = __builtin_fmaf(-floorf(st * rs.inv_count), fN, st);           // into [0, N) (an ulp outside is absorbed by the wrap below)
-                            i0 = (int)ceilf(st - rs.slack);
-                            cnt = (int)floorf(st + wu + rs.slack) - i0 + 1;
-                            cnt = cnt > N ? N : cnt;
+                    for (int k = 0; k < c.n_lasers; k++) {
+                        const FtlRaySensor rs = P.ray_sens[k];             // wave-uniform: two scalar loads.  (Read once before the chunk loop and
+                                                                          // held in SGPRs, the records cost 33 more spilled SGPRs and 2.4 % of the
+                                                                          // step: DESIGN.md section 4, "one candidate-ray mask per segment")
+                        if ((int)((rs.flags >> 5) & 1u) != which || (rs.flags & 64u)) continue;
+                        const int N = rs.count;
+                        int i0 = 0, cnt = 0;
+                        if (m >= 0 && ((rs.flags >> mq) & 1u) && !(dmin2 > rs.reach2)) {
+                            const float fN = (float)N;
+                            const float wu = wd * rs.inv_step;
+                            if ((rs.flags & 16u) || dmin2 < 4.0f || wu > 0.5f * fN - 0.05f) { i0 = 0; cnt = N; }
+                            else {
+                                float st = __builtin_fmaf(a0, rs.inv_step, -rs.off_u);
+                                st = __builtin_fmaf(-floorf(st * rs.inv_count), fN, st);
+                                i0 = (int)ceilf(st - rs.slack);
+                                cnt = (int)floorf(st + wu + rs.slack) - i0 + 1;
+                                cnt = cnt > N ? N : cnt;
+                            }
                         }
+                        mk |= ftl_ray_mask(i0, cnt, N, rs.rbase);
                     }
 #if defined(FTL_RAYS_STOP) && FTL_RAYS_STOP == 5   // diagnostic: decode + fetch + arcs only, no ray tests
-                    cnt = cnt == 0x7fffffff ? 1 : 0;
+                    mk = mk == ~0ull - 1ull ? 1ull : 0ull;
+#endif
+                    // inclusive prefix sum of the counts over the wavefront: four steps inside the rows of 16 lanes, then the last lane of
+                    // row 0 / 2 into row 1 / 3 and lane 31 into rows 2 and 3 (a lane without a source adds 0)
+                    const int cntm = __popcll(mk);
+                    int inc = cntm;
+                    inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);      // row_shr:1
+                    inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);      // row_shr:2
+                    inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, false);      // row_shr:4
+                    inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, false);      // row_shr:8
+                    inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);      // row_bcast:15 -> rows 1, 3
+                    inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);      // row_bcast:31 -> rows 2, 3
+                    const int tot = __builtin_amdgcn_readlane(inc, FTL_WAVE - 1);
+                    const int pos = inc - cntm;                            // where this lane's pairs start among the chunk's
+#ifdef FTL_PROFILE_RAYS
+                    { int mc = cntm; for (int o = 32; o >= 1; o >>= 1) mc = max(mc, __shfl_xor(mc, o)); const int ni = __popcll(__ballot(m >= 0)); if (threadIdx.x == 0) { s_rcyc[8] += 1ull + (w0 == FTL_WAVE ? 1ull << 40 : 0ull); /* bits 40..: env-steps with a second chunk (n_items > 64) */ s_rcyc[9] += mc; s_rcyc[10] += tot; s_rcyc[11] += ni; s_rcyc[12] += (mc <= 2); s_rcyc[13] += (mc > 2 && mc <= 4); s_rcyc[14] += (mc > 4 && mc <= 8); s_rcyc[15] += (mc > 8); } }
+#endif
+                    // the two halves of the mask are peeled with 32-bit operations (rays 0-31, then 32-63); `rel` is the lane's next
+                    // position relative to the window -- it starts as the lane's offset among the chunk's pairs and drops by a window's
+                    // length per window (below zero, unsigned, only in a lane that has no bits left) -- and only positions inside the
+                    // window are ever written
+                    unsigned lo = (unsigned)mk, hi = (unsigned)(mk >> 32);
+                    const unsigned tag = (unsigned)lane << 10;
+                    unsigned rel = (unsigned)pos;
+                    for (int wb = 0; wb < tot; wb += win, rel -= (unsigned)win) {
+                        while (lo != 0u && rel < (unsigned)win) { s_pair[rel++] = (unsigned short)(tag | (unsigned)(__ffs(lo) - 1)); lo &= lo - 1u; }
+                        while (hi != 0u && rel < (unsigned)win) { s_pair[rel++] = (unsigned short)(tag | (unsigned)(__ffs(hi) + 31)); hi &= hi - 1u; }
+                        flush(min(tot - wb, win));
+                    }
+                } else {
+#pragma nounroll
+                    for (int k = 0; k < c.n_lasers; k++) {
+                        const FtlRaySensor rs = P.ray_sens[k];                 // wave-uniform: two scalar loads
+                        if ((int)((rs.flags >> 5) & 1u) != which || (rs.flags & 64u)) continue;
+                        const int N = rs.count, rbase = rs.rbase;
+                        int i0 = 0, cnt = 0;
+                        if (m >= 0 && ((rs.flags >> mq) & 1u) && !(dmin2 > rs.reach2)) {      // the sensor reacts to this class and can reach the segment
+                            // candidate rays: the arc in units of this sensor's ray spacing from its ray 0.  The slack (>= 0.01 rad, and 0.022
+                            // spacings on top) dwarfs what the arc can be off by -- 2e-5 rad per arc_atan2 and a few float32 roundings of values
+                            // below 2 N -- so the rays listed here always include every ray the reference's test can accept.
+                            const float fN = (float)N;
+                            const float wu = wd * rs.inv_step;
+                            if ((rs.flags & 16u) || dmin2 < 4.0f || wu > 0.5f * fN - 0.05f) { i0 = 0; cnt = N; }   // through / next to the origin, or rays
+                                                                                                  // at explicit angles (<= 7 of them): every ray
+                            else {
+                                float st = __builtin_fmaf(a0, rs.inv_step, -rs.off_u);
+                                st = __builtin_fmaf(-floorf(st * rs.inv_count), fN, st);           // into [0, N) (an ulp outside is absorbed by the wrap below)
+                                i0 = (int)ceilf(st - rs.slack);
+                                cnt = (int)floorf(st + wu + rs.slack) - i0 + 1;
+                                cnt = cnt > N ? N : cnt;
+                            }
+                        }
+#if defined(FTL_RAYS_STOP) && FTL_RAYS_STOP == 5   // diagnostic: decode + fetch + arcs only, no ray tests
+                        cnt = cnt == 0x7fffffff ? 1 : 0;
 #endif
 #ifdef FTL_PROFILE_RAYS
-                    if (threadIdx.x == 0) { s_rcyc[8] += 1; }
-                    { int mc = cnt; for (int o = 32; o >= 1; o >>= 1) mc = max(mc, __shfl_xor(mc, o)); int ni = __popcll(__ballot(m >= 0)); int sc = cnt; for (int o = 32; o >= 1; o >>= 1) sc += __shfl_xor(sc, o); if (threadIdx.x == 0) { s_rcyc[9] += mc; s_rcyc[10] += sc; s_rcyc[11] += ni; s_rcyc[12] += (mc <= 2); s_rcyc[13] += (mc > 2 && mc <= 4); s_rcyc[14] += (mc > 4 && mc <= 8); s_rcyc[15] += (mc > 8); } }
+                        if (threadIdx.x == 0) { s_rcyc[8] += 1; }
+                        { int mc = cnt; for (int o = 32; o >= 1; o >>= 1) mc = max(mc, __shfl_xor(mc, o)); int ni = __popcll(__ballot(m >= 0)); int sc = cnt; for (int o = 32; o >= 1; o >>= 1) sc += __shfl_xor(sc, o); if (threadIdx.x == 0) { s_rcyc[9] += mc; s_rcyc[10] += sc; s_rcyc[11] += ni; s_rcyc[12] += (mc <= 2); s_rcyc[13] += (mc > 2 && mc <= 4); s_rcyc[14] += (mc > 4 && mc <= 8); s_rcyc[15] += (mc > 8); } }
 #endif
-                    // (a) segments with more than FTL_WIDE_ARC candidates: the wavefront writes their pairs, one ray per lane; more than a
-                    //     wavefront of them (a segment next to the follower under a 180-ray sensor) are tested on the spot
-                    unsigned long long wide = __ballot(cnt > FTL_WIDE_ARC);
-                    while (wide) {
-                        const int L = __ffsll((long long)wide) - 1; wide &= wide - 1;
-                        const int i0L = __builtin_amdgcn_readlane(i0, L), cntL = __builtin_amdgcn_readlane(cnt, L);
-                        if (cntL > FTL_WAVE) {
-                            const float4 sgL = make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.x), L)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.y), L)),
-                                                           __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.z), L)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.w), L)));
-                            const unsigned smL = (unsigned)__builtin_amdgcn_readlane((int)sm, L);
-                            for (int t = lane; t < cntL; t += FTL_WAVE) {
-                                int i = i0L + t; i = i < 0 ? i + N : (i >= N ? i - N : i);
-                                test(rbase + i, sgL, smL);
+                        // (a) segments with more than FTL_WIDE_ARC candidates: the wavefront writes their pairs, one ray per lane; more than a
+                        //     wavefront of them (a segment next to the follower under a 180-ray sensor) are tested on the spot
+                        unsigned long long wide = __ballot(cnt > FTL_WIDE_ARC);
+                        while (wide) {
+                            const int L = __ffsll((long long)wide) - 1; wide &= wide - 1;
+                            const int i0L = __builtin_amdgcn_readlane(i0, L), cntL = __builtin_amdgcn_readlane(cnt, L);
+                            if (cntL > FTL_WAVE) {
+                                const float4 sgL = make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.x), L)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.y), L)),
+                                                               __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.z), L)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sg.w), L)));
+                                const unsigned smL = (unsigned)__builtin_amdgcn_readlane((int)sm, L);
+                                for (int t = lane; t < cntL; t += FTL_WAVE) {
+                                    int i = i0L + t; i = i < 0 ? i + N : (i >= N ? i - N : i);
+                                    test(rbase + i, sgL, smL);
+                                }
+                                continue;
                             }
-                            continue;
+                            if (np_u + cntL > FTL_PAIR_CAP) { flush(np_u); np_u = 0; }
+                            if (lane < cntL) {
+                                int i = i0L + lane; i = i < 0 ? i + N : (i >= N ? i - N : i);
+                                s_pair[np_u + lane] = (unsigned short)((L << 10) | (rbase + i));
+                            }
+                            np_u += cntL;
                         }
-                        if (np_u + cntL > FTL_PAIR_CAP) { flush(np_u); np_u = 0; }
-                        if (lane < cntL) {
-                            int i = i0L + lane; i = i < 0 ? i + N : (i >= N ? i - N : i);
-                            s_pair[np_u + lane] = (unsigned short)((L << 10) | (rbase + i));
-                        }
-                        np_u += cntL;
-                    }
-                    // (b) the others: each lane appends its own 0..FTL_WIDE_ARC pairs at the prefix sum of the counts (no atomics: the
-                    //     count is two bits, a ballot per bit gives every lane its offset and the wavefront the total)
-                    const int own = cnt > FTL_WIDE_ARC ? 0 : cnt;
-                    int pre = 0, tot = 0;
+                        // (b) the others: each lane appends its own 0..FTL_WIDE_ARC pairs at the prefix sum of the counts (no atomics: the
+                        //     count is two bits, a ballot per bit gives every lane its offset and the wavefront the total)
+                        const int own = cnt > FTL_WIDE_ARC ? 0 : cnt;
+                        int pre = 0, tot = 0;
 #pragma unroll
-                    for (int b = 0; b < 4; b++) if ((FTL_WIDE_ARC >> b) != 0) {
-                        const unsigned long long bm = __ballot((own >> b) & 1);
-                        pre += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u)) << b;
-                        tot += __popcll(bm) << b;
+                        for (int b = 0; b < 4; b++) if ((FTL_WIDE_ARC >> b) != 0) {
+                            const unsigned long long bm = __ballot((own >> b) & 1);
+                            pre += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u)) << b;
+                            tot += __popcll(bm) << b;
+                        }
+                        if (np_u + tot > FTL_PAIR_CAP) { flush(np_u); np_u = 0; }       // (tot <= 64 x FTL_WIDE_ARC = FTL_PAIR_CAP)
+                        for (int t = 0; t < own; t++) {
+                            int i = i0 + t; i = i < 0 ? i + N : (i >= N ? i - N : i);
+                            s_pair[np_u + pre + t] = (unsigned short)((lane << 10) | (rbase + i));
+                        }
+                        np_u += tot;
                     }
-                    if (np_u + tot > FTL_PAIR_CAP) { flush(np_u); np_u = 0; }       // (tot <= 64 x FTL_WIDE_ARC = FTL_PAIR_CAP)
-                    for (int t = 0; t < own; t++) {
-                        int i = i0 + t; i = i < 0 ? i + N : (i >= N ? i - N : i);
-                        s_pair[np_u + pre + t] = (unsigned short)((lane << 10) | (rbase + i));
-                    }
-                    np_u += tot;
+                    if (np_u > 0) { flush(np_u); np_u = 0; }      // before the next chunk replaces the segments in the lanes
                 }
-                if (np_u > 0) { flush(np_u); np_u = 0; }      // before the next chunk replaces the segments in the lanes
             }
         }
         FTL_RTIC(5);

@@ -31,6 +31,9 @@ for phase, steps in (("steps 0-30", 30), ("steps 30-150", 120), ("steps 150-250"
     rc = v[32:48]
     if sum(rc[:8]):
         rn = ["stage corridor (2nd trip)", "phase1 table", "phase2 ray ends", "phase3 decode", "phase3 arcs", "phase3 ray tests", "phase4 rows", "setup (1st trip)"]
+        second = rc[8] >> 40; rc[8] &= (1 << 40) - 1      # mask form: chunks with w0 == 64 ride in the high bits of the chunk counter
+        if second:
+            print(phase, "RAYS env-steps with a second chunk (n_items > 64): %.4f" % (second / (steps * n)))
         rt = sum(rc[:8])
         print(phase, "RAYS cycles share:", " ".join("%s=%.3f" % (rn[i], rc[i] / rt) for i in range(8)), "cycles/env-step=%.0f" % (rt / (steps * n)),
               "chunks/env-step=%.2f max-cnt/chunk=%.2f sum-cnt/chunk=%.1f items/chunk=%.1f" % (rc[8] / (steps * n), rc[9] / max(rc[8], 1), rc[10] / max(rc[8], 1), rc[11] / max(rc[8], 1)),
