@@ -22,6 +22,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_restart.hpp"),
            os.path.join(_PKG, "csrc", "ftl_queue.hpp"),
            os.path.join(_PKG, "csrc", "ftl_sampler.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_rollout.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
 # translation units: the device code + C-ABI, and the host-only scenario generator (reset-time, no GPU code)
 UNITS = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp")]
@@ -80,6 +81,11 @@ def load():
     lib.ftl_step.argtypes = [vp, vp, C.POINTER(abi.Outputs), u32, vp]
     lib.ftl_step_encoded.argtypes = [vp, vp, i32, C.POINTER(abi.Outputs), u32, vp]
     lib.ftl_step_final.argtypes = [vp, vp, i32, C.POINTER(abi.Outputs), C.POINTER(abi.FinalOutputs), u32, vp]
+    lib.ftl_scan.argtypes = [vp, C.POINTER(abi.Outputs), vp]
+    lib.ftl_scan.restype = C.c_int
+    lib.ftl_sizeof_rollout_outputs.restype = C.c_size_t
+    lib.ftl_rollout.argtypes = [vp, vp, C.c_int64, i32, i32, C.c_double, C.POINTER(abi.Outputs), C.POINTER(abi.RolloutOutputs), u32, vp]
+    lib.ftl_rollout.restype = C.c_int
     lib.ftl_kernel_timing.argtypes = [vp, i32]
     lib.ftl_kernel_times.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(i32)]
     lib.ftl_episode_metrics.argtypes = [vp, vp, vp, u32, vp]
@@ -145,6 +151,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_env_bytes", "ftl_env_layout_id", "ftl_pack_envs", "ftl_unpack_envs",
            "ftl_sizeof_episode_record", "ftl_sizeof_episode_queue", "ftl_set_episode_queue", "ftl_queue_start",
            "ftl_sizeof_scenario_sampler", "ftl_set_scenario_sampler", "ftl_sampler_refresh", "ftl_sampler_start",
+           "ftl_scan", "ftl_sizeof_rollout_outputs", "ftl_rollout",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -29,6 +29,7 @@ FTL_STEP_AUTO_RESET = 1
 FTL_STEP_NEXT_RESET = 4
 FTL_STEP_QUEUE_RESET = 8
 FTL_STEP_SAMPLE_RESET = 16
+FTL_STEP_NO_SENSORS = 32          # no sensor kernels in this call: lasers / policy_obs keep what they held (ftl_scan refreshes them)
 FTL_EPISODE_DONE_AT_RESET = 1
 # columns of a scenario sampler's table (include/ftl.h, ftl_scenario_sampler)
 FTL_N_SCEN_STATS = 10
@@ -195,6 +196,11 @@ class FinalOutputs(C.Structure):
     """ftl_final_outputs: the terminal rows and the ended / restarted masks of ftl_step_final."""
     _fields_ = [("obs_num", C.c_void_p), ("lasers", C.c_void_p), ("target", C.c_void_p), ("policy_obs", C.c_void_p),
                 ("ended", C.c_void_p), ("restarted", C.c_void_p)]
+
+
+class RolloutOutputs(C.Structure):
+    """ftl_rollout_outputs: discounted return, alive steps and terminal status row per env of ftl_rollout."""
+    _fields_ = [("ret", C.c_void_p), ("steps", C.c_void_p), ("status", C.c_void_p)]
 
 
 class EpisodeRecord(C.Structure):

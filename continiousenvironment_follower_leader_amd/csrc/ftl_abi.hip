@@ -104,6 +104,7 @@ struct ftl_handle {
     FtlAttached<ftl_episode_queue> queue;         // ftl_set_episode_queue
     FtlAttached<ftl_scenario_sampler> sampler;    // ftl_set_scenario_sampler
     FtlRestartScratch rs;    // what a queue or sampler call hands to the reset pass (library-owned, allocated by the first such call: ftl_restart.hpp)
+    uint8_t* ro_alive;       // [n_envs] "the episode was running on entry to the step" of ftl_rollout (library-owned, allocated by the first rollout: ftl_rollout.hpp)
 };
 
 namespace {
@@ -443,8 +444,9 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
 
 void ftl_destroy(ftl_handle* h) {
     if (!h) return;
-    if (h->dP || h->rg_mem || h->side || h->mt_mem || h->rs.scen_idx) (void)hipSetDevice(h->device);
+    if (h->dP || h->rg_mem || h->side || h->mt_mem || h->rs.scen_idx || h->ro_alive) (void)hipSetDevice(h->device);
     if (h->rs.scen_idx) (void)hipFree(h->rs.scen_idx);
+    if (h->ro_alive) (void)hipFree(h->ro_alive);
     if (h->dP) (void)hipFree(h->dP);
     if (h->mt_mem) (void)hipFree(h->mt_mem);
     for (hipEvent_t ev : h->tev) (void)hipEventDestroy(ev);
@@ -538,7 +540,11 @@ static int sync_params(ftl_handle* h) {
     return FTL_OK;
 }
 
-static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
+// The kernels of one pass (a step, a reset, a reset pass) on `stream`.  FTL_STEP_NO_SENSORS in call_in.flags leaves out the two sensor
+// launches and nothing else; the kernels never see the bit.
+static int launch(ftl_handle* h, const FtlCall& call_in, void* stream) {
+    const bool sensors = !(call_in.flags & FTL_STEP_NO_SENSORS);
+    FtlCall call = call_in; call.flags &= ~(uint32_t)FTL_STEP_NO_SENSORS;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
     if (h->sched.regroup && !h->rg_mem) {
@@ -582,7 +588,7 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
             hipLaunchKernelGGL(ftl::ftl_tracker1_kernel, dim3((unsigned)((h->P.n_envs + 255) / 256)), dim3(256), 0, s, h->dP, c2);
         if (tev) (void)hipEventRecord(tev[1], s);
         // one block per slot of this launch (the tail of the last group may be idle)
-        if (const FtlKernel rays = h->k_rays[parts > 1 ? 1 : 0]) hipLaunchKernelGGL(rays, dim3(my_groups * epw), dim3(FTL_WAVE), h->P.lds_rays, s, h->dP, c2);
+        if (const FtlKernel rays = sensors ? h->k_rays[parts > 1 ? 1 : 0] : nullptr) hipLaunchKernelGGL(rays, dim3(my_groups * epw), dim3(FTL_WAVE), h->P.lds_rays, s, h->dP, c2);
         if (tev) (void)hipEventRecord(tev[2], s);
     };
     if (h->split) {
@@ -594,7 +600,7 @@ static int launch(ftl_handle* h, const FtlCall& call, void* stream) {
         (void)hipStreamWaitEvent((hipStream_t)stream, h->ev_join, 0);        // the caller's stream sees the whole step
     } else launch_range(0, 1, (hipStream_t)stream);
     // compas / lidar / leader-track detectors: one more launch, only for configs that have such a sensor
-    if (h->has_aux) hipLaunchKernelGGL(ftl_aux_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), ftl_aux_lds_bytes(h->P.cfg), (hipStream_t)stream, h->dP, call);
+    if (h->has_aux && sensors) hipLaunchKernelGGL(ftl_aux_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), ftl_aux_lds_bytes(h->P.cfg), (hipStream_t)stream, h->dP, call);
     if (tev) (void)hipEventRecord(tev[3], (hipStream_t)stream);
     // the frame kernel left every env's cost class for its next step: rebuild the slot -> env map.  The classes are stable
     // from step to step unless the frame count is random, so every second launch is enough then.  (The reset pass of ftl_step_final
@@ -659,7 +665,8 @@ int ftl_step_encoded(ftl_handle* h, const void* action, int32_t encoding, const 
 int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, const ftl_final_outputs* fin,
                    uint32_t flags, void* stream) {
     if (!h || !action) return fail(FTL_E_INVALID, "null argument");
-    flags &= FTL_STEP_AUTO_RESET | FTL_STEP_NEXT_RESET | FTL_STEP_QUEUE_RESET | FTL_STEP_SAMPLE_RESET;   // (other bits were always ignored; the kernel's internal ones stay internal)
+    const uint32_t blind = flags & FTL_STEP_NO_SENSORS;     // every pass of this call goes without the sensor kernels (launch())
+    flags &= FTL_STEP_AUTO_RESET | FTL_STEP_NEXT_RESET | FTL_STEP_QUEUE_RESET | FTL_STEP_SAMPLE_RESET;   // the reset bits (other bits were always ignored; the kernel's internal ones stay internal)
     if ((flags & FTL_STEP_AUTO_RESET) && (flags & FTL_STEP_NEXT_RESET)) return fail(FTL_E_INVALID, "FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET exclude each other");
     const bool queue = (flags & FTL_STEP_QUEUE_RESET) != 0;
     if (queue && flags != FTL_STEP_QUEUE_RESET) return fail(FTL_E_INVALID, "FTL_STEP_QUEUE_RESET excludes the other reset flags");
@@ -676,12 +683,12 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
         return fail(FTL_E_INVALID, "ftl_final_outputs: obs_num / lasers / target missing (needed under FTL_STEP_AUTO_RESET / FTL_STEP_QUEUE_RESET / FTL_STEP_SAMPLE_RESET)");
     if (same_step && fin->policy_obs && !out->policy_obs) return fail(FTL_E_INVALID, "ftl_final_outputs.policy_obs needs ftl_outputs.policy_obs");
     FtlCall call = make_call(h, 0, out);
-    call.action = (const double*)action; call.action_kind = encoding; call.flags = flags;
+    call.action = (const double*)action; call.action_kind = encoding; call.flags = flags | blind;
     if (fin) { call.ended = fin->ended; call.restarted = fin->restarted; }
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     if (queue || sample) {   // a plain step, then the chooser's kernel and the reset pass of the slots it restarts (ftl_restart.hpp)
         if (sample) { rc = ftl_sampler_check_window(h); if (rc) return rc; }
-        call.flags = 0; call.ended = nullptr; call.restarted = nullptr;
+        call.flags = blind; call.ended = nullptr; call.restarted = nullptr;
         rc = launch(h, call, stream);
         if (rc) return rc;
         ftlrs::Args a;
@@ -692,9 +699,35 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
     // same-step: the step defers the reset of the envs that finish (their terminal state gets the usual sensor scans), their terminal rows
     // go to `fin`, then a reset pass over fin->ended re-initialises them as the in-kernel auto-reset would have -- all on `stream`, after
     // the step's join when the handle runs two streams
-    call.flags = (flags & ~(uint32_t)FTL_STEP_AUTO_RESET) | FTL_CALL_DEFER_RESET;
+    call.flags = (flags & ~(uint32_t)FTL_STEP_AUTO_RESET) | FTL_CALL_DEFER_RESET | blind;
     rc = launch(h, call, stream);
     return rc ? rc : finish_step(h, call, out, fin, nullptr, fin->ended, stream);
+}
+
+int ftl_scan(ftl_handle* h, const ftl_outputs* out, void* stream) {
+    if (!h || !out) return fail(FTL_E_INVALID, "null argument");
+    int rc = check_ready(h, out);
+    if (rc) return rc;
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    rc = sync_params(h);
+    if (rc) return rc;
+    h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
+    // the sensor launches of a step (mode 0, no flags) with the kernels a step of this handle runs; a two-stream handle's two halves go
+    // one after the other on the caller's stream (every env is scanned once either way)
+    FtlCall call = make_call(h, 0, out);
+    const int parts = h->split ? 2 : 1, epw = h->sched.epw, n_groups = (h->P.n_envs + epw - 1) / epw;
+    if (const FtlKernel rays = h->k_rays[parts > 1 ? 1 : 0])
+        for (int part = 0; part < parts; part++) {
+            const int my_groups = (n_groups - part + parts - 1) / parts;
+            call.part = part; call.parts = parts; call.epw = epw;
+            if (my_groups > 0) hipLaunchKernelGGL(rays, dim3(my_groups * epw), dim3(FTL_WAVE), h->P.lds_rays, (hipStream_t)stream, h->dP, call);
+        }
+    call.part = call.parts = call.epw = 0;      // (as launch() hands the call to the aux kernel)
+    if (h->has_aux) hipLaunchKernelGGL(ftl_aux_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), ftl_aux_lds_bytes(h->P.cfg), (hipStream_t)stream, h->dP, call);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FTL_OK;
 }
 
 int ftl_kernel_timing(ftl_handle* h, int32_t enable) {
@@ -751,6 +784,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 #include "ftl_scenario_dev.hpp"  // the scenario generator on the GPU (ftl_generate_scenarios_device), same translation unit
 #include "ftl_render.hpp"        // batched top-down RGB frames (ftl_render), same translation unit
 #include "ftl_snapshot.hpp"      // snapshot / clone / restore of env rows (ftl_pack_envs, ftl_unpack_envs), same translation unit
+#include "ftl_rollout.hpp"       // T blind steps of an action sequence and their discounted return (ftl_rollout), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

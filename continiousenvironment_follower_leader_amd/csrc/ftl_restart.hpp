@@ -84,7 +84,8 @@ static int finish_step(ftl_handle* h, const FtlCall& step, const ftl_outputs* ou
                            *out, *fin, n, h->P.lasers_len, pol_len);
     }
     FtlCall rcall = step;
-    rcall.mode = 1; rcall.flags = FTL_CALL_FINISH | (scen_idx ? FTL_CALL_SCEN_IDX : 0u); rcall.scen_idx = scen_idx; rcall.mask = mask;
+    rcall.mode = 1; rcall.flags = FTL_CALL_FINISH | (scen_idx ? FTL_CALL_SCEN_IDX : 0u) | (step.flags & FTL_STEP_NO_SENSORS);   // a blind step's reset pass is blind too
+    rcall.scen_idx = scen_idx; rcall.mask = mask;
     rcall.action = nullptr; rcall.ended = nullptr; rcall.restarted = nullptr;
     return launch(h, rcall, stream);
 }

@@ -250,12 +250,14 @@ class _BatchBase:
             mask = torch.as_tensor(mask, dtype=torch.uint8, device=self.device).contiguous()
         return scen_idx, mask
 
-    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None):
+    def evaluate(self, policy, scen_ids, stream_ids=None, check_every=16, max_calls=None, sensors=True):
         """Play every scenario of ``scen_ids`` exactly once with ``action = policy((obs_num, lasers))`` and return the records (structured
         numpy array, ``abi.RECORD_DTYPE``, row q = entry q).  The queue's ``finished()`` count is read (one synchronisation) every
         ``check_every`` calls.  ``max_calls`` defaults to ceil(Q / n_envs) * (max_steps // least frames per step + 2) + check_every --
         no hand-out order needs more -- and exceeding it raises instead of spinning.  Detaches the queue afterwards.  The policy sees the
-        whole batch's rows, so the parts of a pipelined batch are joined after every step."""
+        whole batch's rows, so the parts of a pipelined batch are joined after every step.  ``sensors=False`` steps without the sensor
+        kernels (``step(..., sensors=False)``) for a policy that reads no ray sensor: ``lasers`` then stays what the queue's reset
+        scanned; the records do not depend on it."""
         q = self.set_episode_queue(scen_ids, stream_ids)
         try:
             self.reset_from_queue()
@@ -263,7 +265,7 @@ class _BatchBase:
             def obs():
                 self._wait_parts()
                 return self.obs_num, self.lasers
-            _evaluate_loop(self.cfg, self.n, q, obs, lambda a: self.step(a, auto_reset="queue"), policy, check_every, max_calls)
+            _evaluate_loop(self.cfg, self.n, q, obs, lambda a: self.step(a, auto_reset="queue", sensors=sensors), policy, check_every, max_calls)
             self._wait_parts()
             return q.records()
         finally:
@@ -509,7 +511,7 @@ class VecGame(_BatchBase):
             self.raise_on_errors(live_errors)
         return self.obs_num, self.lasers
 
-    def step(self, action, auto_reset=False, check_errors=False, live_errors=False):
+    def step(self, action, auto_reset=False, check_errors=False, live_errors=False, sensors=True):
         """action: f64[N,2] device tensor = (speed px/frame, signed rotation deg/frame) (ENV:927-933).  With
         ``discrete_action_space=True`` an integer tensor [N] (or [N,1]) of Discrete(5) indices, with ``constant_follower_speed=True`` a
         float tensor [N] (or [N,1]) of rotations: both are decoded on the device as ENV:909-925 does (``ftl_step_encoded``).
@@ -522,14 +524,70 @@ class VecGame(_BatchBase):
         ``"sample"`` -- a finished env adds its episode to the table of the attached ``ScenarioSampler`` and restarts on a world drawn from
         its weights (``set_scenario_sampler``; FTL_STEP_SAMPLE_RESET; outputs as under True, the final buffers are filled when the batch has
         them, ``ended`` = ``restarted`` = done).
+        ``sensors=False`` (with any ``auto_reset`` value; FTL_STEP_NO_SENSORS) leaves out the sensor kernels: ``lasers`` and ``policy_obs``
+        are not written and go stale -- they keep the readings of the last scan, and under ``"same_step"`` / ``"queue"`` / ``"sample"``
+        ``final_lasers`` / ``final_policy_obs`` are copies of those stale rows -- while ``obs_num``, ``target``, ``reward``, ``done``,
+        ``status``, the masks and the whole state are what the same step with sensors gives; ``scan()`` brings the readings up to date.
         ``check_errors=True`` synchronises and raises what the reference would have raised in any env (``raise_on_errors``);
         the default leaves the per-env sticky error words for ``error_report()`` so that the step stays asynchronous."""
         action, enc = self._encode_action(action, self.n)
         flags, fin = self._step_mode(auto_reset)
-        self._step_final(action.data_ptr(), enc, flags, fin, self._stream())
+        self._step_final(action.data_ptr(), enc, flags | (0 if sensors else abi.FTL_STEP_NO_SENSORS), fin, self._stream())
         if check_errors:
             self.raise_on_errors(live_errors)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
+
+    def scan(self):
+        """The sensor half of a step on the current state (``ftl_scan``): refreshes ``lasers``, and ``policy_obs`` when the batch has it, on
+        the current stream and returns ``lasers``.  After ``step(..., sensors=False)`` the readings are those the same step with sensors
+        gives; after ``restore()`` / ``clone()`` those the source env had.  Touches nothing else."""
+        self._need_pool()
+        self._scan(self._stream())
+        return self.lasers
+
+    def _scan(self, stream):
+        _lib.check(self.lib.ftl_scan(self.h, self._out_ref, stream), self.lib)
+
+    def rollout(self, actions, gamma=1.0, sensors=True):
+        """T steps without auto-reset under the open-loop action sequence ``actions`` with one call (``ftl_rollout``): ``[T, N, 2]`` float64,
+        ``[T, N]`` integers for Discrete(5) or ``[T, N]`` floats for Box(1), checked as ``step`` checks one step's actions.  Returns
+        ``(ret, steps, status)``, persistent device tensors allocated on first use: ``ret`` f64[N] = sum of gamma**t * reward_t over the
+        steps the env was alive in (its done word 0 on entry; the step that raises done counts), ``steps`` i32[N] the number of such steps
+        (0 for an env that was done on entry), ``status`` u8[N,3] the status row of the step that ended the episode (0/0/0 if none did).
+        The step outputs are those of step T-1; only that step scans, and with ``sensors=False`` none does (``lasers`` / ``policy_obs``
+        go stale as under ``step(..., sensors=False)``)."""
+        self._need_pool()
+        flat, enc, T = self._encode_rollout(actions, self.n)
+        row = flat.element_size() * (2 if enc == abi.FTL_ACTION_BOX2 else 1)
+        self._rollout(flat.data_ptr(), self.n * row, enc, T, gamma, sensors, self._stream())
+        return self.rollout_ret, self.rollout_steps, self.rollout_status
+
+    def _encode_rollout(self, actions, n):
+        """(the [T * n, ..] tensor ``_encode_action`` makes of a [T, n, ..] action sequence, its encoding, T)."""
+        if actions.dim() < 2 or actions.shape[0] < 1 or actions.shape[1] != n:
+            raise ValueError("a rollout's actions must be [T, n_envs, ...] with T >= 1")
+        T = int(actions.shape[0])
+        flat, enc = self._encode_action(actions.reshape(T * n, *actions.shape[2:]), T * n)
+        self._keep_rollout = flat
+        return flat, enc, T
+
+    def _rollout_outputs(self, views=None):
+        """Allocate (or, the parts of a pipelined batch, take as ``views``) the persistent ``rollout_ret`` / ``_steps`` / ``_status``."""
+        if getattr(self, "_ro", None) is None:
+            if views is None:
+                views = (torch.zeros(self.n, dtype=torch.float64, device=self.device), torch.zeros(self.n, dtype=torch.int32, device=self.device),
+                         torch.zeros(self.n, 3, dtype=torch.uint8, device=self.device))
+            self.rollout_ret, self.rollout_steps, self.rollout_status = views
+            ro = abi.RolloutOutputs()
+            ro.ret, ro.steps, ro.status = (t.data_ptr() for t in views)
+            self._ro = ro
+        return self._ro
+
+    def _rollout(self, action_ptr, step_bytes, enc, T, gamma, sensors, stream):
+        """The one call of ``ftl_rollout``: ``action_ptr`` the device address of this batch's first action row of step 0."""
+        ro = self._rollout_outputs()
+        _lib.check(self.lib.ftl_rollout(self.h, action_ptr, step_bytes, enc, T, float(gamma), self._out_ref, C.byref(ro),
+                                        0 if sensors else abi.FTL_STEP_NO_SENSORS, stream), self.lib)
 
     def _step_final(self, action_ptr, enc, flags, fin, stream):
         """The one call of ``ftl_step_final``: ``action_ptr`` the device address of this batch's first action row, ``fin`` as
@@ -1200,33 +1258,65 @@ class PipelinedVecGame(_BatchBase):
         scen_idx, mask = self._reset_args(scen_idx, mask)
         return self._reset_parts(lambda g, sh: g.reset(scen_idx[sh.lo:sh.hi], None if mask is None else mask[sh.lo:sh.hi]))
 
-    def step_part(self, k, action, auto_reset=False):
-        """One step of part k on its stream; ``action`` = the rows of part k (any layout ``VecGame.step`` takes); ``auto_reset`` as
-        ``VecGame.step`` (the final buffers' rows of part k are valid on ``stream(k)``)."""
+    def step_part(self, k, action, auto_reset=False, sensors=True):
+        """One step of part k on its stream; ``action`` = the rows of part k (any layout ``VecGame.step`` takes); ``auto_reset`` and
+        ``sensors`` as ``VecGame.step`` (the final buffers' rows of part k are valid on ``stream(k)``)."""
         with self._on(k):
-            self.games[k].step(action, auto_reset=auto_reset)
+            self.games[k].step(action, auto_reset=auto_reset, sensors=sensors)
             if not self._serial:
                 action.record_stream(self.streams[k])
 
-    def step(self, action, auto_reset=False):
-        """One step of every part (``action``: the whole batch's tensor, rows in env order).  Does not join -- see the class text.
+    def step(self, action, auto_reset=False, sensors=True):
+        """One step of every part (``action``: the whole batch's tensor, rows in env order; ``auto_reset`` and ``sensors`` as
+        ``VecGame.step``).  Does not join -- see the class text.
         The part streams wait for what the current stream has been given so far (the producer of ``action``); nothing waits for them."""
         g0 = self.games[0]
         action, enc = g0._encode_action(action, self.n)            # checked / decoded once for the whole batch, then handed over by row range
         self._keep_action = action
         modes = [g._step_mode(auto_reset) for g in self.games]      # (validated before anything is enqueued)
-        cur = torch.cuda.current_stream(self.device)
+        blind = 0 if sensors else abi.FTL_STEP_NO_SENSORS
         base, row = action.data_ptr(), action.element_size() * (2 if enc == abi.FTL_ACTION_BOX2 else 1)
-        if not self._serial:
-            self._ev.record(cur)
-        for g, sh, stream, sptr, (flags, fin) in zip(self.games, self.shards, self.streams, self._stream_ptrs, modes):
-            if self._serial:
-                sptr = C.c_void_p(cur.cuda_stream)
-            else:
-                stream.wait_event(self._ev)
-                action.record_stream(stream)       # (the caller may drop the tensor right away: its memory must outlive the part's read)
-            g._step_final(base + sh.lo * row, enc, flags, fin, sptr)
+        for g, sh, sptr, (flags, fin) in zip(self.games, self.shards, self._part_streams(action), modes):
+            g._step_final(base + sh.lo * row, enc, flags | blind, fin, sptr)
         return self.obs_num, self.lasers, self.reward, self.done, self.status
+
+    def _part_streams(self, action=None):
+        """The ``c_void_p`` stream of every part for one call over the whole batch: the parts' own streams, each made to wait for what
+        the current stream has been given so far and told about ``action`` -- or, while ``kernel_timing`` is on, the current stream."""
+        cur = torch.cuda.current_stream(self.device)
+        if self._serial:
+            return [C.c_void_p(cur.cuda_stream)] * len(self.games)
+        self._ev.record(cur)
+        for stream in self.streams:
+            stream.wait_event(self._ev)
+            if action is not None:
+                action.record_stream(stream)       # (the caller may drop the tensor right away: its memory must outlive the part's read)
+        return self._stream_ptrs
+
+    def scan(self):
+        """``VecGame.scan`` of every part on its stream; does not join, like ``step`` (part k's rows of ``lasers`` / ``policy_obs`` are
+        valid on ``stream(k)``)."""
+        self._need_pool()
+        for g, sptr in zip(self.games, self._part_streams()):
+            g._scan(sptr)
+        return self.lasers
+
+    def rollout(self, actions, gamma=1.0, sensors=True):
+        """``VecGame.rollout`` of every part on its stream (``actions``: the whole batch's ``[T, N, ...]`` tensor; every part reads its
+        rows of it); returns the whole batch's ``(ret, steps, status)``.  Does not join, like ``step``."""
+        self._need_pool()
+        flat, enc, T = self.games[0]._encode_rollout(actions, self.n)
+        self._keep_action = flat
+        if getattr(self, "rollout_ret", None) is None:
+            dev = self.device
+            self.rollout_ret, self.rollout_steps, self.rollout_status = (torch.zeros(self.n, dtype=torch.float64, device=dev), torch.zeros(
+                self.n, dtype=torch.int32, device=dev), torch.zeros(self.n, 3, dtype=torch.uint8, device=dev))
+            for g, sh in zip(self.games, self.shards):
+                g._rollout_outputs((self.rollout_ret[sh.lo:sh.hi], self.rollout_steps[sh.lo:sh.hi], self.rollout_status[sh.lo:sh.hi]))
+        base, row = flat.data_ptr(), flat.element_size() * (2 if enc == abi.FTL_ACTION_BOX2 else 1)
+        for g, sh, sptr in zip(self.games, self.shards, self._part_streams(flat)):
+            g._rollout(base + sh.lo * row, self.n * row, enc, T, gamma, sensors, sptr)
+        return self.rollout_ret, self.rollout_steps, self.rollout_status
 
     def set_episode_queue(self, scen_ids, stream_ids=None, stream_base=0):
         """``VecGame.set_episode_queue`` for the whole batch: the parts share ONE queue -- one head, one table -- so every entry is still

@@ -437,6 +437,44 @@ int ftl_step_encoded(ftl_handle* h, const void* action, int32_t encoding, const 
 int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ftl_outputs* out, const ftl_final_outputs* fin,
                    uint32_t flags, void* stream);
 
+/* ---- sensor scans on demand: step without them, scan without a step -----------------------------------------------------------------
+ * A step is two halves: the frame kernel (plus ftl_tracker1_kernel for the v1 tracker) advances the world -- robots, collisions, tracker,
+ * reward, done, obs_num, target --, then ftl_rays_kernel and ftl_aux_kernel turn the new state into `lasers` and `policy_obs`.  Nothing the
+ * sensor kernels do feeds back into the state: they recompute every row of every history depth from the snapshots the state keeps.
+ *
+ * FTL_STEP_NO_SENSORS (ftl_step / ftl_step_encoded / ftl_step_final, alone or with any one reset flag): no pass of the call -- the step,
+ * the reset pass of same-step / queue / sample, the restart of FTL_STEP_NEXT_RESET -- launches the two sensor kernels; every other launch
+ * is the same.  `lasers` and `policy_obs` are not written and keep what they held (fin->lasers / fin->policy_obs are then copies of those
+ * stale rows); every other output and every state word is bit-identical to the same call without the flag, except that a call that does
+ * not scan cannot raise FTL_ERR_LIDAR_OVERFLOW (the one error bit a sensor kernel sets).
+ *
+ * ftl_scan is the other half: the sensor launches of a step on the current state of all envs and nothing else (no frame kernel, no
+ * regroup).  It writes `lasers` (ray and aux blocks) and `policy_obs` when given -- the other arrays of `out` are checked as for a step
+ * and not touched -- and is asynchronous on `stream`.  ftl_step*(flags | FTL_STEP_NO_SENSORS) followed by ftl_scan leaves outputs and
+ * state as ftl_step*(flags) does (no flags, or FTL_STEP_AUTO_RESET without final buffers); after ftl_unpack_envs it reproduces the
+ * readings the source env had when it was packed.  FTL_E_INVALID: NULL handle / out, output arrays missing; FTL_E_STATE without bound
+ * state / scenarios. */
+#define FTL_STEP_NO_SENSORS 32u
+int ftl_scan(ftl_handle* h, const ftl_outputs* out, void* stream);
+
+/* ftl_rollout: T steps of an open-loop action sequence with one call (planners: clone, roll out, restore, ftl_scan).  actions +
+ * t * step_bytes is the action block of step t in `encoding` (row 0 = env 0 of this handle; the stride lets the parts of a pipelined batch
+ * read their rows of one [T][N] array).  The envs are stepped exactly as T calls of ftl_step_encoded without auto-reset step them
+ * (finished envs stay done and keep simulating); steps 0 .. T-2 run with FTL_STEP_NO_SENSORS, step T-1 scans unless `flags` carries
+ * FTL_STEP_NO_SENSORS -- the only flag accepted.  After every frame launch ftl_rollout_fold_kernel folds out->reward / done / status into
+ * `ro`: an env is alive in step t when its done word was 0 on entry to it (the step that raises done counts, later ones do not), and
+ * ret = ret + disc_t * reward_t over those steps with disc_0 = 1, disc_{t+1} = disc_t * gamma, all in float64, one rounding per
+ * operation.  `out` holds the outputs of step T-1.  FTL_E_INVALID before any device work: NULL pointers (a NULL field of `ro` included),
+ * T <= 0, any other flag, an unknown encoding; FTL_E_STATE without bound state / scenarios. */
+typedef struct ftl_rollout_outputs {  /* DEVICE pointers, every row written */
+    double*  ret;     /* [n]    sum over the steps the env was alive in of disc_t * reward_t */
+    int32_t* steps;   /* [n]    number of such steps: T if the episode never ended, 0 if the env was done on entry */
+    uint8_t* status;  /* [n][3] status row of the step that ended the episode, 0/0/0 if none did */
+} ftl_rollout_outputs;
+size_t ftl_sizeof_rollout_outputs(void);
+int ftl_rollout(ftl_handle* h, const void* actions, int64_t step_bytes, int32_t encoding, int32_t T, double gamma,
+                const ftl_outputs* out, const ftl_rollout_outputs* ro, uint32_t flags, void* stream);
+
 /* ---- episode metrics + error report (ENV:941-944 reports overall_reward / step_count at done) --------
  * Every env slot accumulates, at the step in which an episode ends (done set by this step; under FTL_STEP_AUTO_RESET
  * before the slot is re-initialised), the vector below in its "ep_stats" state field (f64[FTL_N_METRICS] per env).
@@ -467,8 +505,9 @@ int ftl_kernel_times(ftl_handle* h, double* ms, int32_t* n_steps);
 /* ---- batched top-down RGB frames (render(), ENV:1196-1202, layers of _show_tick ENV:1229-1281) --------------------------------
  * ftl_render draws k envs of the handle into rgb[k][height][width][3] (uint8, row-major [y][x][r, g, b]: the reference's
  * np.transpose(pygame.surfarray.array3d(.), (1, 0, 2))).  It reads the state, the scenario pool and the `lasers` output of the last
- * ftl_reset / ftl_step* call on the handle (that buffer must still be alive) and writes nothing but `rgb` and the caller's workspace:
- * a render never changes a later step.  env_ids are env indices of the handle (not slots of its cost-sorted permutation); repeats are
+ * ftl_reset / ftl_step* / ftl_scan / ftl_rollout call on the handle (that buffer must still be alive) and writes nothing but `rgb` and the
+ * caller's workspace: a render never changes a later step.  The SENSORS layer draws the readings of the last scan, which may be older than
+ * the state (FTL_STEP_NO_SENSORS, ftl_unpack_envs).  env_ids are env indices of the handle (not slots of its cost-sorted permutation); repeats are
  * allowed; an id outside [0, n_envs) gives a white frame.  Asynchronous on `stream`.
  *
  * Coverage rules (what a pixel shows).  Output pixel (i, j) samples the world point origin + (i + 0.5, j + 0.5) * scale.  Positions
@@ -556,7 +595,8 @@ int ftl_render(ftl_handle* h, const int32_t* env_ids, int32_t k, const ftl_rende
  * destination's FTL_EI_STREAM word (the copy then draws from the destination's own stream and diverges from its source on the first
  * random draw).  Ids are not range-checked on the device (the caller checks them, as for ftl_reset's scenario indices).  Rejected with
  * FTL_E_INVALID before any device work: k < 0, NULL pointers with k > 0, rows not 16-byte aligned, unknown flag bits; FTL_E_STATE
- * without bound state.  k == 0 does nothing.  Asynchronous on `stream`; the outputs (obs, lasers, ...) are the caller's to copy. */
+ * without bound state.  k == 0 does nothing.  Asynchronous on `stream`; the outputs (obs, lasers, ...) are the caller's to copy
+ * (ftl_scan recomputes `lasers` / `policy_obs` of the unpacked state). */
 #define FTL_ENV_SLOT_STATS 1u  /* also move ep_stats, FTL_EI_EPISODES, FTL_EI_ERROR_STICKY (checkpoints); default: dst keeps its own */
 #define FTL_ENV_OWN_STREAM 2u  /* dst keeps its own random stream instead of the row's */
 size_t   ftl_env_bytes(const ftl_handle* h);
