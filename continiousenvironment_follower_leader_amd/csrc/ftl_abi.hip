@@ -42,6 +42,7 @@ constexpr int kRecOrder[] = {F_env_int, F_fol_cs, F_rb_pos, F_rb_dbl, F_snap_win
 // The environment switches, read once by ftl_create.  -1 = not given: a given 0 / 1 wins over the library's rule and over ftl_tune.
 struct Switches {
     int split, no_regroup, g8, one_pass, defer;                       // FTL_SPLIT, FTL_NO_REGROUP, FTL_DEBUG_G8, FTL_RAYS_ONE_PASS, FTL_DEFER
+    int class_cull;                                                   // FTL_RAYS_CLASS_CULL
     int regroup_every, corr_lds_cap, lds_pad, lds_pad_rays;            // FTL_REGROUP_EVERY, FTL_DEBUG_CORR_LDS_CAP, FTL_DEBUG_LDS_PAD[_RAYS] (0: not given)
     int pair_window;                                                  // FTL_DEBUG_PAIR_WINDOW (0: not given)
     bool print_lds;                                                   // FTL_DEBUG_PRINT_LDS
@@ -51,6 +52,7 @@ Switches read_switches() {
     auto tri = [](const char* name, int other) { const char* v = getenv(name); return !v ? -1 : v[0] == '1' ? 1 : v[0] == '0' ? 0 : other; };
     auto num = [](const char* name, int hi) { const char* v = getenv(name); const int p = v ? atoi(v) : 0; return p < 0 ? 0 : (p > hi ? hi : p); };
     return Switches{tri("FTL_SPLIT", 0), tri("FTL_NO_REGROUP", 0), tri("FTL_DEBUG_G8", 0), tri("FTL_RAYS_ONE_PASS", 1), tri("FTL_DEFER", 1),
+                    tri("FTL_RAYS_CLASS_CULL", 1),
                     num("FTL_REGROUP_EVERY", INT32_MAX), num("FTL_DEBUG_CORR_LDS_CAP", INT32_MAX), num("FTL_DEBUG_LDS_PAD", 48 * 1024),
                     num("FTL_DEBUG_LDS_PAD_RAYS", 48 * 1024), num("FTL_DEBUG_PAIR_WINDOW", FTL_PAIR_CAP), getenv("FTL_DEBUG_PRINT_LDS") != nullptr};
 }
@@ -273,6 +275,15 @@ void report_plan(const ftl_handle* h) {
             r[0], r[1], h->sched.regroup ? "on" : "off", h->rg_every, h->split ? "on" : "off");
     // (a continuation line: the three lines above are parsed as they stand)
     if (h->k_rays[0]) fprintf(stderr, "     ray candidates: %s form on one stream, %s form on two, window %d\n", h->rays[0].mask ? "mask" : "list", h->rays[1].mask ? "mask" : "list", P.pair_window);
+    // (one more per pass that has rays: the reach phase 1 culls each segment class with, in px)
+    if (h->k_rays[0]) for (int which = 0; which < 2; which++) if (P.pass_rays[which] > 0) {
+        char r[4][24];
+        for (int q = 0; q < 4; q++) {
+            if (P.cls_reach[which][q] < 0.0f) snprintf(r[q], sizeof r[q], "none");
+            else snprintf(r[q], sizeof r[q], "%g", (double)P.cls_reach[which][q]);
+        }
+        fprintf(stderr, "     ray cull: pass %d static %s dynamic %s corridor %s green %s\n", which, r[0], r[1], r[2], r[3]);
+    }
 }
 
 }  // namespace
@@ -368,6 +379,18 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
                 }
             }
             P.pass_rays[which] = g - P.pass_base[which];
+            // phase 1's cull per segment class: the longest reach among the pass's sensors that react to the class -- the float32 value
+            // whose square is rs.reach2 above -- or -1: no sensor of the pass sees the class.
+            // FTL_RAYS_CLASS_CULL=0: one box of pass_lmax + 2 for every class (the table before the class cull)
+            for (int q = 0; q < 4; q++) {
+                float reach = -1.0f;
+                for (int k = 0; k < cfg->n_lasers; k++) {
+                    const ftl_laser_cfg& l = cfg->lasers[k];
+                    if ((l.after_tracker ? 1 : 0) != which || l.compas || !((P.ray_sens[k].flags >> q) & 1u)) continue;
+                    reach = fmaxf(reach, (float)l.length + 2.0f);
+                }
+                P.cls_reach[which][q] = h->sw.class_cull != 0 ? reach : P.pass_lmax[which] + 2.0f;
+            }
         }
         // Every shipped config scans all its ray sensors on one side of the tracker: the other pass has nothing to do, and the kernels
         // compiled without the loop over the passes run the one that has.  FTL_RAYS_ONE_PASS=0/1 overrides (1 is the default where it applies).

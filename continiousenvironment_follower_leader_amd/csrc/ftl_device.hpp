@@ -57,6 +57,10 @@ struct FtlDevParams {
     int32_t n_envs, R, lasers_len, total_rays, hmax, lds_rays;
     int32_t pass_rays[2], pass_base[2];   // rays of the sensors scanned before / after the tracker, and where they start in ray_dir
     float pass_lmax[2];               // longest laser_length of the pass (float32)
+    // phase 1 of the ray kernel culls each segment class (SEG_STATIC / DYNAMIC / CORRIDOR / GREEN) by the sensors of the pass that react to it:
+    // the longest (float)length + 2 among them, or -1 where no sensor of the pass sees the class (nothing of it is pushed).
+    // FTL_RAYS_CLASS_CULL=0: pass_lmax + 2 for every class.  (32 bytes: ray_dir below stays on its 32-byte boundary)
+    float cls_reach[2][4];
     int32_t pass_single;              // the only pass that has rays (0 / 1), or -1 when both have: what the ONE_PASS ray kernels run
     int32_t pair_window;              // mask form of phase 3: pairs per window of a chunk's candidate list (FTL_PAIR_CAP; FTL_DEBUG_PAIR_WINDOW
                                       // makes it smaller).  (Also keeps ray_dir below on a 32-byte boundary: static_assert behind the struct)
@@ -559,7 +563,9 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
         const int lane = lane_v;
         const int n_rays = P.pass_rays[which], pbase = P.pass_base[which];      // the rays of the pass's sensors share one index space
         if (n_rays == 0) continue;
-        const float lmax = P.pass_lmax[which];
+        // reach of the pass's sensors per segment class (host-built; < 0: no sensor of the pass sees the class)
+        const float rch_st = P.cls_reach[which][SEG_STATIC], rch_dy = P.cls_reach[which][SEG_DYNAMIC];
+        const float rch_co = P.cls_reach[which][SEG_CORRIDOR], rch_gr = P.cls_reach[which][SEG_GREEN];
         // this lane's snapshot rect and static rect: requested here, with the pass's other loads, and dead after phase 1 (held across
         // the passes they cost the test loop of phase 3 eight registers)
         // (with room for both in one wavefront -- 37 + 10 lanes on the bench workload -- the snapshot rects sit in the lanes behind the
@@ -604,7 +610,10 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
         // global memory, uncompacted (same values, same results).
         const bool staged = !CAPPED || umax - umin <= P.corr_lds_cap;
         auto corr_f32 = [&](int p) { return *corr32_slot(P, env, p); };
-        if (staged) for (int p = umin + lane; p < umax; p += FTL_WAVE) s_corr[p & cmask] = corr_f32(p);
+        // (a pass in which no sensor reacts to the corridor or to the green zone -- config D's -- stages nothing: no global round trip
+        // here.  The barrier stays, it also puts the zeroed counters before phase 1's atomics)
+        const bool ring_seen = !(rch_co < 0.0f) || !(rch_gr < 0.0f);
+        if (staged && ring_seen) for (int p = umin + lane; p < umax; p += FTL_WAVE) s_corr[p & cmask] = corr_f32(p);
         __syncthreads();
         FTL_RTIC(0);
 #if defined(FTL_RAYS_STOP) && FTL_RAYS_STOP == 1
@@ -612,17 +621,19 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
 #endif
 
         // ---- phase 1: culled, compacted segment table; sources flattened: statics | snapshot rects | corridor points | caps
-        const float reach = lmax + 2.0f;
-        const float bx0 = cx - reach, bx1 = cx + reach, by0 = cy - reach, by1 = cy + reach;
+        // Every class is culled against the box of its own reach around the follower -- the longest laser (+ 2 px) among the sensors that
+        // see the class, not the pass's longest.  Exact: what is dropped here, phase 3 (dmin2 > reach2) drops for every sensor that reacts
+        // to the class.
         // Only the edges that FACE the follower go to the work list.  A ray that reaches a back-facing edge of an axis-aligned rect
         // has entered the rect through a facing edge at a smaller distance, and the reference's own test detects that entry unless the
         // ray passes within rounding (~1e-13 px: the float32 orientation test of an axis-aligned edge is an exact sign test, the
         // others are float64) of a corner -- so the minimum over the facing edges IS the reference's minimum over all four.  A
         // follower inside or on the rect keeps all four.
         auto push_rect = [&](int cls, int4 q, unsigned sm) {
-            if (sm == 0u) return;
+            const float reach = cls == SEG_STATIC ? rch_st : rch_dy;
+            if (sm == 0u || reach < 0.0f) return;
             const float l = (float)q.x, t = (float)q.y, r = (float)(q.x + q.z), b = (float)(q.y + q.w);
-            if (r < bx0 || l > bx1 || b < by0 || t > by1) return;
+            if (r < cx - reach || l > cx + reach || b < cy - reach || t > cy + reach) return;
             const int slot = (cls == SEG_STATIC ? 0 : cap_rs) + atomicAdd(&s_cnt[cls], 1);
             s_rect[slot] = q; s_rmask[slot] = sm;
             unsigned em = (cy > b ? 1u : 0u) | (cx > r ? 2u : 0u) | (cy < t ? 4u : 0u) | (cx < l ? 8u : 0u);      // edge order of sensors.py:668-671
@@ -632,15 +643,16 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
         };
         // both ends beyond one side of the reach box.  Plain comparisons: fminf / fmaxf first quiet a NaN in each operand (a v_max_f32 of
         // the value with itself), and these are finite coordinates from LDS
-        auto outside_box = [&](float ax, float ay, float bx, float by) {
+        auto outside_box = [&](float reach, float ax, float ay, float bx, float by) {
+            const float bx0 = cx - reach, bx1 = cx + reach, by0 = cy - reach, by1 = cy + reach;
             return (ax < bx0 && bx < bx0) || (ax > bx1 && bx > bx1) || (ay < by0 && by < by0) || (ay > by1 && by > by1);
         };
         auto push_corr = [&](int p, int side, float ax, float ay, float bx, float by, unsigned sm) {
-            if (outside_box(ax, ay, bx, by)) return;
+            if (outside_box(rch_co, ax, ay, bx, by)) return;
             s_cref[atomicAdd(&s_cnt[SEG_CORRIDOR], 1)] = (unsigned)(p & cmask) | ((unsigned)side << 15) | (sm << 16);
         };
         auto push_green = [&](float ax, float ay, float bx, float by, unsigned sm) {
-            if (outside_box(ax, ay, bx, by)) return;
+            if (outside_box(rch_gr, ax, ay, bx, by)) return;
             int at = atomicAdd(&s_cnt[SEG_GREEN], 1);
             s_green[at] = make_float4(ax, ay, bx, by); s_gmask[at] = sm;
         };
@@ -660,7 +672,8 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
                 push_rect(o == 0 ? SEG_STATIC : SEG_DYNAMIC, dynq, sm_dyn);
             }
             // corridor polylines: segment p -> p+1 belongs to every snapshot whose window holds both points
-            if (staged) for (int p = umin + lane; p < umax - 1; p += FTL_WAVE) {
+            if (rch_co < 0.0f) { }                              // nobody sees the corridor: its count stays 0
+            else if (staged) for (int p = umin + lane; p < umax - 1; p += FTL_WAVE) {
                 unsigned sm = 0;
 #pragma unroll
                 for (int a = 0; a < HM; a++) if (a < nsnap && win_lo[a] <= p && p + 1 < win_hi[a]) sm |= 1u << a;
@@ -671,7 +684,7 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_RAYS_WPE) ftl_rays_kernel(const 
                 }
             }
             else if (lane == 0) s_cnt[SEG_CORRIDOR] = 2 * max(umax - umin - 1, 0);      // every segment of the span, culled where it is fetched
-            if (lane < nsnap) {     // green-zone end caps of snapshot age `lane` (sensors.py:648-650)
+            if (lane < nsnap && !(rch_gr < 0.0f)) {     // green-zone end caps of snapshot age `lane` (sensors.py:648-650)
                 int lo = 0, hi = 0;
 #pragma unroll
                 for (int j = 0; j < HM; j++) if (j == lane) { lo = win_lo[j]; hi = win_hi[j]; }
