@@ -23,6 +23,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_queue.hpp"),
            os.path.join(_PKG, "csrc", "ftl_sampler.hpp"),
            os.path.join(_PKG, "csrc", "ftl_rollout.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_baseline.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
 # translation units: the device code + C-ABI, and the host-only scenario generator (reset-time, no GPU code)
 UNITS = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp")]
@@ -86,6 +87,13 @@ def load():
     lib.ftl_sizeof_rollout_outputs.restype = C.c_size_t
     lib.ftl_rollout.argtypes = [vp, vp, C.c_int64, i32, i32, C.c_double, C.POINTER(abi.Outputs), C.POINTER(abi.RolloutOutputs), u32, vp]
     lib.ftl_rollout.restype = C.c_int
+    lib.ftl_baseline_bytes.argtypes = [vp, i32]
+    lib.ftl_baseline_bytes.restype = C.c_size_t
+    lib.ftl_baseline_act.argtypes = [vp, C.POINTER(abi.Outputs), vp, C.c_size_t, i32, vp, vp]
+    lib.ftl_baseline_act.restype = C.c_int
+    lib.ftl_rollout_baseline.argtypes = [vp, i32, C.c_double, C.POINTER(abi.Outputs), C.POINTER(abi.RolloutOutputs), vp, C.c_size_t, i32,
+                                         vp, C.c_int64, u32, vp]
+    lib.ftl_rollout_baseline.restype = C.c_int
     lib.ftl_kernel_timing.argtypes = [vp, i32]
     lib.ftl_kernel_times.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(i32)]
     lib.ftl_episode_metrics.argtypes = [vp, vp, vp, u32, vp]
@@ -152,6 +160,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_sizeof_episode_record", "ftl_sizeof_episode_queue", "ftl_set_episode_queue", "ftl_queue_start",
            "ftl_sizeof_scenario_sampler", "ftl_set_scenario_sampler", "ftl_sampler_refresh", "ftl_sampler_start",
            "ftl_scan", "ftl_sizeof_rollout_outputs", "ftl_rollout",
+           "ftl_baseline_bytes", "ftl_baseline_act", "ftl_rollout_baseline",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

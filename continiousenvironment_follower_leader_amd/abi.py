@@ -31,6 +31,14 @@ FTL_STEP_QUEUE_RESET = 8
 FTL_STEP_SAMPLE_RESET = 16
 FTL_STEP_NO_SENSORS = 32          # no sensor kernels in this call: lasers / policy_obs keep what they held (ftl_scan refreshes them)
 FTL_EPISODE_DONE_AT_RESET = 1
+# the baseline follower (include/ftl.h, ftl_baseline_act): sticky bits of a row's flags word, the row's header and size
+FTL_BL_EMPTY, FTL_BL_OVERFLOW = 1, 2
+BL_HEAD, BL_COUNT, BL_PENDING, BL_FLAGS = range(4)
+
+
+def baseline_row_bytes(cap):
+    """Bytes of one follower row: int32 {head, count, pending, flags} + ``cap`` points of two float64."""
+    return 16 + 16 * int(cap)
 # columns of a scenario sampler's table (include/ftl.h, ftl_scenario_sampler)
 FTL_N_SCEN_STATS = 10
 (SS_EPISODES, SS_FRAMES_SUM, SS_SUCCESS, SS_CRASH, SS_LOW_REWARD, SS_TOO_FAR, SS_TIMEOUT, SS_RETURN_Q16, SS_DONE_AT_RESET,

@@ -107,6 +107,7 @@ struct ftl_handle {
     FtlAttached<ftl_scenario_sampler> sampler;    // ftl_set_scenario_sampler
     FtlRestartScratch rs;    // what a queue or sampler call hands to the reset pass (library-owned, allocated by the first such call: ftl_restart.hpp)
     uint8_t* ro_alive;       // [n_envs] "the episode was running on entry to the step" of ftl_rollout (library-owned, allocated by the first rollout: ftl_rollout.hpp)
+    double* bl_action;       // [n_envs][2] the actions of ftl_rollout_baseline when the caller keeps no record (library-owned, allocated on first use: ftl_baseline.hpp)
 };
 
 namespace {
@@ -467,9 +468,10 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
 
 void ftl_destroy(ftl_handle* h) {
     if (!h) return;
-    if (h->dP || h->rg_mem || h->side || h->mt_mem || h->rs.scen_idx || h->ro_alive) (void)hipSetDevice(h->device);
+    if (h->dP || h->rg_mem || h->side || h->mt_mem || h->rs.scen_idx || h->ro_alive || h->bl_action) (void)hipSetDevice(h->device);
     if (h->rs.scen_idx) (void)hipFree(h->rs.scen_idx);
     if (h->ro_alive) (void)hipFree(h->ro_alive);
+    if (h->bl_action) (void)hipFree(h->bl_action);
     if (h->dP) (void)hipFree(h->dP);
     if (h->mt_mem) (void)hipFree(h->mt_mem);
     for (hipEvent_t ev : h->tev) (void)hipEventDestroy(ev);
@@ -808,6 +810,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 #include "ftl_render.hpp"        // batched top-down RGB frames (ftl_render), same translation unit
 #include "ftl_snapshot.hpp"      // snapshot / clone / restore of env rows (ftl_pack_envs, ftl_unpack_envs), same translation unit
 #include "ftl_rollout.hpp"       // T blind steps of an action sequence and their discounted return (ftl_rollout), same translation unit
+#include "ftl_baseline.hpp"      // the reference's way-point chase as a policy and as closed-loop rollouts (ftl_baseline_act, ftl_rollout_baseline), same translation unit
 
 #ifdef FTL_WAVE_TIMES
 extern "C" int ftl_debug_wave_timeline(unsigned long long* times, unsigned int* info) {

@@ -271,6 +271,17 @@ class _BatchBase:
         finally:
             self.set_episode_queue(None)
 
+    def rollout_baseline(self, follower, T, gamma=1.0, sensors=True, record=False):
+        """``T`` closed-loop steps of the reference's baseline controller with one call and no host round trip (``ftl_rollout_baseline``):
+        ``rollout`` with the action of every step decided on the stream by ``follower`` (a ``baseline.BaselineFollower`` of this batch)
+        from the observation the step before it wrote -- so the outputs must hold the observation of the current state (the last reset /
+        step / rollout wrote them).  Returns ``(ret, steps, status)`` as ``rollout`` does, plus with ``record=True`` the float64
+        ``[T, N, 2]`` actions that were played.  Bit-identical to ``T`` times ``follower.act()`` + ``step(sensors=False; the last one as
+        asked)``, and in env state and returns to ``rollout`` on the recorded actions.  Does not join a pipelined batch, like ``step``."""
+        if getattr(follower, "batch", None) is not self:
+            raise ValueError("rollout_baseline() takes a BaselineFollower of this batch")
+        return follower.rollout(T, gamma, sensors, record)
+
     def terminated_truncated(self):
         """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
         truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap
@@ -582,6 +593,9 @@ class VecGame(_BatchBase):
             ro.ret, ro.steps, ro.status = (t.data_ptr() for t in views)
             self._ro = ro
         return self._ro
+
+    def _prepare_rollout_outputs(self):
+        self._rollout_outputs()
 
     def _rollout(self, action_ptr, step_bytes, enc, T, gamma, sensors, stream):
         """The one call of ``ftl_rollout``: ``action_ptr`` the device address of this batch's first action row of step 0."""
@@ -1307,16 +1321,20 @@ class PipelinedVecGame(_BatchBase):
         self._need_pool()
         flat, enc, T = self.games[0]._encode_rollout(actions, self.n)
         self._keep_action = flat
+        self._prepare_rollout_outputs()
+        base, row = flat.data_ptr(), flat.element_size() * (2 if enc == abi.FTL_ACTION_BOX2 else 1)
+        for g, sh, sptr in zip(self.games, self.shards, self._part_streams(flat)):
+            g._rollout(base + sh.lo * row, self.n * row, enc, T, gamma, sensors, sptr)
+        return self.rollout_ret, self.rollout_steps, self.rollout_status
+
+    def _prepare_rollout_outputs(self):
+        """The whole batch's ``rollout_ret`` / ``_steps`` / ``_status``, allocated on first use; every part takes its rows."""
         if getattr(self, "rollout_ret", None) is None:
             dev = self.device
             self.rollout_ret, self.rollout_steps, self.rollout_status = (torch.zeros(self.n, dtype=torch.float64, device=dev), torch.zeros(
                 self.n, dtype=torch.int32, device=dev), torch.zeros(self.n, 3, dtype=torch.uint8, device=dev))
             for g, sh in zip(self.games, self.shards):
                 g._rollout_outputs((self.rollout_ret[sh.lo:sh.hi], self.rollout_steps[sh.lo:sh.hi], self.rollout_status[sh.lo:sh.hi]))
-        base, row = flat.data_ptr(), flat.element_size() * (2 if enc == abi.FTL_ACTION_BOX2 else 1)
-        for g, sh, sptr in zip(self.games, self.shards, self._part_streams(flat)):
-            g._rollout(base + sh.lo * row, self.n * row, enc, T, gamma, sensors, sptr)
-        return self.rollout_ret, self.rollout_steps, self.rollout_status
 
     def set_episode_queue(self, scen_ids, stream_ids=None, stream_base=0):
         """``VecGame.set_episode_queue`` for the whole batch: the parts share ONE queue -- one head, one table -- so every entry is still

@@ -475,6 +475,55 @@ size_t ftl_sizeof_rollout_outputs(void);
 int ftl_rollout(ftl_handle* h, const void* actions, int64_t step_bytes, int32_t encoding, int32_t T, double gamma,
                 const ftl_outputs* out, const ftl_rollout_outputs* ro, uint32_t flags, void* stream);
 
+/* ---- baseline follower: the reference's way-point chase as a policy and as closed-loop rollouts -------------------------------------
+ * run_2d.py --mode base (lines 109-151) drives the follower with MISC:65-95 (move_to_the_point) along a FIFO of the leader's target points.
+ * Here the FIFO of every env lives in caller-owned DEVICE memory `bl`: n_envs rows of 16 + 16 * cap bytes, row e =
+ * int32 {head, count, pending, flags} followed by cap points of two doubles used as a ring (front = point head, indices modulo cap).  A
+ * row is self-contained -- copying row i to row j moves a follower, so followers can be cloned with their envs -- and a zeroed buffer is a
+ * valid fresh state.  cap >= 2; `bl` 8-byte aligned.
+ *
+ * ftl_baseline_act (ftl_baseline_kernel, one thread per env, asynchronous on `stream`) reads what the last reset / step wrote to `out`
+ * (obs_num[5], [6], [8] and target) and the env's step word, and per env:
+ *   new episode   env_int[FTL_EI_STEP_COUNT] == 0 -- the env's rows of `out` are a reset observation, under every reset discipline, since
+ *                 every step advances the word by at least one frame -- or count == 0 (zeroed row): FIFO = [target], pending cleared.
+ *                 This is the only restart rule; there is no mask.
+ *   otherwise     the bookkeeping of the step just taken, in the reference's order (run_2d.py:141-145): if target differs from the FIFO's
+ *                 back (either coordinate, double ==, as np.array_equal) it is appended; then, if the previous decision left a pending
+ *                 pop, the front is popped.
+ *   decision      pos = (double)obs_num[5], [6]; cur = (int)obs_num[8]; desirable = (int)angle_to_point(pos, front) (MISC:16-26, the
+ *                 float64 operation sequence of the frame kernel); delta_turn and the sign by the four branches of MISC:73-91;
+ *                 action = (v, (double)(delta_turn * sign) / 10.0) with v = the euclidean distance pos -> front; pending = v <= 20.0.
+ *                 The env clips the action as it clips any Box(2) action.
+ * Two places where the reference cannot go on get a rule and a sticky bit in the row's flags word (no env error bit):
+ *   FTL_BL_EMPTY     a pop that would empty the FIFO is not made, the follower keeps its last point (the reference raises IndexError on
+ *                    its next iteration);
+ *   FTL_BL_OVERFLOW  an append to a full FIFO drops the front (the reference's list is unbounded).
+ * v: the reference's distance.euclidean is BLAS dnrm2 in x87 extended precision rounded to double; the device returns the correctly
+ * rounded sqrt(dx^2 + dy^2) of the float64 differences (exact squares and sum, one final rounding).  A double rounding of the x87 path
+ * can sit one ulp away (about 2^-12 of random inputs; counted in tests/test_baseline_host.py).  v matters to the env only below the
+ * follower's max speed, i.e. within a few px of a point that is popped at 20 px.
+ *
+ * ftl_rollout_baseline is ftl_rollout with the action of step t produced on the stream: for t = 0 .. T-1 the act kernel, a step without
+ * auto-reset (FTL_STEP_NO_SENSORS for t < T-1, `flags` -- FTL_STEP_NO_SENSORS or 0 -- for the last) and ftl_rollout_fold_kernel; a
+ * two-stream handle is handled as ftl_rollout handles it.  actions == NULL: the actions go to an [n][2] scratch the handle owns;
+ * otherwise block t is written at actions + t * step_bytes -- the record of what was played.  Precondition: `out` holds the observation
+ * of the current state (the last reset / step / rollout on the handle wrote it).  It is bit-identical -- `out`, `ro`, every state byte,
+ * every follower row -- to T iterations of ftl_baseline_act + ftl_step_encoded(FTL_ACTION_BOX2) + fold, and its env state and `ro` are
+ * those of ftl_rollout on the recorded actions.
+ * FTL_E_INVALID before any device work: NULL pointers, cap < 2, bl_bytes below ftl_baseline_bytes, `bl` not 8-byte aligned, T <= 0, any
+ * flag but FTL_STEP_NO_SENSORS, step_bytes below one block when `actions` is given; FTL_E_STATE without bound state / scenarios.  The
+ * action is Box(2): a config with discrete_action_space or constant_follower_speed decodes another encoding and has no use for it
+ * (the Python wrapper refuses such a config). */
+#define FTL_BL_EMPTY 1u
+#define FTL_BL_OVERFLOW 2u
+size_t ftl_baseline_bytes(const ftl_handle* h, int32_t cap);      /* n_envs rows of 16 + 16 * cap bytes; no device access; 0 on a NULL handle or cap < 2 */
+int ftl_baseline_act(ftl_handle* h, const ftl_outputs* out, void* bl, size_t bl_bytes, int32_t cap,
+                     double* action /* [n][2] */, void* stream);
+int ftl_rollout_baseline(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                         void* bl, size_t bl_bytes, int32_t cap,
+                         double* actions /* [T] blocks of [n][2], or NULL */, int64_t step_bytes,
+                         uint32_t flags /* FTL_STEP_NO_SENSORS only */, void* stream);
+
 /* ---- episode metrics + error report (ENV:941-944 reports overall_reward / step_count at done) --------
  * Every env slot accumulates, at the step in which an episode ends (done set by this step; under FTL_STEP_AUTO_RESET
  * before the slot is re-initialised), the vector below in its "ep_stats" state field (f64[FTL_N_METRICS] per env).
