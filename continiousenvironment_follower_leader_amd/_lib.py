@@ -24,6 +24,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_sampler.hpp"),
            os.path.join(_PKG, "csrc", "ftl_rollout.hpp"),
            os.path.join(_PKG, "csrc", "ftl_baseline.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_search.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
 # translation units: the device code + C-ABI, and the host-only scenario generator (reset-time, no GPU code)
 UNITS = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc", "ftl_scenario.cpp")]
@@ -120,6 +121,18 @@ def load():
     lib.ftl_pack_envs.restype = C.c_int
     lib.ftl_unpack_envs.argtypes = [vp, vp, vp, i32, u32, vp]
     lib.ftl_unpack_envs.restype = C.c_int
+    lib.ftl_unpack_envs_from.argtypes = [vp, vp, vp, vp, i32, u32, vp]
+    lib.ftl_unpack_envs_from.restype = C.c_int
+    lib.ftl_sizeof_search_params.restype = C.c_size_t
+    lib.ftl_sizeof_search_buffers.restype = C.c_size_t
+    lib.ftl_search_begin.argtypes = [vp, vp, i32, i32, C.c_uint64, i32, vp, vp]
+    lib.ftl_search_begin.restype = C.c_int
+    lib.ftl_search_sample.argtypes = [vp, vp, i32, C.POINTER(abi.SearchParams), C.c_uint64, i32, C.c_double, vp, vp, vp]
+    lib.ftl_search_sample.restype = C.c_int
+    lib.ftl_search_select.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.ftl_search_select.restype = C.c_int
+    lib.ftl_search.argtypes = [vp, vp, C.POINTER(abi.SearchParams), C.c_uint64, i32, C.POINTER(abi.SearchBuffers), vp]
+    lib.ftl_search.restype = C.c_int
     lib.ftl_sizeof_episode_record.restype = C.c_size_t
     lib.ftl_sizeof_episode_queue.restype = C.c_size_t
     lib.ftl_set_episode_queue.argtypes = [vp, C.POINTER(abi.EpisodeQueueC)]
@@ -161,6 +174,8 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_sizeof_scenario_sampler", "ftl_set_scenario_sampler", "ftl_sampler_refresh", "ftl_sampler_start",
            "ftl_scan", "ftl_sizeof_rollout_outputs", "ftl_rollout",
            "ftl_baseline_bytes", "ftl_baseline_act", "ftl_rollout_baseline",
+           "ftl_unpack_envs_from", "ftl_sizeof_search_params", "ftl_sizeof_search_buffers", "ftl_search_begin", "ftl_search_sample",
+           "ftl_search_select", "ftl_search",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -144,6 +144,12 @@ def uniform01(rng_seed, env_id, resets, frame):
     return (mix64(key + 0x9E3779B97F4A7C15 * (frame + 1)) >> 11) * (1.0 / 9007199254740992.0)
 
 
+def search_uniform(seed, stream_id, call, it, k, block, j):
+    """Python twin of ftl_search_uniform() in include/ftl.h: coordinate ``j`` of hold block ``block`` of candidate ``k`` in round ``it`` of
+    search call ``call`` of the env on absolute stream ``stream_id`` (key range bit 43 of the ``uniform01`` stream)."""
+    return uniform01(seed, stream_id, call, (1 << 43) | block | (j << 16) | (it << 17) | (k << 24))
+
+
 def mulhi64(a, b):
     return ((a & _M64) * (b & _M64)) >> 64
 
@@ -209,6 +215,23 @@ class FinalOutputs(C.Structure):
 class RolloutOutputs(C.Structure):
     """ftl_rollout_outputs: discounted return, alive steps and terminal status row per env of ftl_rollout."""
     _fields_ = [("ret", C.c_void_p), ("steps", C.c_void_p), ("status", C.c_void_p)]
+
+
+FTL_SEARCH_OWN_STREAM = 1
+
+
+class SearchParams(C.Structure):
+    """ftl_search_params: candidates per env, horizon, hold, rounds; discount, radius and its decay; seed; flags."""
+    _fields_ = [("K", C.c_int32), ("T", C.c_int32), ("hold", C.c_int32), ("iters", C.c_int32),
+                ("gamma", C.c_double), ("spread", C.c_double), ("decay", C.c_double), ("seed", C.c_uint64),
+                ("flags", C.c_uint32), ("_pad", C.c_int32)]
+
+
+class SearchBuffers(C.Structure):
+    """ftl_search_buffers: the device buffers of one ftl_search call (``search.ActionSearch`` owns them)."""
+    _fields_ = [("rows", C.c_void_p), ("row_ids", C.c_void_p), ("env_ids", C.c_void_p), ("nominal", C.c_void_p), ("cand", C.c_void_p),
+                ("action", C.c_void_p), ("best_k", C.c_void_p), ("best_ret", C.c_void_p), ("out", C.POINTER(Outputs)),
+                ("ro", C.POINTER(RolloutOutputs))]
 
 
 class EpisodeRecord(C.Structure):

@@ -1,4 +1,4 @@
-// ftl_snapshot.hpp -- snapshot / clone / restore of env states (include/ftl.h: ftl_env_bytes .. ftl_unpack_envs).  Included at the end of
+// ftl_snapshot.hpp -- snapshot / clone / restore of env states (include/ftl.h: ftl_env_bytes .. ftl_unpack_envs_from).  Included at the end of
 // ftl_abi.hip (same translation unit: it reads the handle's field table).
 //
 // One kernel, templated on the direction, moves env rows between the state buffer and a dense [k][env_bytes] row buffer.  An env is a
@@ -28,6 +28,7 @@ struct Args {
     unsigned char* blob;            // the bound state buffer
     unsigned char* rows;            // [k][row_bytes]
     const int32_t* ids;             // [k] env indices of the handle
+    const int32_t* row_ids;         // unpack: [k] env ids[i] takes row row_ids[i] (ftl_unpack_envs_from), or null: row i
     unsigned long long row_bytes;
     int32_t k, nseg, row16, env_id_base;
     uint32_t flags;                 // FTL_ENV_* (unpack)
@@ -62,7 +63,8 @@ template <bool UNPACK>
 __global__ __launch_bounds__(FTL_SNAP_THREADS) void ftl_snapshot_kernel(Args a) {
     const int i = blockIdx.x;                                  // row i of the buffer <-> env a.ids[i]
     const int env = a.ids[i];
-    unsigned char* row = a.rows + (size_t)i * a.row_bytes;
+    const int ri = (UNPACK && a.row_ids) ? a.row_ids[i] : i;
+    unsigned char* row = a.rows + (size_t)ri * a.row_bytes;
     const uint32_t c0 = blockIdx.y * (FTL_SNAP_THREADS * FTL_SNAP_UNROLL) + threadIdx.x;
     uint4 v[FTL_SNAP_UNROLL];
 #pragma unroll
@@ -201,13 +203,18 @@ int ftl_pack_envs(const ftl_handle* h, const int32_t* env_ids, int32_t k, void* 
     return ftls::snap_launch(h, a, false, stream);
 }
 
-int ftl_unpack_envs(ftl_handle* h, const void* rows, const int32_t* env_ids, int32_t k, uint32_t flags, void* stream) {
+int ftl_unpack_envs_from(ftl_handle* h, const void* rows, const int32_t* row_ids, const int32_t* env_ids, int32_t k, uint32_t flags, void* stream) {
     int rc = ftls::snap_check(h, env_ids, k, rows, flags);
     if (rc || k == 0) return rc;
     ftls::Args a = ftls::make_args(h);
-    a.blob = (unsigned char*)h->P.env_int - h->fields[F_env_int].offset; a.rows = (unsigned char*)rows; a.ids = env_ids; a.k = k; a.flags = flags;
+    a.blob = (unsigned char*)h->P.env_int - h->fields[F_env_int].offset; a.rows = (unsigned char*)rows; a.ids = env_ids; a.row_ids = row_ids; a.k = k;
+    a.flags = flags;
     if (flags & FTL_ENV_SLOT_STATS) a.skip_seg = -1;
     return ftls::snap_launch(h, a, true, stream);
+}
+
+int ftl_unpack_envs(ftl_handle* h, const void* rows, const int32_t* env_ids, int32_t k, uint32_t flags, void* stream) {
+    return ftl_unpack_envs_from(h, rows, nullptr, env_ids, k, flags, stream);
 }
 
 }  // extern "C"

@@ -652,6 +652,88 @@ size_t   ftl_env_bytes(const ftl_handle* h);
 uint64_t ftl_env_layout_id(const ftl_handle* h);
 int ftl_pack_envs(const ftl_handle* h, const int32_t* env_ids, int32_t k, void* rows, void* stream);
 int ftl_unpack_envs(ftl_handle* h, const void* rows, const int32_t* env_ids, int32_t k, uint32_t flags, void* stream);
+/* ftl_unpack_envs with rows[row_ids[i]] in place of rows[i] (row_ids [k] DEVICE, repeats allowed, not range-checked): one packed row fanned
+ * out into many slots without a k-row copy of it.  row_ids == NULL is ftl_unpack_envs (the same kernel). */
+int ftl_unpack_envs_from(ftl_handle* h, const void* rows, const int32_t* row_ids, const int32_t* env_ids, int32_t k, uint32_t flags,
+                         void* stream);
+
+/* ---- action search: K candidate action sequences per env, rolled out on clones, the best one kept (random shooting with a shrinking
+ * radius) ------------------------------------------------------------------------------------------------------------------------------
+ * Two handles with equal ftl_env_layout_id on one device, used on one stream, with the same scenario pool loaded: the REAL handle of n
+ * envs and the SEARCH handle of n * K envs, whose env e * K + k is candidate k of real env e.  One ftl_search call is enqueued on `stream`
+ * without a host synchronisation:
+ *   1. ftl_pack_envs of the n real envs (b->env_ids[0 .. n)) into b->rows.
+ *   2. begin (ftl_search_begin_kernel, one thread per env): if word FTL_EI_STEP_COUNT of the env's row is 0 (a new episode: the baseline
+ *      follower's rule), or call == 0, or warm == 0, nominal[t][e] = (follower.max_speed, 0.0) for every t; otherwise nominal[t][e] =
+ *      nominal[t + 1][e] for t < T - 1 and the last step is kept (the plan of the last call, one step later).
+ *   3. for it = 0 .. iters - 1, with the radius s_0 = spread, s_{it+1} = s_it * decay (host, float64):
+ *      sample  (ftl_search_sample_kernel, one thread per (t, clone)): cand[t][e * K][j] = nominal[t][e][j] exactly (candidate 0 is the
+ *              incumbent); for k > 0 x = nominal[t][e][j] + (s * (u - 0.5)) * (hi_j - lo_j), cand = fmin(fmax(x, lo_j), hi_j) with
+ *              u = ftl_search_uniform(p->seed, stream_e, call, it, k, t / hold, j) and (lo, hi) the Box(2) bounds of ENV:374-378:
+ *              (follower.min_speed, -follower.max_rotation_speed), (follower.max_speed, follower.max_rotation_speed).  Float64, this
+ *              operation order, one rounding per operation.  stream_e is the ABSOLUTE stream id the row carries at FTL_EI_STREAM, so the
+ *              candidates follow an env through clone, restore and re-sharding and do not depend on its slot.
+ *      fan-out ftl_unpack_envs_from(search, rows, row_ids, env_ids, n * K, FTL_ENV_OWN_STREAM under FTL_SEARCH_OWN_STREAM else 0).
+ *      rollout ftl_rollout(search, cand, ..., FTL_ACTION_BOX2, T, gamma, FTL_STEP_NO_SENSORS) into b->ro: ret[n * K].
+ *      select  (ftl_search_select_kernel, one wavefront per env): k* = the candidate with the largest ret, the lowest k among equals (-0.0
+ *              equals 0.0); best_k[e] = k*, best_ret[e] = ret[e * K + k*], nominal[t][e] = cand[t][e * K + k*] for every t.  ret is
+ *              assumed free of NaN.
+ *   4. action[e] = nominal[0][e] (a device copy).
+ * Buffers (ftl_search_buffers; all DEVICE memory the caller owns, alive until the stream has passed the call): rows [n][ftl_env_bytes],
+ * 16-byte aligned; row_ids / env_ids [n * K] int32, filled by the CALLER with row_ids[i] = i / K and env_ids[i] = i and only read here;
+ * nominal [T][n][2], cand [T][n * K][2], action [n][2], best_ret [n] float64; best_k [n] int32; out / ro: the search handle's step and
+ * rollout outputs.  nominal carries the plan from call to call; everything else is scratch or result.
+ * Properties:
+ *   - The real handle is only read (the one ftl_pack_envs): its state and outputs are byte-identical before and after.
+ *   - Without FTL_SEARCH_OWN_STREAM a clone keeps its source's random stream, so it is the real env's exact future under the same actions:
+ *     best_ret is non-decreasing over the rounds of a call (candidate 0 is the incumbent), and ftl_rollout of `nominal` on the real handle
+ *     returns best_ret bit for bit.  It also means that the search SEES THE FUTURE random draws of the env (the leader's speed regime
+ *     draws, random frames per step, bear way-points): it plans against the world as it will be, not as a model of it.
+ *     FTL_SEARCH_OWN_STREAM is the honest-model switch: every clone draws from its own slot's stream, best_ret is an estimate, and
+ *     neither property above holds.
+ *   - A real env that is done on entry gives ret = 0 for every clone, hence best_k = 0 and the nominal action.
+ *   - Limits of the draw key: T / hold < 65536, iters < 128, K < 2^19.
+ * FTL_E_INVALID before any device work: NULL pointers (any field of b, out, ro), K / T / hold / iters < 1 or beyond the limits, spread or
+ * decay outside (0, 1], gamma not finite, unknown flag bits, layout ids that differ, devices that differ, search handle size != n * K,
+ * n * K beyond INT32_MAX, rows / nominal / cand not 16-byte aligned; FTL_E_STATE: no bound state or no scenario pool on either handle.
+ * ftl_search_begin / _sample / _select are the three kernels on plain buffers (the pieces of the sequence above, for callers with a
+ * candidate generator of their own); `h` gives the row layout, the Box and the device.  `s` is the round's radius in [0, 1] (0: every candidate is the nominal). */
+#define FTL_SEARCH_OWN_STREAM 1u
+typedef struct ftl_search_params {
+    int32_t K, T, hold, iters;      /* candidates per env, horizon in steps, steps per drawn action, refinement rounds; all >= 1 */
+    double  gamma, spread, decay;   /* discount of ftl_rollout; radius as a share of the Box width, 0 < spread <= 1; 0 < decay <= 1 */
+    uint64_t seed;
+    uint32_t flags;                 /* FTL_SEARCH_OWN_STREAM: clones draw from their own streams (FTL_ENV_OWN_STREAM) */
+    int32_t _pad;
+} ftl_search_params;
+typedef struct ftl_search_buffers {
+    void*    rows;                  /* [n][ftl_env_bytes] */
+    const int32_t* row_ids;         /* [n * K]  i / K */
+    const int32_t* env_ids;         /* [n * K]  i */
+    double*  nominal;               /* [T][n][2] */
+    double*  cand;                  /* [T][n * K][2] */
+    double*  action;                /* [n][2] */
+    int32_t* best_k;                /* [n] */
+    double*  best_ret;              /* [n] */
+    const ftl_outputs* out;         /* of the search handle */
+    const ftl_rollout_outputs* ro;  /* of the search handle */
+} ftl_search_buffers;
+size_t ftl_sizeof_search_params(void);
+size_t ftl_sizeof_search_buffers(void);
+
+/* The draw of candidate k > 0 of the env on stream `stream_id` in round `it` of call `call`: coordinate j (0 speed, 1 rotation) of hold
+ * block `block` = t / hold, on the counter stream of ftl_uniform01 in a key range of its own (bit 43 of the frame key). */
+static inline double ftl_search_uniform(uint64_t seed, uint64_t stream_id, uint64_t call, uint32_t it, uint32_t k, uint32_t block, uint32_t j) {
+    return ftl_uniform01(seed, stream_id, call, (1ULL << 43) | block | ((uint64_t)j << 16) | ((uint64_t)it << 17) | ((uint64_t)k << 24));
+}
+
+int ftl_search_begin(const ftl_handle* h, const void* rows, int32_t n, int32_t T, uint64_t call, int32_t warm, double* nominal, void* stream);
+int ftl_search_sample(const ftl_handle* h, const void* rows, int32_t n, const ftl_search_params* p, uint64_t call, int32_t it, double s,
+                      const double* nominal, double* cand, void* stream);
+int ftl_search_select(const ftl_handle* h, const double* ret, int32_t n, int32_t K, int32_t T, const double* cand, double* nominal,
+                      int32_t* best_k, double* best_ret, void* stream);
+int ftl_search(const ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm,
+               const ftl_search_buffers* b, void* stream);
 
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
