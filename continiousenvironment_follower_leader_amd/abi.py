@@ -234,6 +234,13 @@ class SearchBuffers(C.Structure):
                 ("ro", C.POINTER(RolloutOutputs))]
 
 
+class GuidedBuffers(C.Structure):
+    """ftl_guided_buffers: the fields of ``SearchBuffers`` (``nominal`` / ``cand`` hold residuals), the real batch's outputs, the follower
+    rows of the real envs and of the clones with their byte sizes, and ``cap`` (``search.GuidedSearch`` owns them)."""
+    _fields_ = SearchBuffers._fields_ + [("real_out", C.POINTER(Outputs)), ("real_bl", C.c_void_p), ("real_bl_bytes", C.c_size_t),
+                                         ("search_bl", C.c_void_p), ("search_bl_bytes", C.c_size_t), ("cap", C.c_int32), ("_pad", C.c_int32)]
+
+
 class EpisodeRecord(C.Structure):
     """ftl_episode_record: one row per entry of an episode queue, written once (``RECORD_DTYPE`` is the same row for numpy)."""
     _fields_ = [("state", C.c_int32), ("scenario", C.c_int32), ("env", C.c_int32), ("frames", C.c_int32), ("calls", C.c_int32),

@@ -6,7 +6,8 @@
 // ftl_baseline_kernel: one thread per env.  It reads the env's step word (env_int + e * rec_stride: an env index, not a slot of the cost
 // permutation), three floats of its obs_num row and its target, reads and writes its follower row (16 + 16 * cap bytes) and writes 16
 // bytes of action.  Neighbouring lanes read rows that lie a row stride apart, so nothing here coalesces; per env it touches a handful of
-// cache lines against the kilobytes of a step.
+// cache lines against the kilobytes of a step.  ftl_baseline_guided_kernel (ftl_baseline_act_guided, ftl_rollout_guided) is the same
+// bookkeeping and decision -- one __device__ function, decide() -- with the action clipped to the Box(2), a residual added, clipped again.
 //
 // v = distance.euclidean(position, next_point) is BLAS dnrm2 on x87 in the reference (oracle/ftl_oracle.c, numeric notes): squares and sum
 // in a 64-bit mantissa, sqrtl, one more rounding to double.  The device has no such format, so it returns the correctly rounded
@@ -36,9 +37,9 @@ __device__ __forceinline__ double euclid_cr(double ax, double ay, double bx, dou
     return q + r / (2.0 * q);
 }
 
-__global__ __launch_bounds__(256) void ftl_baseline_kernel(const Args a) {
-    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (e >= a.n_envs) return;
+// The bookkeeping and the decision of env e (e < n_envs): reads and writes the env's follower row, returns the unclipped action (v, w).
+// What ftl_baseline_kernel and ftl_baseline_guided_kernel share.
+__device__ __forceinline__ double2 decide(const Args& a, const int e) {
     const int cap = a.cap;
     unsigned char* row = a.bl + (size_t)e * (16 + 16 * (size_t)cap);
     int32_t* w = reinterpret_cast<int32_t*>(row);
@@ -78,8 +79,31 @@ __global__ __launch_bounds__(256) void ftl_baseline_kernel(const Args a) {
     }
     const double v = euclid_cr(px, py, fx, fy);
     w[0] = head; w[1] = count; w[2] = v <= 20.0 ? 1 : 0; w[3] = (int32_t)flags;
-    a.action[2 * (size_t)e] = v;
-    a.action[2 * (size_t)e + 1] = (double)(delta * sign) / 10.0;
+    return make_double2(v, (double)(delta * sign) / 10.0);
+}
+
+__global__ __launch_bounds__(256) void ftl_baseline_kernel(const Args a) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= a.n_envs) return;
+    const double2 x = decide(a, e);
+    a.action[2 * (size_t)e] = x.x;
+    a.action[2 * (size_t)e + 1] = x.y;
+}
+
+// ftl_baseline_act_guided: the same row bookkeeping and decision, then the action clipped to the Box(2), the residual added, clipped again
+struct GuidedArgs {
+    Args b;
+    const double* resid;     // [n_envs][2]
+    double lo0, hi0, lo1, hi1;
+};
+
+__global__ __launch_bounds__(256) void ftl_baseline_guided_kernel(const GuidedArgs g) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= g.b.n_envs) return;
+    const double2 x = decide(g.b, e);
+    const double r0 = g.resid[2 * (size_t)e], r1 = g.resid[2 * (size_t)e + 1];
+    g.b.action[2 * (size_t)e] = fmin(fmax(fmin(fmax(x.x, g.lo0), g.hi0) + r0, g.lo0), g.hi0);
+    g.b.action[2 * (size_t)e + 1] = fmin(fmax(fmin(fmax(x.y, g.lo1), g.hi1) + r1, g.lo1), g.hi1);
 }
 
 }  // namespace ftlbl
@@ -96,6 +120,12 @@ static int baseline_args(ftl_handle* h, const ftl_outputs* out, void* bl, size_t
     a.env_int = h->P.env_int; a.rec_stride = h->P.rec_stride; a.n_envs = h->P.n_envs; a.cap = cap;
     a.obs_num = out->obs_num; a.target = out->target; a.bl = (unsigned char*)bl; a.action = nullptr;
     return FTL_OK;
+}
+
+// the Box(2) bounds of ENV:374-378 (those of ftl_search_sample and of the env's own clip)
+static void baseline_box(const ftl_handle* h, ftlbl::GuidedArgs& g) {
+    const ftl_robot_params& f = h->P.cfg.follower;
+    g.lo0 = f.min_speed; g.hi0 = f.max_speed; g.lo1 = -f.max_rotation_speed; g.hi1 = f.max_rotation_speed;
 }
 
 extern "C" {
@@ -115,16 +145,44 @@ int ftl_baseline_act(ftl_handle* h, const ftl_outputs* out, void* bl, size_t bl_
     return FTL_OK;
 }
 
-int ftl_rollout_baseline(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
-                         void* bl, size_t bl_bytes, int32_t cap, double* actions, int64_t step_bytes, uint32_t flags, void* stream) {
+int ftl_baseline_act_guided(ftl_handle* h, const ftl_outputs* out, void* bl, size_t bl_bytes, int32_t cap, const double* resid, double* action,
+                            void* stream) {
+    if (!action || !resid) return fail(FTL_E_INVALID, "null argument");
+    if (((uintptr_t)resid) & 7) return fail(FTL_E_INVALID, "ftl_baseline_act_guided: resid must be 8-byte aligned");
+    ftlbl::GuidedArgs g;
+    if (int rc = baseline_args(h, out, bl, bl_bytes, cap, g.b)) return rc;
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    g.b.action = action; g.resid = resid;
+    baseline_box(h, g);
+    hipLaunchKernelGGL(ftlbl::ftl_baseline_guided_kernel, dim3((unsigned)((h->P.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FTL_OK;
+}
+
+}  // extern "C"
+
+// ftl_rollout_baseline (T steps, no residual) and ftl_rollout_guided: steps 0 .. T-1 add resid + t * resid_step_bytes when `resid` is given,
+// steps T .. T+tail-1 are the plain baseline; one fold, one discount across both parts.  `name` heads the messages.
+static int baseline_rollout(const char* name, ftl_handle* h, int32_t T, int32_t tail, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                            void* bl, size_t bl_bytes, int32_t cap, const double* resid, int64_t resid_step_bytes, double* actions,
+                            int64_t step_bytes, uint32_t flags, void* stream) {
     if (!h || !out || !ro || !bl) return fail(FTL_E_INVALID, "null argument");
     if (!ro->ret || !ro->steps || !ro->status) return fail(FTL_E_INVALID, "ftl_rollout_outputs: ret / steps / status missing");
-    if (T <= 0) return fail(FTL_E_INVALID, "ftl_rollout_baseline: T must be positive");
-    if (flags & ~(uint32_t)FTL_STEP_NO_SENSORS) return fail(FTL_E_INVALID, "ftl_rollout_baseline takes no flag but FTL_STEP_NO_SENSORS (there is no auto-reset inside a rollout)");
-    if (actions && step_bytes < (int64_t)h->P.n_envs * 16) return fail(FTL_E_INVALID, "ftl_rollout_baseline: step_bytes below one block of [n_envs][2] doubles");
-    ftlbl::Args b;
+    if (T <= 0) return fail(FTL_E_INVALID, std::string(name) + ": T must be positive");
+    if (tail < 0 || tail > INT32_MAX - T) return fail(FTL_E_INVALID, std::string(name) + ": tail must be at least 0 (and T + tail an int32)");
+    if (flags & ~(uint32_t)FTL_STEP_NO_SENSORS) return fail(FTL_E_INVALID, std::string(name) + " takes no flag but FTL_STEP_NO_SENSORS (there is no auto-reset inside a rollout)");
+    if (actions && step_bytes < (int64_t)h->P.n_envs * 16) return fail(FTL_E_INVALID, std::string(name) + ": step_bytes below one block of [n_envs][2] doubles");
+    if (resid && resid_step_bytes < (int64_t)h->P.n_envs * 16) return fail(FTL_E_INVALID, std::string(name) + ": resid_step_bytes below one block of [n_envs][2] doubles");
+    if (resid && ((((uintptr_t)resid) | (uintptr_t)resid_step_bytes) & 7)) return fail(FTL_E_INVALID, std::string(name) + ": resid and resid_step_bytes must be 8-byte aligned");
+    ftlbl::GuidedArgs g;
+    ftlbl::Args& b = g.b;
     int rc = baseline_args(h, out, bl, bl_bytes, cap, b);
     if (rc) return rc;
+    baseline_box(h, g);
+    const int32_t guided = resid ? T : 0;
+    T += tail;
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
     if (!h->ro_alive) {
@@ -146,7 +204,10 @@ int ftl_rollout_baseline(ftl_handle* h, int32_t T, double gamma, const ftl_outpu
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     for (int32_t t = 0; t < T; t++) {
         b.action = actions ? (double*)((char*)actions + (int64_t)t * step_bytes) : h->bl_action;
-        hipLaunchKernelGGL(ftlbl::ftl_baseline_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
+        if (t < guided) {
+            g.resid = (const double*)((const char*)resid + (int64_t)t * resid_step_bytes);
+            hipLaunchKernelGGL(ftlbl::ftl_baseline_guided_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
+        } else hipLaunchKernelGGL(ftlbl::ftl_baseline_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
         call.action = b.action;
         call.flags = (t < T - 1) ? (uint32_t)FTL_STEP_NO_SENSORS : flags;
         rc = launch(h, call, stream);                           // (a two-stream handle forks after the act kernel and joins before the fold)
@@ -157,6 +218,19 @@ int ftl_rollout_baseline(ftl_handle* h, int32_t T, double gamma, const ftl_outpu
     e = hipGetLastError();
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
     return FTL_OK;
+}
+
+extern "C" {
+
+int ftl_rollout_baseline(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                         void* bl, size_t bl_bytes, int32_t cap, double* actions, int64_t step_bytes, uint32_t flags, void* stream) {
+    return baseline_rollout("ftl_rollout_baseline", h, T, 0, gamma, out, ro, bl, bl_bytes, cap, nullptr, 0, actions, step_bytes, flags, stream);
+}
+
+int ftl_rollout_guided(ftl_handle* h, int32_t T, int32_t tail, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                       void* bl, size_t bl_bytes, int32_t cap, const double* resid, int64_t resid_step_bytes, double* actions, int64_t step_bytes,
+                       uint32_t flags, void* stream) {
+    return baseline_rollout("ftl_rollout_guided", h, T, tail, gamma, out, ro, bl, bl_bytes, cap, resid, resid_step_bytes, actions, step_bytes, flags, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // ftl_search.hpp -- action search on the device (include/ftl.h: ftl_search, ftl_search_begin / _sample / _select): K candidate action
-// sequences per env, rolled out blind on clones in a second handle, the best one kept, refined with a shrinking radius.  Included at the
-// end of ftl_abi.hip after ftl_baseline.hpp (same translation unit: it reads the handles and calls ftl_pack_envs, ftl_unpack_envs_from and
-// ftl_rollout).  Everything heavy is those three; the kernels here move a few doubles per candidate:
+// sequences per env, rolled out blind on clones in a second handle, the best one kept, refined with a shrinking radius.  Included by
+// ftl_abi.hip after ftl_baseline.hpp and before ftl_guided.hpp, which launches the same kernels on residuals (same translation unit: it
+// reads the handles and calls ftl_pack_envs, ftl_unpack_envs_from and ftl_rollout).  Everything heavy is those three; the kernels here
+// move a few doubles per candidate:
 //
 // ftl_search_begin_kernel   one thread per env: the nominal sequence of this call -- the default (max speed, straight on) for a new episode,
 //                           else the last call's plan shifted by one step.  Reads one word of the env's packed row.
@@ -133,6 +134,43 @@ static int launched() {
 
 static int32_t row_word(const ftl_handle* h, int which) { return (int32_t)(h->fields[F_env_int].offset / 4 + which); }
 
+// ftl_search_begin with the default plan's speed given (ftl_search_guided starts from the zero residual)
+static int begin(const ftl_handle* h, const void* rows, int32_t n, int32_t T, uint64_t call, int32_t warm, double speed, double* nominal, void* stream) {
+    if (!h || !rows || !nominal) return fail(FTL_E_INVALID, "null argument");
+    if (int rc = check_size(n, 1, T)) return rc;
+    if (int rc = set_device(h)) return rc;
+    BeginArgs a;
+    a.rows = (const unsigned char*)rows; a.row_bytes = ftls::make_args(h).row_bytes; a.w_step = row_word(h, FTL_EI_STEP_COUNT);
+    a.n = n; a.T = T; a.fresh = (call == 0 || !warm) ? 1 : 0; a.speed = speed; a.nominal = nominal;
+    hipLaunchKernelGGL(ftl_search_begin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launched();
+}
+
+// ftl_search_sample on the action Box(2), or (residual: ftl_search_guided) on the box of the same width centred on 0
+static int sample(const ftl_handle* h, const void* rows, int32_t n, const ftl_search_params* p, uint64_t call, int32_t it, double s, bool residual,
+                  const double* nominal, double* cand, void* stream) {
+    if (!h || !rows || !nominal || !cand) return fail(FTL_E_INVALID, "null argument");
+    if (int rc = check_params(p)) return rc;
+    if (int rc = check_size(n, p->K, p->T)) return rc;
+    if (it < 0 || it >= 128) return fail(FTL_E_INVALID, "ftl_search_sample: round outside 0 .. 127");
+    if (!(s >= 0.0 && s <= 1.0)) return fail(FTL_E_INVALID, "ftl_search_sample: the radius s must lie in [0, 1]");
+    if ((((uintptr_t)nominal) | ((uintptr_t)cand)) & 15) return fail(FTL_E_INVALID, "nominal and cand must be 16-byte aligned");
+    if (int rc = set_device(h)) return rc;
+    const ftl_robot_params& f = h->P.cfg.follower;
+    SampleArgs a;
+    a.rows = (const unsigned char*)rows; a.row_bytes = ftls::make_args(h).row_bytes; a.w_stream = row_word(h, FTL_EI_STREAM);
+    a.n = n; a.K = p->K; a.T = p->T; a.hold = p->hold; a.it = it; a.seed = p->seed; a.call = call; a.s = s;
+    a.lo0 = f.min_speed; a.hi0 = f.max_speed; a.lo1 = -f.max_rotation_speed; a.hi1 = f.max_rotation_speed;
+    if (residual) {                                            // hi - lo is the Box's width again, exactly
+        const double h0 = (a.hi0 - a.lo0) / 2.0, h1 = (a.hi1 - a.lo1) / 2.0;
+        a.lo0 = -h0; a.hi0 = h0; a.lo1 = -h1; a.hi1 = h1;
+    }
+    a.nominal = nominal; a.cand = cand;
+    const unsigned long long total = (unsigned long long)n * p->K * p->T;
+    hipLaunchKernelGGL(ftl_search_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return launched();
+}
+
 }  // namespace ftlse
 
 extern "C" {
@@ -141,34 +179,13 @@ size_t ftl_sizeof_search_params(void) { return sizeof(ftl_search_params); }
 size_t ftl_sizeof_search_buffers(void) { return sizeof(ftl_search_buffers); }
 
 int ftl_search_begin(const ftl_handle* h, const void* rows, int32_t n, int32_t T, uint64_t call, int32_t warm, double* nominal, void* stream) {
-    if (!h || !rows || !nominal) return fail(FTL_E_INVALID, "null argument");
-    if (int rc = ftlse::check_size(n, 1, T)) return rc;
-    if (int rc = ftlse::set_device(h)) return rc;
-    ftlse::BeginArgs a;
-    a.rows = (const unsigned char*)rows; a.row_bytes = ftls::make_args(h).row_bytes; a.w_step = ftlse::row_word(h, FTL_EI_STEP_COUNT);
-    a.n = n; a.T = T; a.fresh = (call == 0 || !warm) ? 1 : 0; a.speed = h->P.cfg.follower.max_speed; a.nominal = nominal;
-    hipLaunchKernelGGL(ftlse::ftl_search_begin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return ftlse::launched();
+    if (!h) return fail(FTL_E_INVALID, "null argument");
+    return ftlse::begin(h, rows, n, T, call, warm, h->P.cfg.follower.max_speed, nominal, stream);
 }
 
 int ftl_search_sample(const ftl_handle* h, const void* rows, int32_t n, const ftl_search_params* p, uint64_t call, int32_t it, double s,
                       const double* nominal, double* cand, void* stream) {
-    if (!h || !rows || !nominal || !cand) return fail(FTL_E_INVALID, "null argument");
-    if (int rc = ftlse::check_params(p)) return rc;
-    if (int rc = ftlse::check_size(n, p->K, p->T)) return rc;
-    if (it < 0 || it >= 128) return fail(FTL_E_INVALID, "ftl_search_sample: round outside 0 .. 127");
-    if (!(s >= 0.0 && s <= 1.0)) return fail(FTL_E_INVALID, "ftl_search_sample: the radius s must lie in [0, 1]");
-    if ((((uintptr_t)nominal) | ((uintptr_t)cand)) & 15) return fail(FTL_E_INVALID, "nominal and cand must be 16-byte aligned");
-    if (int rc = ftlse::set_device(h)) return rc;
-    const ftl_robot_params& f = h->P.cfg.follower;
-    ftlse::SampleArgs a;
-    a.rows = (const unsigned char*)rows; a.row_bytes = ftls::make_args(h).row_bytes; a.w_stream = ftlse::row_word(h, FTL_EI_STREAM);
-    a.n = n; a.K = p->K; a.T = p->T; a.hold = p->hold; a.it = it; a.seed = p->seed; a.call = call; a.s = s;
-    a.lo0 = f.min_speed; a.hi0 = f.max_speed; a.lo1 = -f.max_rotation_speed; a.hi1 = f.max_rotation_speed;
-    a.nominal = nominal; a.cand = cand;
-    const unsigned long long total = (unsigned long long)n * p->K * p->T;
-    hipLaunchKernelGGL(ftlse::ftl_search_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return ftlse::launched();
+    return ftlse::sample(h, rows, n, p, call, it, s, false, nominal, cand, stream);
 }
 
 int ftl_search_select(const ftl_handle* h, const double* ret, int32_t n, int32_t K, int32_t T, const double* cand, double* nominal,

@@ -282,6 +282,17 @@ class _BatchBase:
             raise ValueError("rollout_baseline() takes a BaselineFollower of this batch")
         return follower.rollout(T, gamma, sensors, record)
 
+    def rollout_guided(self, follower, resid, tail=0, gamma=1.0, sensors=True, record=False):
+        """``rollout_baseline`` over ``T + tail`` steps whose first ``T`` decisions are guided by the float64 ``[T, N, 2]`` residuals
+        ``resid`` (``ftl_rollout_guided``): in step t < T the baseline's action is clipped to the Box(2), ``resid[t]`` added and the sum
+        clipped again; the ``tail`` steps after them are the plain baseline.  One fold and one discount across both parts.  Returns
+        ``(ret, steps, status)``, plus with ``record=True`` the ``[T + tail, N, 2]`` actions that were played.  A zero ``resid`` steps the envs
+        and the follower as ``rollout_baseline(follower, T + tail)`` does.  With the residual plan of a ``search.GuidedSearch`` (its
+        ``nominal``) and a copy of its follower from the same state, ``ret`` is its ``best_ret`` bit for bit."""
+        if getattr(follower, "batch", None) is not self:
+            raise ValueError("rollout_guided() takes a BaselineFollower of this batch")
+        return follower.rollout_guided(resid, tail, gamma, sensors, record)
+
     def terminated_truncated(self):
         """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
         truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap

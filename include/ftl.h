@@ -735,6 +735,81 @@ int ftl_search_select(const ftl_handle* h, const double* ret, int32_t n, int32_t
 int ftl_search(const ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm,
                const ftl_search_buffers* b, void* stream);
 
+/* ---- guided search: the action search over RESIDUALS added to the baseline follower's own closed-loop action, scored over a horizon that
+ * ends in a closed-loop baseline tail ----------------------------------------------------------------------------------------------------
+ * ftl_baseline_act_guided (ftl_baseline_guided_kernel) is ftl_baseline_act with one more input, resid (DEVICE, [n][2] float64, 8-byte
+ * aligned): the follower-row bookkeeping and the decision are those of ftl_baseline_kernel bit for bit (one __device__ function), and with
+ * base = the baseline's raw action (v, w) the written action is
+ *     a_j = fmin(fmax(fmin(fmax(base_j, lo_j), hi_j) + r_j, lo_j), hi_j)
+ * in float64, this operation order, one rounding per operation, (lo, hi) the Box(2) bounds of ftl_search_sample.  The raw action is clipped
+ * FIRST: it is almost always saturated (v is a distance in pixels, the turn is in tenths of degrees), so a residual added before the clip
+ * would do nothing.  The env clips with the same bounds, so a zero residual steps the env exactly as the unclipped baseline action does.
+ *
+ * ftl_rollout_guided is ftl_rollout_baseline over T + tail steps whose first T decisions are guided: for t < T the guided act kernel with
+ * resid + t * resid_step_bytes, for T <= t < T + tail the plain ftl_baseline_kernel; after each a step without auto-reset and
+ * ftl_rollout_fold_kernel, the discount running on across both parts (disc_{t+1} = disc_t * gamma).  All steps but the last run with
+ * FTL_STEP_NO_SENSORS, the last with `flags`; a two-stream handle, `actions` / step_bytes (the record of what was played, T + tail blocks)
+ * and the precondition on `out` are those of ftl_rollout_baseline.  resid == NULL is ftl_rollout_baseline(T + tail).  FTL_E_INVALID before
+ * any device work: what ftl_rollout_baseline refuses, T < 1, tail < 0, resid_step_bytes below one block of [n][2] doubles, resid or
+ * resid_step_bytes not 8-byte aligned; FTL_E_STATE without bound state / scenarios.
+ *
+ * ftl_guided_fanout (ftl_guided_fanout_kernel) gives clone i = e * K + k of the search handle what ftl_unpack_envs_from does not carry: the
+ * real follower row e (16 + 16 * cap bytes) -> follower row i of search_bl, and rows e of real_out->obs_num (FTL_OBS_NUM floats) and
+ * real_out->target (two doubles) -> rows i of search_out.  After ftl_unpack_envs_from a clone's first decision then reads the observation
+ * its source had.  Nothing else is written.  16-byte loads and stores, both follower buffers 16-byte aligned.  FTL_E_INVALID: NULL
+ * pointers, cap < 2, a follower buffer below its handle's ftl_baseline_bytes or misaligned, search handle size != n * K, another device,
+ * source and destination the same buffer.
+ *
+ * ftl_search_guided: the two handles of ftl_search, one call enqueued on `stream` without a host synchronisation:
+ *   1. ftl_pack_envs of the n real envs.
+ *   2. begin: ftl_search_begin_kernel with the default plan (0, 0) in place of (max_speed, 0) -- the zero residual, i.e. the baseline itself;
+ *      the new-episode rule and the warm shift are those of ftl_search.  nominal [T][n][2] is the RESIDUAL plan.
+ *   3. for it = 0 .. iters - 1 (radius as in ftl_search):
+ *      sample  ftl_search_sample_kernel on the residual box [-(hi_j - lo_j) / 2, +(hi_j - lo_j) / 2]: its width is the action Box's, so the
+ *              formula and the draws of ftl_search_uniform carry over; candidate 0 is the incumbent residual plan.
+ *      fan-out ftl_unpack_envs_from as in ftl_search, then ftl_guided_fanout.
+ *      rollout ftl_rollout_guided(search, T, tail, gamma, out, ro, search_bl, ..., resid = cand, FTL_STEP_NO_SENSORS).
+ *      select  ftl_search_select_kernel.
+ *   4. ftl_baseline_act_guided on the REAL handle with resid = nominal[0], writing `action`: it books the real follower's step exactly once,
+ *      as one ftl_baseline_act per step does, and comes last so that every round fans out the follower rows as they were before it.
+ * Properties (clones on their source's stream): candidate 0 of a call that starts from the default plan is the baseline itself, so best_ret
+ * is never below the baseline's return over T + tail steps, bit for bit equal for K = 1; best_ret is non-decreasing over the rounds;
+ * ftl_rollout_guided of `nominal` on the real handle from the same state and a copy of the follower rows returns best_ret bit for bit.
+ * The real handle's state and outputs are only read; its follower rows and `action` are written by step 4 alone.
+ * FTL_E_INVALID before any device work: what ftl_search refuses, tail < 0, a NULL field of gb, cap < 2, a follower buffer below its
+ * handle's ftl_baseline_bytes or not 16-byte aligned; FTL_E_STATE as ftl_search.  FTL_SEARCH_OWN_STREAM means what it means there. */
+typedef struct ftl_guided_buffers {
+    void*    rows;                  /* the fields of ftl_search_buffers, as there; nominal and cand hold residuals */
+    const int32_t* row_ids;
+    const int32_t* env_ids;
+    double*  nominal;
+    double*  cand;
+    double*  action;                /* [n][2] the action to play: clip(clip(base) + nominal[0]) */
+    int32_t* best_k;
+    double*  best_ret;
+    const ftl_outputs* out;         /* of the search handle */
+    const ftl_rollout_outputs* ro;  /* of the search handle */
+    const ftl_outputs* real_out;    /* of the real handle: what its last reset / step wrote */
+    void*    real_bl;               /* [n] follower rows of the real envs */
+    size_t   real_bl_bytes;
+    void*    search_bl;             /* [n * K] follower rows of the clones (scratch) */
+    size_t   search_bl_bytes;
+    int32_t  cap;
+    int32_t  _pad;
+} ftl_guided_buffers;
+size_t ftl_sizeof_guided_buffers(void);
+int ftl_baseline_act_guided(ftl_handle* h, const ftl_outputs* out, void* bl, size_t bl_bytes, int32_t cap,
+                            const double* resid /* [n][2] */, double* action /* [n][2] */, void* stream);
+int ftl_rollout_guided(ftl_handle* h, int32_t T, int32_t tail, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                       void* bl, size_t bl_bytes, int32_t cap,
+                       const double* resid /* [T] blocks of [n][2], or NULL */, int64_t resid_step_bytes,
+                       double* actions /* [T + tail] blocks of [n][2], or NULL */, int64_t step_bytes,
+                       uint32_t flags /* FTL_STEP_NO_SENSORS only */, void* stream);
+int ftl_guided_fanout(const ftl_handle* real, const ftl_handle* search, int32_t K, const ftl_outputs* real_out, const ftl_outputs* search_out,
+                      const void* real_bl, size_t real_bl_bytes, void* search_bl, size_t search_bl_bytes, int32_t cap, void* stream);
+int ftl_search_guided(ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm, int32_t tail,
+                      const ftl_guided_buffers* gb, void* stream);
+
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
  * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
