@@ -56,40 +56,38 @@ class BaselineFollower:
 
     def rollout(self, T, gamma=1.0, sensors=True, record=False):
         """``batch.rollout_baseline(self, ...)``."""
-        b, T = self.batch, int(T)
-        b._need_pool()
+        T = int(T)
+        self.batch._need_pool()
         if T < 1:
             raise ValueError("a rollout needs T >= 1")
-        actions = torch.empty(T, self.n, 2, dtype=torch.float64, device=self.device) if record else None
-        b._prepare_rollout_outputs()
-        sp, ap = self.state.data_ptr(), (actions.data_ptr() if record else 0)
-        flags = 0 if sensors else abi.FTL_STEP_NO_SENSORS
-        for (g, lo, n), s in zip(self._parts, self._streams(actions)):
-            _lib.check(self.lib.ftl_rollout_baseline(g.h, T, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), sp + lo * self.row,
-                                                     n * self.row, self.cap, (ap + lo * 16) if record else None, self.n * 16 if record else 0,
-                                                     flags, s), self.lib)
-        out = (b.rollout_ret, b.rollout_steps, b.rollout_status)
-        return out + (actions,) if record else out
+        return self._rollout(T, None, gamma, sensors, record)
 
     def rollout_guided(self, resid, tail=0, gamma=1.0, sensors=True, record=False):
         """``batch.rollout_guided(self, ...)``."""
-        b, tail = self.batch, int(tail)
-        b._need_pool()
+        tail = int(tail)
+        self.batch._need_pool()
         if (not torch.is_tensor(resid) or resid.dim() != 3 or resid.shape[0] < 1 or tuple(resid.shape[1:]) != (self.n, 2)
                 or resid.dtype != torch.float64 or resid.device != self.state.device):
             raise ValueError("resid must be a float64 [T, n_envs, 2] tensor on the batch's device with T >= 1")
         if tail < 0:
             raise ValueError("tail must be at least 0")
-        T = int(resid.shape[0])
         self._keep_resid = resid = resid.contiguous()      # (alive until the next call: the parts of a pipelined batch read it on their streams)
-        actions = torch.empty(T + tail, self.n, 2, dtype=torch.float64, device=self.device) if record else None
+        return self._rollout(int(resid.shape[0]) + tail, resid, gamma, sensors, record)
+
+    def _rollout(self, steps, resid, gamma, sensors, record):
+        """The call of every part and the return tuple of both rollouts: ``steps`` steps in all, the first ``len(resid)`` of them guided
+        (``ftl_rollout_guided``); ``resid`` None is ``ftl_rollout_baseline``."""
+        b, guided = self.batch, resid is not None
+        T = int(resid.shape[0]) if guided else steps
+        call = self.lib.ftl_rollout_guided if guided else self.lib.ftl_rollout_baseline
+        actions = torch.empty(steps, self.n, 2, dtype=torch.float64, device=self.device) if record else None
         b._prepare_rollout_outputs()
-        sp, ap, rp = self.state.data_ptr(), (actions.data_ptr() if record else 0), resid.data_ptr()
+        sp, ap = self.state.data_ptr(), (actions.data_ptr() if record else 0)
         flags = 0 if sensors else abi.FTL_STEP_NO_SENSORS
         for (g, lo, n), s in zip(self._parts, self._streams(actions)):
-            _lib.check(self.lib.ftl_rollout_guided(g.h, T, tail, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), sp + lo * self.row,
-                                                   n * self.row, self.cap, rp + lo * 16, self.n * 16, (ap + lo * 16) if record else None,
-                                                   self.n * 16 if record else 0, flags, s), self.lib)
+            head, res = ((g.h, T, steps - T), (resid.data_ptr() + lo * 16, self.n * 16)) if guided else ((g.h, T), ())
+            _lib.check(call(*head, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), sp + lo * self.row, n * self.row, self.cap, *res,
+                            (ap + lo * 16) if record else None, self.n * 16 if record else 0, flags, s), self.lib)
         out = (b.rollout_ret, b.rollout_steps, b.rollout_status)
         return out + (actions,) if record else out
 

@@ -114,6 +114,20 @@ namespace {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The first and the last line of every entry that launches.  set_device: the device of the handle (an ftl_handle or an ftl_gz_handle)
+// becomes the thread's current one.  launched: the runtime accepted every launch since the last such check.
+template <typename H> int set_device(const H* h) {
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    return FTL_OK;
+}
+
+int launched() {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FTL_OK;
+}
+
 int validate(const ftl_config& c, std::string& why) {
     char buf[256];
 #define REQ(cond, ...) do { if (!(cond)) { snprintf(buf, sizeof buf, __VA_ARGS__); why = buf; return FTL_E_INVALID; } } while (0)
@@ -570,12 +584,11 @@ static int sync_params(ftl_handle* h) {
 static int launch(ftl_handle* h, const FtlCall& call_in, void* stream) {
     const bool sensors = !(call_in.flags & FTL_STEP_NO_SENSORS);
     FtlCall call = call_in; call.flags &= ~(uint32_t)FTL_STEP_NO_SENSORS;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     if (h->sched.regroup && !h->rg_mem) {
         const size_t n = (size_t)h->P.n_envs, nb = (n + FTL_RG_BLOCK - 1) / FTL_RG_BLOCK;
         const size_t o_bh = align_up(n * 4, 256), o_rank = o_bh + align_up(nb * FTL_NKEYS * 4, 256), o_keys = o_rank + align_up(n * 2, 256), o_tot = o_keys + align_up(n, 256);
-        e = hipMalloc(&h->rg_mem, o_tot + 2 * FTL_NKEYS * sizeof(int));
+        hipError_t e = hipMalloc(&h->rg_mem, o_tot + 2 * FTL_NKEYS * sizeof(int));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(regroup): ") + hipGetErrorString(e));
         char* b = (char*)h->rg_mem;
         h->P.perm = (int32_t*)b; h->P.bh = (int32_t*)(b + o_bh); h->P.rank = (uint16_t*)(b + o_rank); h->P.keys = (uint8_t*)(b + o_keys);
@@ -638,9 +651,7 @@ static int launch(ftl_handle* h, const FtlCall& call_in, void* stream) {
         hipLaunchKernelGGL(ftl::ftl_regroup_scatter_kernel, dim3(nb), dim3(FTL_RG_BLOCK), 0, (hipStream_t)stream, h->dP, (const int*)tot, tot_next);
     }
     if (tev) (void)hipEventRecord(tev[4], (hipStream_t)stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 }  // extern "C"
@@ -731,12 +742,9 @@ int ftl_step_final(ftl_handle* h, const void* action, int32_t encoding, const ft
 
 int ftl_scan(ftl_handle* h, const ftl_outputs* out, void* stream) {
     if (!h || !out) return fail(FTL_E_INVALID, "null argument");
-    int rc = check_ready(h, out);
-    if (rc) return rc;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    rc = sync_params(h);
-    if (rc) return rc;
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (int rc = sync_params(h)) return rc;
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     // the sensor launches of a step (mode 0, no flags) with the kernels a step of this handle runs; a two-stream handle's two halves go
     // one after the other on the caller's stream (every env is scanned once either way)
@@ -750,9 +758,7 @@ int ftl_scan(ftl_handle* h, const ftl_outputs* out, void* stream) {
         }
     call.part = call.parts = call.epw = 0;      // (as launch() hands the call to the aux kernel)
     if (h->has_aux) hipLaunchKernelGGL(ftl_aux_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), ftl_aux_lds_bytes(h->P.cfg), (hipStream_t)stream, h->dP, call);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 int ftl_kernel_timing(ftl_handle* h, int32_t enable) {
@@ -786,21 +792,18 @@ int ftl_kernel_times(ftl_handle* h, double* ms, int32_t* n_steps) {
 int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors, uint32_t flags, void* stream) {
     if (!h || !dev_metrics) return fail(FTL_E_INVALID, "null argument");
     if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     const int nb = (h->P.n_envs + FTL_MT_BLOCK - 1) / FTL_MT_BLOCK;
     const size_t o_err = align_up((size_t)nb * FTL_N_METRICS * sizeof(double), 256);
     if (!h->mt_mem) {
-        e = hipMalloc(&h->mt_mem, o_err + (size_t)nb * 2 * sizeof(int));
+        hipError_t e = hipMalloc(&h->mt_mem, o_err + (size_t)nb * 2 * sizeof(int));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(metrics): ") + hipGetErrorString(e));
     }
     { int rc = sync_params(h); if (rc) return rc; }
     double* part = (double*)h->mt_mem; int* epart = (int*)((char*)h->mt_mem + o_err);
     hipLaunchKernelGGL(ftl::ftl_metrics_partial_kernel, dim3((unsigned)nb), dim3(FTL_MT_THREADS), 0, (hipStream_t)stream, h->dP, part, epart, (flags & FTL_METRICS_CLEAR) ? 1 : 0);
     hipLaunchKernelGGL(ftl::ftl_metrics_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)part, (const int*)epart, nb, dev_metrics, dev_errors);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // ftl_baseline.hpp -- the reference's way-point chase ("base algorithm", run_2d.py --mode base, lines 109-151, around
 // utils/misc.py:move_to_the_point, MISC:65-95) as a policy on the device (ftl_baseline_act) and as closed-loop rollouts with one call
 // (ftl_rollout_baseline); the contract is in include/ftl.h.  Included by ftl_abi.hip after ftl_rollout.hpp (same translation unit: it
-// reads the handle, calls launch() and reuses ftl_rollout_fold_kernel).
+// reads the handle and hands its act kernels to rollout_loop, which owns the steps and the fold).
 //
 // ftl_baseline_kernel: one thread per env.  It reads the env's step word (env_int + e * rec_stride: an env index, not a slot of the cost
 // permutation), three floats of its obs_num row and its target, reads and writes its follower row (16 + 16 * cap bytes) and writes 16
@@ -136,13 +136,10 @@ int ftl_baseline_act(ftl_handle* h, const ftl_outputs* out, void* bl, size_t bl_
     if (!action) return fail(FTL_E_INVALID, "null argument");
     ftlbl::Args a;
     if (int rc = baseline_args(h, out, bl, bl_bytes, cap, a)) return rc;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     a.action = action;
     hipLaunchKernelGGL(ftlbl::ftl_baseline_kernel, dim3((unsigned)((h->P.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 int ftl_baseline_act_guided(ftl_handle* h, const ftl_outputs* out, void* bl, size_t bl_bytes, int32_t cap, const double* resid, double* action,
@@ -151,73 +148,45 @@ int ftl_baseline_act_guided(ftl_handle* h, const ftl_outputs* out, void* bl, siz
     if (((uintptr_t)resid) & 7) return fail(FTL_E_INVALID, "ftl_baseline_act_guided: resid must be 8-byte aligned");
     ftlbl::GuidedArgs g;
     if (int rc = baseline_args(h, out, bl, bl_bytes, cap, g.b)) return rc;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     g.b.action = action; g.resid = resid;
     baseline_box(h, g);
     hipLaunchKernelGGL(ftlbl::ftl_baseline_guided_kernel, dim3((unsigned)((h->P.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 }  // extern "C"
 
 // ftl_rollout_baseline (T steps, no residual) and ftl_rollout_guided: steps 0 .. T-1 add resid + t * resid_step_bytes when `resid` is given,
-// steps T .. T+tail-1 are the plain baseline; one fold, one discount across both parts.  `name` heads the messages.
+// steps T .. T+tail-1 are the plain baseline; one fold, one discount across both parts.  `name` heads the messages.  The loop is
+// rollout_loop of ftl_rollout.hpp; what is here is the action of step t: the act kernel of its part, into the caller's record or bl_action.
 static int baseline_rollout(const char* name, ftl_handle* h, int32_t T, int32_t tail, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
                             void* bl, size_t bl_bytes, int32_t cap, const double* resid, int64_t resid_step_bytes, double* actions,
                             int64_t step_bytes, uint32_t flags, void* stream) {
-    if (!h || !out || !ro || !bl) return fail(FTL_E_INVALID, "null argument");
-    if (!ro->ret || !ro->steps || !ro->status) return fail(FTL_E_INVALID, "ftl_rollout_outputs: ret / steps / status missing");
-    if (T <= 0) return fail(FTL_E_INVALID, std::string(name) + ": T must be positive");
-    if (tail < 0 || tail > INT32_MAX - T) return fail(FTL_E_INVALID, std::string(name) + ": tail must be at least 0 (and T + tail an int32)");
-    if (flags & ~(uint32_t)FTL_STEP_NO_SENSORS) return fail(FTL_E_INVALID, std::string(name) + " takes no flag but FTL_STEP_NO_SENSORS (there is no auto-reset inside a rollout)");
+    if (!h || !out || !bl) return fail(FTL_E_INVALID, "null argument");
+    if (int rc = rollout_check(name, ro, T, tail, flags)) return rc;
     if (actions && step_bytes < (int64_t)h->P.n_envs * 16) return fail(FTL_E_INVALID, std::string(name) + ": step_bytes below one block of [n_envs][2] doubles");
     if (resid && resid_step_bytes < (int64_t)h->P.n_envs * 16) return fail(FTL_E_INVALID, std::string(name) + ": resid_step_bytes below one block of [n_envs][2] doubles");
     if (resid && ((((uintptr_t)resid) | (uintptr_t)resid_step_bytes) & 7)) return fail(FTL_E_INVALID, std::string(name) + ": resid and resid_step_bytes must be 8-byte aligned");
     ftlbl::GuidedArgs g;
     ftlbl::Args& b = g.b;
-    int rc = baseline_args(h, out, bl, bl_bytes, cap, b);
-    if (rc) return rc;
+    if (int rc = baseline_args(h, out, bl, bl_bytes, cap, b)) return rc;
     baseline_box(h, g);
     const int32_t guided = resid ? T : 0;
-    T += tail;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    if (!h->ro_alive) {
-        e = hipMalloc((void**)&h->ro_alive, align_up((size_t)h->P.n_envs, 256));
-        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(rollout scratch): ") + hipGetErrorString(e));
-    }
+    if (int rc = set_device(h)) return rc;
     if (!actions && !h->bl_action) {
-        e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
+        hipError_t e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(baseline actions): ") + hipGetErrorString(e));
     }
-    ftlro::Args a;
-    a.env_int = h->P.env_int; a.rec_stride = h->P.rec_stride; a.n_envs = h->P.n_envs;
-    a.reward = out->reward; a.done = out->done; a.status = out->status;
-    a.ro = *ro; a.alive = h->ro_alive; a.disc = 1.0; a.first = 1;
     const dim3 grid((unsigned)((h->P.n_envs + 255) / 256));
-    hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    a.first = 0;
-    FtlCall call = make_call(h, 0, out);
-    h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
-    for (int32_t t = 0; t < T; t++) {
+    return rollout_loop(h, FTL_ACTION_BOX2, T + tail, gamma, out, ro, flags, stream, [&](int32_t t) {
         b.action = actions ? (double*)((char*)actions + (int64_t)t * step_bytes) : h->bl_action;
         if (t < guided) {
             g.resid = (const double*)((const char*)resid + (int64_t)t * resid_step_bytes);
             hipLaunchKernelGGL(ftlbl::ftl_baseline_guided_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
         } else hipLaunchKernelGGL(ftlbl::ftl_baseline_kernel, grid, dim3(256), 0, (hipStream_t)stream, b);
-        call.action = b.action;
-        call.flags = (t < T - 1) ? (uint32_t)FTL_STEP_NO_SENSORS : flags;
-        rc = launch(h, call, stream);                           // (a two-stream handle forks after the act kernel and joins before the fold)
-        if (rc) return rc;
-        hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-        a.disc = a.disc * gamma;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+        return b.action;
+    });
 }
 
 extern "C" {

@@ -318,12 +318,9 @@ int ftl_gz_state_field(const ftl_gz_handle* h, const char* name, size_t* offset,
 }
 static int gz_launch(ftl_gz_handle* h, const FtlGzCall& call, void* stream) {
     if (!h->bound) return fail(FTL_E_STATE, "ftl_gz_bind_state has not been called");
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     hipLaunchKernelGGL(ftl_gz_kernel, dim3((unsigned)h->P.n_envs), dim3(FTL_WAVE), 0, (hipStream_t)stream, h->P, call);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 int ftl_gz_reset(ftl_gz_handle* h, const uint8_t* mask, void* stream) {
     if (!h) return fail(FTL_E_INVALID, "null argument");

@@ -1,7 +1,8 @@
 // ftl_guided.hpp -- guided search (include/ftl.h: ftl_search_guided, ftl_guided_fanout): the action search of ftl_search.hpp over RESIDUALS
 // added to the baseline follower's own closed-loop action, scored over a horizon that ends in a closed-loop baseline tail.  Included at the
-// end of ftl_abi.hip after ftl_search.hpp (same translation unit: it reads the handles and calls ftl_pack_envs, ftl_unpack_envs_from,
-// ftl_rollout_guided, ftl_baseline_act_guided and the begin / sample / select launches of ftl_search.hpp).
+// end of ftl_abi.hip after ftl_search.hpp (same translation unit).  The shared checks and the rounds are those of ftl_search.hpp
+// (check_buffers, check_handles, rounds); what is here is the fan-out, the guided search's own checks, what a round rolls
+// (ftl_guided_fanout, ftl_rollout_guided) and the decision (ftl_baseline_act_guided).
 //
 // ftl_guided_fanout_kernel  what ftl_unpack_envs_from does not carry to a clone: the follower row of its source env and the two output rows
 //                           the follower's next decision reads (obs_num, target).  One lane per piece of a clone's rows, pieces in the order
@@ -68,9 +69,9 @@ int ftl_guided_fanout(const ftl_handle* real, const ftl_handle* search, int32_t 
     a.K = K; a.chunks = 1 + cap;
     a.total = (unsigned long long)n * K * ((unsigned long long)a.chunks + 1 + FTL_OBS_NUM);
     if ((a.total + 255) / 256 > 0x7fffffffull) return fail(FTL_E_INVALID, "ftl_guided_fanout: n * K * cap is too large for one launch");
-    if (int rc = ftlse::set_device(search)) return rc;
+    if (int rc = set_device(search)) return rc;
     hipLaunchKernelGGL(ftlgd::ftl_guided_fanout_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return ftlse::launched();
+    return launched();
 }
 
 int ftl_search_guided(ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm, int32_t tail,
@@ -78,48 +79,23 @@ int ftl_search_guided(ftl_handle* real, ftl_handle* search, const ftl_search_par
     if (!real || !search || !b) return fail(FTL_E_INVALID, "null argument");
     if (int rc = ftlse::check_params(p)) return rc;
     if (tail < 0 || tail > INT32_MAX - p->T) return fail(FTL_E_INVALID, "ftl_search_guided: tail must be at least 0 (and T + tail an int32)");
-    if (!b->rows || !b->row_ids || !b->env_ids || !b->nominal || !b->cand || !b->action || !b->best_k || !b->best_ret || !b->out || !b->ro ||
-        !b->real_out || !b->real_bl || !b->search_bl)
-        return fail(FTL_E_INVALID, "ftl_guided_buffers: a buffer is missing");
-    if ((((uintptr_t)b->rows) | ((uintptr_t)b->nominal) | ((uintptr_t)b->cand)) & 15) return fail(FTL_E_INVALID, "rows, nominal and cand must be 16-byte aligned");
-    if (!b->ro->ret || !b->ro->steps || !b->ro->status) return fail(FTL_E_INVALID, "ftl_rollout_outputs: ret / steps / status missing");
-    const int32_t n = real->P.n_envs, K = p->K, T = p->T, cap = b->cap;
-    if (int rc = ftlse::check_size(n, K, T)) return rc;
-    if ((long long)search->P.n_envs != (long long)n * K) return fail(FTL_E_INVALID, "ftl_search_guided: the search handle must hold n * K envs");
-    if (real->device != search->device) return fail(FTL_E_INVALID, "ftl_search_guided: the two handles live on different devices");
-    if (real == search || ftl_env_layout_id(real) != ftl_env_layout_id(search))
-        return fail(FTL_E_INVALID, "ftl_search_guided: the two handles must be distinct and share one env layout (ftl_env_layout_id)");
+    if (!b->real_out || !b->real_bl || !b->search_bl) return fail(FTL_E_INVALID, "ftl_guided_buffers: a buffer is missing");
+    const ftl_search_buffers sb = {b->rows, b->row_ids, b->env_ids, b->nominal, b->cand, b->action, b->best_k, b->best_ret, b->out, b->ro};
+    if (int rc = ftlse::check_buffers("ftl_guided_buffers", "ftl_search_guided", real, search, p, sb)) return rc;
+    const int32_t n = real->P.n_envs, K = p->K, cap = b->cap;
     if (cap < 2) return fail(FTL_E_INVALID, "baseline follower: cap must be at least 2");
     if (b->real_bl_bytes < (size_t)n * baseline_row_bytes(cap) || b->search_bl_bytes < (size_t)n * K * baseline_row_bytes(cap))
         return fail(FTL_E_INVALID, "baseline follower: state buffer too small (ftl_baseline_bytes)");
     if ((((uintptr_t)b->real_bl) | ((uintptr_t)b->search_bl)) & 15) return fail(FTL_E_INVALID, "ftl_search_guided: the follower buffers must be 16-byte aligned");
-    for (const ftl_outputs* o : {b->out, b->real_out})
-        if (!o->obs_num || !o->target || !o->reward || !o->done || !o->status || (search->P.lasers_len > 0 && !o->lasers))
-            return fail(FTL_E_INVALID, "output arrays missing");
-    if (!real->bound || !search->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
-    if (!real->have_scen || !search->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
-
-    const int32_t nk = n * K;
-    int rc = ftl_pack_envs(real, b->env_ids, n, b->rows, stream);
+    if (int rc = ftlse::check_handles(real, search, {b->out, b->real_out})) return rc;
+    // the default plan is the zero residual: the baseline itself
+    int rc = ftlse::rounds(real, search, p, call, warm, 0.0, true, sb, stream, [&] {
+        if (int rc = ftl_guided_fanout(real, search, K, b->real_out, b->out, b->real_bl, b->real_bl_bytes, b->search_bl, b->search_bl_bytes, cap, stream))
+            return rc;
+        return ftl_rollout_guided(search, p->T, tail, p->gamma, b->out, b->ro, b->search_bl, b->search_bl_bytes, cap, b->cand, (int64_t)n * K * 16, nullptr, 0,
+                                  FTL_STEP_NO_SENSORS, stream);
+    });
     if (rc) return rc;
-    rc = ftlse::begin(real, b->rows, n, T, call, warm, 0.0, b->nominal, stream);     // the default plan is the zero residual: the baseline itself
-    if (rc) return rc;
-    const uint32_t uflags = (p->flags & FTL_SEARCH_OWN_STREAM) ? (uint32_t)FTL_ENV_OWN_STREAM : 0u;
-    double s = p->spread;
-    for (int32_t it = 0; it < p->iters; it++) {
-        rc = ftlse::sample(real, b->rows, n, p, call, it, s, true, b->nominal, b->cand, stream);
-        if (rc) return rc;
-        rc = ftl_unpack_envs_from(search, b->rows, b->row_ids, b->env_ids, nk, uflags, stream);
-        if (rc) return rc;
-        rc = ftl_guided_fanout(real, search, K, b->real_out, b->out, b->real_bl, b->real_bl_bytes, b->search_bl, b->search_bl_bytes, cap, stream);
-        if (rc) return rc;
-        rc = ftl_rollout_guided(search, T, tail, p->gamma, b->out, b->ro, b->search_bl, b->search_bl_bytes, cap, b->cand, (int64_t)nk * 16, nullptr, 0,
-                                FTL_STEP_NO_SENSORS, stream);
-        if (rc) return rc;
-        rc = ftl_search_select(search, b->ro->ret, n, K, T, b->cand, b->nominal, b->best_k, b->best_ret, stream);
-        if (rc) return rc;
-        s = s * p->decay;
-    }
     // last, so that every round fanned out the follower rows as they were before this decision: books the real follower's step exactly once
     return ftl_baseline_act_guided(real, b->real_out, b->real_bl, b->real_bl_bytes, cap, b->nominal, b->action, stream);
 }

@@ -161,9 +161,7 @@ int ftl_queue_start(ftl_handle* h, const ftl_outputs* out, void* stream) {
     int rc = start_chosen(h, out, stream, ftl_queue_choose, r);
     if (rc) return rc;
     hipLaunchKernelGGL(ftlq::ftl_queue_park_kernel, dim3((unsigned)((r.n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ftl_queue_args(h, r));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 }  // extern "C"

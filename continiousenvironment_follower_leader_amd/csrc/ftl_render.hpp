@@ -389,8 +389,7 @@ int ftl_render(ftl_handle* h, const int32_t* env_ids, int32_t k, const ftl_rende
     if (blocks * FTL_RENDER_THREADS > 0xFFFFFFFFull) return fail(FTL_E_INVALID, "k x image size too large for one launch");
     if (!h->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
     if (!h->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     { int rc = sync_params(h); if (rc) return rc; }
     ftlr::Args A;
     A.width = rp->width; A.height = rp->height; A.scale = rp->scale; A.ox = rp->origin_x; A.oy = rp->origin_y; A.layers = rp->layers;
@@ -401,9 +400,7 @@ int ftl_render(ftl_handle* h, const int32_t* env_ids, int32_t k, const ftl_rende
     A.aligned = (rp->width % 4 == 0 && ((uintptr_t)rgb & 3) == 0) ? 1 : 0;
     hipLaunchKernelGGL(ftlr::ftl_render_list_kernel, dim3((unsigned)k), dim3(FTL_WAVE), 0, (hipStream_t)stream, h->dP, A);
     hipLaunchKernelGGL(ftlr::ftl_render_tile_kernel, dim3((unsigned)blocks), dim3(FTL_RENDER_THREADS), 0, (hipStream_t)stream, A);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 }  // extern "C"

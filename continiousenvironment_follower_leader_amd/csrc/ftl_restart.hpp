@@ -57,12 +57,11 @@ typedef int FtlChoose(ftl_handle* h, const ftl_outputs* out, const ftl_final_out
 // Allocates the handle's restart scratch at first use.
 static int restart_args(ftl_handle* h, ftlrs::Args& a, const ftl_outputs* out, const ftl_final_outputs* fin, int mode, int32_t& calls) {
     a.now = mode == ftlrs::MODE_STEP ? ++calls : calls;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     if (!h->rs.scen_idx) {
         const size_t n = (size_t)h->P.n_envs, o_list = align_up(n * 4, 256), o_ended = 2 * o_list, o_rest = o_ended + align_up(n, 256);
         char* b = nullptr;
-        e = hipMalloc((void**)&b, o_rest + align_up(n, 256));
+        hipError_t e = hipMalloc((void**)&b, o_rest + align_up(n, 256));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(restart scratch): ") + hipGetErrorString(e));
         h->rs = {(int32_t*)b, (int32_t*)(b + o_list), (uint8_t*)b + o_ended, (uint8_t*)b + o_rest};
     }

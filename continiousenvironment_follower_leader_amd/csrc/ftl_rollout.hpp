@@ -1,5 +1,7 @@
-// ftl_rollout.hpp -- T steps of an open-loop action sequence with one call (ftl_rollout, include/ftl.h).  Included by ftl_abi.hip after
-// ftl_step_final (same translation unit: it reads the handle and calls launch()).
+// ftl_rollout.hpp -- T steps of an open-loop action sequence with one call (ftl_rollout, include/ftl.h), and the one rollout loop of the
+// library: rollout_loop, which ftl_rollout calls with a pointer into the caller's sequence as the action of step t and ftl_baseline.hpp
+// (ftl_rollout_baseline, ftl_rollout_guided) with the follower's act kernel.  Included by ftl_abi.hip after ftl_step_final (same
+// translation unit: it reads the handle and calls launch()).
 //
 // The rollout is T launches of a step without auto-reset -- the first T - 1 of them without the sensor kernels -- and, after each frame
 // launch, ftl_rollout_fold_kernel: one thread per env adds the step's discounted reward to the env's return while its episode runs.  The
@@ -40,23 +42,24 @@ __global__ __launch_bounds__(256) void ftl_rollout_fold_kernel(const Args a) {
 
 }  // namespace ftlro
 
-extern "C" {
-
-size_t ftl_sizeof_rollout_outputs(void) { return sizeof(ftl_rollout_outputs); }
-
-int ftl_rollout(ftl_handle* h, const void* actions, int64_t step_bytes, int32_t encoding, int32_t T, double gamma,
-                const ftl_outputs* out, const ftl_rollout_outputs* ro, uint32_t flags, void* stream) {
-    if (!h || !actions || !out || !ro) return fail(FTL_E_INVALID, "null argument");
+// What the three rollout entries check alike, in their common order; `name` heads the messages.  (ftl_rollout has no tail: it passes 0.)
+static int rollout_check(const char* name, const ftl_rollout_outputs* ro, int32_t T, int32_t tail, uint32_t flags) {
+    if (!ro) return fail(FTL_E_INVALID, "null argument");
     if (!ro->ret || !ro->steps || !ro->status) return fail(FTL_E_INVALID, "ftl_rollout_outputs: ret / steps / status missing");
-    if (T <= 0) return fail(FTL_E_INVALID, "ftl_rollout: T must be positive");
-    if (flags & ~(uint32_t)FTL_STEP_NO_SENSORS) return fail(FTL_E_INVALID, "ftl_rollout takes no flag but FTL_STEP_NO_SENSORS (there is no auto-reset inside a rollout)");
-    if (encoding < FTL_ACTION_BOX2 || encoding > FTL_ACTION_TURN) return fail(FTL_E_INVALID, "unknown action encoding");
-    int rc = check_ready(h, out);
-    if (rc) return rc;
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (T <= 0) return fail(FTL_E_INVALID, std::string(name) + ": T must be positive");
+    if (tail < 0 || tail > INT32_MAX - T) return fail(FTL_E_INVALID, std::string(name) + ": tail must be at least 0 (and T + tail an int32)");
+    if (flags & ~(uint32_t)FTL_STEP_NO_SENSORS)
+        return fail(FTL_E_INVALID, std::string(name) + " takes no flag but FTL_STEP_NO_SENSORS (there is no auto-reset inside a rollout)");
+    return FTL_OK;
+}
+
+// The rollout loop of every entry, after its checks and set_device: T steps on `stream`, the first T - 1 of them blind, each followed by
+// the fold.  action(t) enqueues whatever decides step t and returns what the step reads: [n_envs][2] doubles, or the encoded actions.
+template <typename Action>
+static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                        uint32_t flags, void* stream, Action action) {
     if (!h->ro_alive) {
-        e = hipMalloc((void**)&h->ro_alive, align_up((size_t)h->P.n_envs, 256));
+        hipError_t e = hipMalloc((void**)&h->ro_alive, align_up((size_t)h->P.n_envs, 256));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(rollout scratch): ") + hipGetErrorString(e));
     }
     ftlro::Args a;
@@ -70,16 +73,28 @@ int ftl_rollout(ftl_handle* h, const void* actions, int64_t step_bytes, int32_t 
     call.action_kind = encoding;
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     for (int32_t t = 0; t < T; t++) {
-        call.action = (const double*)((const char*)actions + (int64_t)t * step_bytes);
+        call.action = (const double*)action(t);
         call.flags = (t < T - 1) ? (uint32_t)FTL_STEP_NO_SENSORS : flags;
-        rc = launch(h, call, stream);                           // (on a two-stream handle the caller's stream has joined the side stream)
-        if (rc) return rc;
+        // (a two-stream handle forks after what action(t) enqueued, and the caller's stream has joined the side stream before the fold)
+        if (int rc = launch(h, call, stream)) return rc;
         hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
         a.disc = a.disc * gamma;                                // disc_{t+1} = disc_t * gamma, one rounding each
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
+}
+
+extern "C" {
+
+size_t ftl_sizeof_rollout_outputs(void) { return sizeof(ftl_rollout_outputs); }
+
+int ftl_rollout(ftl_handle* h, const void* actions, int64_t step_bytes, int32_t encoding, int32_t T, double gamma,
+                const ftl_outputs* out, const ftl_rollout_outputs* ro, uint32_t flags, void* stream) {
+    if (!h || !actions || !out) return fail(FTL_E_INVALID, "null argument");
+    if (int rc = rollout_check("ftl_rollout", ro, T, 0, flags)) return rc;
+    if (encoding < FTL_ACTION_BOX2 || encoding > FTL_ACTION_TURN) return fail(FTL_E_INVALID, "unknown action encoding");
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    return rollout_loop(h, encoding, T, gamma, out, ro, flags, stream, [&](int32_t t) { return (const char*)actions + (int64_t)t * step_bytes; });
 }
 
 }  // extern "C"

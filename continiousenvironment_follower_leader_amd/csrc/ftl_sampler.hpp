@@ -144,13 +144,10 @@ int ftl_set_scenario_sampler(ftl_handle* h, const ftl_scenario_sampler* s) {
 int ftl_sampler_refresh(ftl_handle* h, void* stream) {
     if (!h) return fail(FTL_E_INVALID, "null argument");
     if (!h->sampler.attached) return fail(FTL_E_STATE, "ftl_set_scenario_sampler has not been called");
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     const ftl_scenario_sampler& s = h->sampler.v;
     hipLaunchKernelGGL(ftlsm::ftl_sampler_scan_kernel, dim3(1), dim3(FTL_SCAN_THREADS), 0, (hipStream_t)stream, s.weight, s.cdf, (int)s.count);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 int ftl_sampler_start(ftl_handle* h, const ftl_outputs* out, void* stream) {

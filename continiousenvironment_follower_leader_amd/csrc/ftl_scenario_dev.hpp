@@ -355,18 +355,15 @@ int ftl_generate_scenarios_device(const ftl_config* cfg, const ftl_scen_params* 
     const int waves = ftl_sg::n_waves(n);
     if (workspace_bytes < head + (size_t)waves * per) return fail(FTL_E_INVALID, "workspace smaller than ftl_generate_scenarios_device_workspace");
     if (n == 0) return FTL_OK;
-    hipError_t e;
     if (P.sp.fixed_route_len > 0) {
-        e = hipMemcpyAsync(workspace, sp->fixed_route, (size_t)P.sp.fixed_route_len * 16, hipMemcpyHostToDevice, (hipStream_t)stream);
+        hipError_t e = hipMemcpyAsync(workspace, sp->fixed_route, (size_t)P.sp.fixed_route_len * 16, hipMemcpyHostToDevice, (hipStream_t)stream);
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMemcpyAsync(fixed route): ") + hipGetErrorString(e));
     }
     P.sp.fixed_route = (const double*)workspace;                 // the kernel reads the device copy
     A.seeds = dev_seeds; A.out = *dev_out; A.status = dev_status;
     A.ws = (char*)workspace + head; A.ws_per_wave = per;
     hipLaunchKernelGGL(ftl_sg::ftl_scenario_gen_kernel, dim3((unsigned)waves), dim3(64), ftl_sg::lds_bytes(A, P.n_static), (hipStream_t)stream, P, A);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // ftl_search.hpp -- action search on the device (include/ftl.h: ftl_search, ftl_search_begin / _sample / _select): K candidate action
 // sequences per env, rolled out blind on clones in a second handle, the best one kept, refined with a shrinking radius.  Included by
-// ftl_abi.hip after ftl_baseline.hpp and before ftl_guided.hpp, which launches the same kernels on residuals (same translation unit: it
-// reads the handles and calls ftl_pack_envs, ftl_unpack_envs_from and ftl_rollout).  Everything heavy is those three; the kernels here
-// move a few doubles per candidate:
+// ftl_abi.hip after ftl_baseline.hpp and before ftl_guided.hpp, which searches over residuals (same translation unit: it reads the handles
+// and calls ftl_pack_envs, ftl_unpack_envs_from and ftl_rollout).  The checks both searches share (check_buffers, check_handles) and the
+// one loop over their rounds (rounds, with what a round rolls as a callable) are here; each entry keeps its own checks and its decision.
+// Everything heavy is those three calls; the kernels here move a few doubles per candidate:
 //
 // ftl_search_begin_kernel   one thread per env: the nominal sequence of this call -- the default (max speed, straight on) for a new episode,
 //                           else the last call's plan shifted by one step.  Reads one word of the env's packed row.
@@ -120,18 +121,6 @@ static int check_size(int32_t n, int32_t K, int32_t T) {
     return FTL_OK;
 }
 
-static int set_device(const ftl_handle* h) {
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    return FTL_OK;
-}
-
-static int launched() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
-}
-
 static int32_t row_word(const ftl_handle* h, int which) { return (int32_t)(h->fields[F_env_int].offset / 4 + which); }
 
 // ftl_search_begin with the default plan's speed given (ftl_search_guided starts from the zero residual)
@@ -171,6 +160,54 @@ static int sample(const ftl_handle* h, const void* rows, int32_t n, const ftl_se
     return launched();
 }
 
+// What ftl_search and ftl_search_guided check alike of the ten buffers their structs share (ftl_guided_buffers: copied into `b` by value)
+// and of the two handles, after check_params; `bufs` and `entry` head the messages
+static int check_buffers(const char* bufs, const char* entry, const ftl_handle* real, const ftl_handle* search, const ftl_search_params* p,
+                         const ftl_search_buffers& b) {
+    if (!b.rows || !b.row_ids || !b.env_ids || !b.nominal || !b.cand || !b.action || !b.best_k || !b.best_ret || !b.out || !b.ro)
+        return fail(FTL_E_INVALID, std::string(bufs) + ": a buffer is missing");
+    if ((((uintptr_t)b.rows) | ((uintptr_t)b.nominal) | ((uintptr_t)b.cand)) & 15) return fail(FTL_E_INVALID, "rows, nominal and cand must be 16-byte aligned");
+    if (!b.ro->ret || !b.ro->steps || !b.ro->status) return fail(FTL_E_INVALID, "ftl_rollout_outputs: ret / steps / status missing");
+    const int32_t n = real->P.n_envs;
+    if (int rc = check_size(n, p->K, p->T)) return rc;
+    if ((long long)search->P.n_envs != (long long)n * p->K) return fail(FTL_E_INVALID, std::string(entry) + ": the search handle must hold n * K envs");
+    if (real->device != search->device) return fail(FTL_E_INVALID, std::string(entry) + ": the two handles live on different devices");
+    if (real == search || ftl_env_layout_id(real) != ftl_env_layout_id(search))
+        return fail(FTL_E_INVALID, std::string(entry) + ": the two handles must be distinct and share one env layout (ftl_env_layout_id)");
+    return FTL_OK;
+}
+
+// ... and last of all their checks (the guided search has its own between the two): the output arrays of every struct, then the state
+static int check_handles(const ftl_handle* real, const ftl_handle* search, std::initializer_list<const ftl_outputs*> outs) {
+    for (const ftl_outputs* o : outs)
+        if (!o->obs_num || !o->target || !o->reward || !o->done || !o->status || (search->P.lasers_len > 0 && !o->lasers))
+            return fail(FTL_E_INVALID, "output arrays missing");
+    if (!real->bound || !search->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
+    if (!real->have_scen || !search->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
+    return FTL_OK;
+}
+
+// The rounds of both searches on `stream`: the real envs packed, the start plan (default: `speed`, straight on), then per round the draws
+// (`residual`: sample), the rows unpacked to the clones, roll() -- whatever leaves the clones' returns in b.ro->ret --, the selection.
+// Leaves the plan in b.nominal; the decision is the caller's.
+template <typename Roll>
+static int rounds(const ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm, double speed, bool residual,
+                  const ftl_search_buffers& b, void* stream, Roll roll) {
+    const int32_t n = real->P.n_envs, K = p->K, T = p->T;
+    if (int rc = ftl_pack_envs(real, b.env_ids, n, b.rows, stream)) return rc;
+    if (int rc = begin(real, b.rows, n, T, call, warm, speed, b.nominal, stream)) return rc;
+    const uint32_t uflags = (p->flags & FTL_SEARCH_OWN_STREAM) ? (uint32_t)FTL_ENV_OWN_STREAM : 0u;
+    double s = p->spread;
+    for (int32_t it = 0; it < p->iters; it++) {
+        if (int rc = sample(real, b.rows, n, p, call, it, s, residual, b.nominal, b.cand, stream)) return rc;
+        if (int rc = ftl_unpack_envs_from(search, b.rows, b.row_ids, b.env_ids, n * K, uflags, stream)) return rc;
+        if (int rc = roll()) return rc;
+        if (int rc = ftl_search_select(search, b.ro->ret, n, K, T, b.cand, b.nominal, b.best_k, b.best_ret, stream)) return rc;
+        s = s * p->decay;
+    }
+    return FTL_OK;
+}
+
 }  // namespace ftlse
 
 extern "C" {
@@ -193,51 +230,24 @@ int ftl_search_select(const ftl_handle* h, const double* ret, int32_t n, int32_t
     if (!h || !ret || !cand || !nominal || !best_k || !best_ret) return fail(FTL_E_INVALID, "null argument");
     if (int rc = ftlse::check_size(n, K, T)) return rc;
     if ((((uintptr_t)nominal) | ((uintptr_t)cand)) & 15) return fail(FTL_E_INVALID, "nominal and cand must be 16-byte aligned");
-    if (int rc = ftlse::set_device(h)) return rc;
+    if (int rc = set_device(h)) return rc;
     ftlse::SelectArgs a;
     a.ret = ret; a.cand = cand; a.nominal = nominal; a.best_k = best_k; a.best_ret = best_ret; a.n = n; a.K = K; a.T = T;
     hipLaunchKernelGGL(ftlse::ftl_search_select_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-    return ftlse::launched();
+    return launched();
 }
 
 int ftl_search(const ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm,
                const ftl_search_buffers* b, void* stream) {
     if (!real || !search || !b) return fail(FTL_E_INVALID, "null argument");
     if (int rc = ftlse::check_params(p)) return rc;
-    if (!b->rows || !b->row_ids || !b->env_ids || !b->nominal || !b->cand || !b->action || !b->best_k || !b->best_ret || !b->out || !b->ro)
-        return fail(FTL_E_INVALID, "ftl_search_buffers: a buffer is missing");
-    if ((((uintptr_t)b->rows) | ((uintptr_t)b->nominal) | ((uintptr_t)b->cand)) & 15) return fail(FTL_E_INVALID, "rows, nominal and cand must be 16-byte aligned");
-    if (!b->ro->ret || !b->ro->steps || !b->ro->status) return fail(FTL_E_INVALID, "ftl_rollout_outputs: ret / steps / status missing");
-    const int32_t n = real->P.n_envs, K = p->K, T = p->T;
-    if (int rc = ftlse::check_size(n, K, T)) return rc;
-    if ((long long)search->P.n_envs != (long long)n * K) return fail(FTL_E_INVALID, "ftl_search: the search handle must hold n * K envs");
-    if (real->device != search->device) return fail(FTL_E_INVALID, "ftl_search: the two handles live on different devices");
-    if (real == search || ftl_env_layout_id(real) != ftl_env_layout_id(search))
-        return fail(FTL_E_INVALID, "ftl_search: the two handles must be distinct and share one env layout (ftl_env_layout_id)");
-    const ftl_outputs* o = b->out;
-    if (!o->obs_num || !o->target || !o->reward || !o->done || !o->status || (search->P.lasers_len > 0 && !o->lasers))
-        return fail(FTL_E_INVALID, "output arrays missing");
-    if (!real->bound || !search->bound) return fail(FTL_E_STATE, "ftl_bind_state has not been called");
-    if (!real->have_scen || !search->have_scen) return fail(FTL_E_STATE, "ftl_load_scenarios has not been called");
-
-    const int32_t nk = n * K;
-    int rc = ftl_pack_envs(real, b->env_ids, n, b->rows, stream);
+    if (int rc = ftlse::check_buffers("ftl_search_buffers", "ftl_search", real, search, p, *b)) return rc;
+    if (int rc = ftlse::check_handles(real, search, {b->out})) return rc;
+    const int32_t n = real->P.n_envs;
+    int rc = ftlse::rounds(real, search, p, call, warm, real->P.cfg.follower.max_speed, false, *b, stream, [&] {
+        return ftl_rollout(search, b->cand, (int64_t)n * p->K * 16, FTL_ACTION_BOX2, p->T, p->gamma, b->out, b->ro, FTL_STEP_NO_SENSORS, stream);
+    });
     if (rc) return rc;
-    rc = ftl_search_begin(real, b->rows, n, T, call, warm, b->nominal, stream);
-    if (rc) return rc;
-    const uint32_t uflags = (p->flags & FTL_SEARCH_OWN_STREAM) ? (uint32_t)FTL_ENV_OWN_STREAM : 0u;
-    double s = p->spread;
-    for (int32_t it = 0; it < p->iters; it++) {
-        rc = ftl_search_sample(real, b->rows, n, p, call, it, s, b->nominal, b->cand, stream);
-        if (rc) return rc;
-        rc = ftl_unpack_envs_from(search, b->rows, b->row_ids, b->env_ids, nk, uflags, stream);
-        if (rc) return rc;
-        rc = ftl_rollout(search, b->cand, (int64_t)nk * 16, FTL_ACTION_BOX2, T, p->gamma, b->out, b->ro, FTL_STEP_NO_SENSORS, stream);
-        if (rc) return rc;
-        rc = ftl_search_select(search, b->ro->ret, n, K, T, b->cand, b->nominal, b->best_k, b->best_ret, stream);
-        if (rc) return rc;
-        s = s * p->decay;
-    }
     hipError_t e = hipMemcpyAsync(b->action, b->nominal, (size_t)n * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream);   // nominal[0]
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
     return FTL_OK;

@@ -156,15 +156,12 @@ static Args make_args(const ftl_handle* h) {
 }
 
 static int snap_launch(const ftl_handle* h, Args& a, bool unpack, void* stream) {
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    if (int rc = set_device(h)) return rc;
     const unsigned per_wg = FTL_SNAP_THREADS * FTL_SNAP_UNROLL;
     const dim3 grid((unsigned)a.k, (unsigned)((a.row16 + per_wg - 1) / per_wg)), block(FTL_SNAP_THREADS);
     if (unpack) hipLaunchKernelGGL(ftl_snapshot_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(ftl_snapshot_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("kernel launch: ") + hipGetErrorString(e));
-    return FTL_OK;
+    return launched();
 }
 
 static int snap_check(const ftl_handle* h, const int32_t* env_ids, int32_t k, const void* rows, uint32_t flags) {

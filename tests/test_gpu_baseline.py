@@ -231,6 +231,14 @@ def test_rollout_on_a_two_stream_handle(monkeypatch):
         assert torch.equal(env.state_field(k), one["state"][k]), k
     assert torch.equal(f.state, one["fol"]) and torch.equal(torch.stack(played), one["acts"])
     assert bool(one["ro"][1].eq(T).any())
+    env.restore(snap, slot_stats=True)                             # ftl_rollout on the same handle: the open-loop rollout of the record
+    r2 = env.rollout(one["acts"], gamma=gamma)
+    for k in OUT:
+        assert torch.equal(getattr(env, k), one["out"][k]), ("rollout", k)
+    for x, y, k in zip(r2, one["ro"], ("ret", "steps", "status")):
+        assert torch.equal(x, y), ("rollout", k)
+    for k in FIELDS:
+        assert torch.equal(env.state_field(k), one["state"][k]), ("rollout", k)
     env.close()
 
 
