@@ -65,9 +65,14 @@ bool plan_route(const Grid& g, int sx, int sy, int gx, int gy, int max_iterat, s
         uint8_t* dst = &blocked[(size_t)(x + 1) * W2 + 1];
         for (int y = 0; y < g.cols; y++) dst[y] = src[y];
     }
-    const int nb = g.rows + g.cols + 8;                      // keys stay below rows + cols (a path never needs more moves than that)
-    if ((int)bucket.size() < nb) bucket.resize((size_t)nb);
-    for (int i = 0; i < nb; i++) bucket[(size_t)i].clear();
+    // Keys have no useful bound: around a dense field of rocks a shortest route is far longer than rows + cols moves (100 rocks on
+    // 150 x 100 cells: costs up to 370 on 0.5 % of the seeds), so the bucket array grows with the keys.  Bucket bi only ever pushes into
+    // buckets <= bi + 2 (key < bi + 1, move <= sqrt 2): the array is sized BEFORE the reference to bucket bi is taken and no push can
+    // move it.  `dirty` = buckets written by the previous call of this thread -- the only ones that need clearing.
+    static thread_local int dirty = 0;
+    for (int i = 0; i < dirty; i++) bucket[(size_t)i].clear();
+    if (bucket.size() < 3) bucket.resize(3);
+    int top = 0;                                             // the last bucket that holds an entry (a local: the loop below is hot)
     const int goal = (gx + 1) * W2 + gy + 1, start = (sx + 1) * W2 + sy + 1;
     const double SQ2 = sqrt(2.0);
     // neighbour order of Map.get_neighbors (dstar.py:62-74): i = -1..1 outer, j = -1..1 inner
@@ -76,7 +81,8 @@ bool plan_route(const Grid& g, int sx, int sy, int gx, int gy, int max_iterat, s
     h[(size_t)goal] = 0.0;
     bucket[0].push_back(Item{0.0, goal});
     bool reached = false;
-    for (int bi = 0; bi < nb && !reached; bi++) {
+    for (int bi = 0; bi <= top && !reached; bi++) {
+        if (bucket.size() < (size_t)bi + 3) bucket.resize(std::max((size_t)bi + 3, 2 * bucket.size()));
         std::vector<Item>& B = bucket[(size_t)bi];
         if (B.empty()) continue;
         std::stable_sort(B.begin(), B.end(), [](const Item& a, const Item& b) { return a.k < b.k; });
@@ -91,13 +97,14 @@ bool plan_route(const Grid& g, int sx, int sy, int gx, int gy, int max_iterat, s
                 const double hn = it.k + dcost[d];
                 if (hn < h[(size_t)nid]) {
                     h[(size_t)nid] = hn; parent[(size_t)nid] = it.id;
-                    const int to = (int)hn;
-                    if (to >= nb) return false;              // (cannot happen on a grid this size)
+                    const int to = (int)hn;                  // bi + 1 or bi + 2
+                    top = to > top ? to : top;
                     bucket[(size_t)to].push_back(Item{hn, nid});
                 }
             }
         }
     }
+    dirty = top + 1;
     if (!reached) return false;                               // unreachable goal: the reference would never return
     int cur = start, iter = 0;
     while (cur != goal) {

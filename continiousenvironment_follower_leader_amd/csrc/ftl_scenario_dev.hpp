@@ -14,9 +14,9 @@
 //   order (pop index = pops so far + rank), then its neighbours are relaxed in two phases -- a 64-bit atomic minimum over the bit pattern
 //   of h (all h >= 0, so the bits order like the doubles), then, among the relaxations that reached the final h of a node lowered in this
 //   bucket, an atomic minimum over the tag pop_index * 8 + d.  The winner of the tag is the host's parent (nid - doff[d]).  Nodes popped
-//   after the start in its own bucket do not relax (the host stops at the start).  A bucket close enough to the end of the host's bucket
-//   array that a relaxation could overflow it (the `to >= nb` quirk, ftl_scenario.cpp plan_route) is run by lane 0 in pop order, with
-//   the host's own early return -- never on a real grid, but the outputs stay the host's.
+//   after the start in its own bucket do not relax (the host stops at the start).  Keys have no bound but the grid's: the host's bucket
+//   array grows with them (routes around dense rocks cost far more than rows + cols), here a bucket is a range of h whatever its
+//   index, and the tag fits 32 bits as long as pops * 8 does (N2 <= FTL_SG_MAX_CELLS = 65536).
 //
 // Every loop is bounded: the rejection samplers (rocks, finish points) and randbelow stop after FTL_SG_MAX_ATTEMPTS draws (DevicePolicy) and
 // mark the scenario FTL_SCEN_GEN_LIMIT (unusable; the host never gets there on a real seed), a bucket closes at least one node, the parent
@@ -76,7 +76,6 @@ __device__ bool plan_route_wave(const Params& P, const FtlSgArgs& A, Shared& S, 
     if (sx == gx && sy == gy) return true;
     const int goal = (gx + 1) * W2 + gy + 1, start = (sx + 1) * W2 + sy + 1;
     if (bit(obst, goal) || bit(obst, start)) return false;
-    const int nb = rows + cols + 8;
     const double INF = 1e300;
     const unsigned long long INFB = (unsigned long long)__double_as_longlong(INF);
     const double SQ2 = sqrt(2.0);
@@ -138,68 +137,43 @@ __device__ bool plan_route_wave(const Params& P, const FtlSgArgs& A, Shared& S, 
         has_start = S.start_rank != 0x7fffffff;
         const int srank = S.start_rank;
         const int* rank = open + N2;
-        if (bi + 2 >= nb) {
-            // near the end of the host's bucket array: lane 0 pops in order with the host's early return on an overflowing push
-            if (lane == 0) {
-                for (int r = 0; r < nf && r < srank; r++) {
-                    int id = -1;
-                    for (int j = 0; j < nf; j++) if (rank[j] == r) { id = front[j]; break; }
-                    const double k = hh[id];
-                    for (int d = 0; d < 8; d++) {
-                        const int nid = id + doff[d];
-                        if (bit(obst, nid) || bit(closed, nid)) continue;
-                        const double hn = k + dcost[d];
-                        if (hn < hh[nid]) {
-                            const bool fresh = hh[nid] == INF;
-                            hh[nid] = hn; tag[nid] = (base + (unsigned)r) * 8u + (unsigned)d;
-                            if ((int)hn >= nb) { S.fail = 1; break; }
-                            if (fresh) open[S.m_open++] = nid;
-                        }
-                    }
-                    if (S.fail) break;
-                }
-            }
-            wave_sync();
-            if (S.fail) return false;
-        } else {
-            // phase A: h = min over the relaxations (64-bit minimum on the bit pattern); a lowered node's tag is reset, a new one opened
-            for (int c0 = 0; c0 < nf; c0 += 64) {
-                const int i = c0 + lane;
-                if (i < nf && rank[i] < srank) {
-                    const int id = front[i];
-                    const double k = hh[id];
-                    for (int d = 0; d < 8; d++) {
-                        const int nid = id + doff[d];
-                        if (bit(obst, nid) || bit(closed, nid)) continue;
-                        const double hn = k + dcost[d];
-                        const unsigned long long hb = (unsigned long long)__double_as_longlong(hn);
-                        const unsigned long long old = atomicMin((unsigned long long*)&hh[nid], hb);
-                        if (hb < old) {
-                            tag[nid] = 0xffffffffu;
-                            if (old == INFB) open[atomicAdd(&S.m_open, 1)] = nid;
-                        }
+        // phase A: h = min over the relaxations (64-bit minimum on the bit pattern); a lowered node's tag is reset, a new one opened
+        for (int c0 = 0; c0 < nf; c0 += 64) {
+            const int i = c0 + lane;
+            if (i < nf && rank[i] < srank) {
+                const int id = front[i];
+                const double k = hh[id];
+                for (int d = 0; d < 8; d++) {
+                    const int nid = id + doff[d];
+                    if (bit(obst, nid) || bit(closed, nid)) continue;
+                    const double hn = k + dcost[d];
+                    const unsigned long long hb = (unsigned long long)__double_as_longlong(hn);
+                    const unsigned long long old = atomicMin((unsigned long long*)&hh[nid], hb);
+                    if (hb < old) {
+                        tag[nid] = 0xffffffffu;
+                        if (old == INFB) open[atomicAdd(&S.m_open, 1)] = nid;
                     }
                 }
             }
-            wave_sync();
-            // phase B: the first setter of the final h, in pop order, among nodes lowered in this bucket (their tag is >= base * 8)
-            for (int c0 = 0; c0 < nf; c0 += 64) {
-                const int i = c0 + lane;
-                if (i < nf && rank[i] < srank) {
-                    const int id = front[i];
-                    const double k = hh[id];
-                    const unsigned pk = (base + (unsigned)rank[i]) * 8u;
-                    for (int d = 0; d < 8; d++) {
-                        const int nid = id + doff[d];
-                        if (bit(obst, nid) || bit(closed, nid)) continue;
-                        const double hn = k + dcost[d];
-                        if (hn == hh[nid] && tag[nid] >= base * 8u)
-                            atomicMin(&tag[nid], pk + (unsigned)d);
-                    }
-                }
-            }
-            wave_sync();
         }
+        wave_sync();
+        // phase B: the first setter of the final h, in pop order, among nodes lowered in this bucket (their tag is >= base * 8)
+        for (int c0 = 0; c0 < nf; c0 += 64) {
+            const int i = c0 + lane;
+            if (i < nf && rank[i] < srank) {
+                const int id = front[i];
+                const double k = hh[id];
+                const unsigned pk = (base + (unsigned)rank[i]) * 8u;
+                for (int d = 0; d < 8; d++) {
+                    const int nid = id + doff[d];
+                    if (bit(obst, nid) || bit(closed, nid)) continue;
+                    const double hn = k + dcost[d];
+                    if (hn == hh[nid] && tag[nid] >= base * 8u)
+                        atomicMin(&tag[nid], pk + (unsigned)d);
+                }
+            }
+        }
+        wave_sync();
         base += (unsigned)nf;
         reached = has_start;
     }

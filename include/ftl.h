@@ -255,7 +255,10 @@ typedef struct ftl_scenarios {
  * in the reference (ENV:1537 is D*-only), so FTL_SCEN_FOUND is set whenever the route has at least two points.
  * The (dstar) route is a shortest 8-connected path on the reference's cost model (1 / sqrt 2 per move, inflated obstacle
  * cells); among equal-cost paths the reference's choice depends on CPython set iteration order over object ids and is
- * not reproducible -- the generator breaks such ties by insertion order (documented as unpinned in DESIGN.md). */
+ * not reproducible -- the generator breaks such ties by insertion order (documented as unpinned in DESIGN.md).  The route's cost has
+ * no bound but the grid's: around dense rocks it exceeds rows + cols several times over (370 on the 150 x 100 grid with 100 rocks), and
+ * both generators find such a route as the reference does; it takes a route_cap to match (FTL_SCEN_ROUTE_OVERFLOW otherwise).  A
+ * finish point the leader cannot reach leaves FTL_SCEN_FOUND clear and the route empty (the reference's planner would not return). */
 typedef struct ftl_scen_params {
     int32_t width, height;                /* game_width, game_height */
     int32_t step_grid, obstacle_number;   /* obstacle_number is 0 when add_obstacles is False (ENV:323-324) */

@@ -15,6 +15,7 @@ Determinism policy:
 Nothing here is imported by the product; the GPU box never runs this file.
 
 usage:  python tests/golden/gen/make_golden.py [--only NAME] [--pool P] [--jobs J]
+        python tests/golden/gen/make_golden.py --pool-config D --pool-seeds LIST --pool-name D_long    (pool_D_long.npz: these seeds only)
         python tests/golden/gen/make_golden.py --fuzz LO:HI [--jobs J]      (the configs of tests/fuzz_configs.py: fuzz_s{seed}.npz)
 """
 import argparse
@@ -746,13 +747,68 @@ def pool_worker(args):
     return recs
 
 
-def make_pool(config_name, n_seeds, jobs, seed0=0):
-    """Scenario pool for bench.py / full-size property tests: post-reset scenarios of the reference
-    for python seeds seed0..seed0+n_seeds-1 (D*-failed scenarios dropped)."""
+def _seed_child(conn, config_name, seed):
+    r = Runner(config_name)
+    r.reset(seed)
+    sc = scenario_of(r.game)
+    sc["seed"] = np.array(seed)
+    conn.send(sc)
+
+
+def seed_worker(args):
+    """One reset() of the reference in a child process of its own, ended after `limit` seconds: with an unreachable finish point the
+    reference's planner never returns, and a seed list written by hand may name such a seed by mistake."""
     import multiprocessing as mp
-    chunks = [list(range(seed0 + i, seed0 + n_seeds, jobs)) for i in range(jobs)]
-    with mp.Pool(jobs) as p:
-        parts = p.map(pool_worker, [(config_name, c) for c in chunks])
+    config_name, seed, limit = args
+    recv, send = mp.Pipe(False)
+    p = mp.Process(target=_seed_child, args=(send, config_name, seed))
+    p.start()
+    send.close()
+    try:
+        sc = recv.recv() if recv.poll(limit) else None
+    except EOFError:
+        sc = None
+    p.join(5)
+    if p.is_alive():
+        p.kill()
+        p.join()
+    if sc is None:
+        raise RuntimeError("seed %d of config %s: no scenario from the reference within %d s (exit code %s)" % (seed, config_name, limit, p.exitcode))
+    return sc
+
+
+def parse_seeds(text):
+    """"0:42,147,302" -> [0, ..., 41, 147, 302] (LO:HI is half open), duplicates dropped, ascending."""
+    out = set()
+    for part in text.split(","):
+        if ":" in part:
+            lo, hi = (int(x) for x in part.split(":"))
+            out.update(range(lo, hi))
+        elif part.strip():
+            out.add(int(part))
+    return sorted(out)
+
+
+def make_pool(config_name, n_seeds, jobs, seed0=0, seeds=None, name=None, seed_limit=120):
+    """Scenario pool for bench.py / full-size property tests: post-reset scenarios of the reference
+    for python seeds seed0..seed0+n_seeds-1 (D*-failed scenarios dropped).
+    `seeds`: an explicit list instead, one child process with a time limit per seed (seed_worker); the file then also says what became
+    of EVERY requested seed -- `requested_seed`, `found` (the reference's found_target_point) and `done_at_reset`, in list order."""
+    import multiprocessing as mp
+    extra = {}
+    if seeds is not None:
+        from multiprocessing.pool import ThreadPool
+        with ThreadPool(jobs) as p:                    # the threads only wait for their child processes
+            every = p.map(seed_worker, [(config_name, s, seed_limit) for s in seeds])
+        extra = dict(requested_seed=np.array(seeds, dtype=np.int32),
+                     found=np.array([bool(r["found_target_point"]) for r in every]),
+                     done_at_reset=np.array([bool(r["done_at_reset"]) for r in every]))
+        parts = [[r for r in every if bool(r["found_target_point"]) and not bool(r["done_at_reset"])]]
+        n_seeds = len(seeds)
+    else:
+        chunks = [list(range(seed0 + i, seed0 + n_seeds, jobs)) for i in range(jobs)]
+        with mp.Pool(jobs) as p:
+            parts = p.map(pool_worker, [(config_name, c) for c in chunks])
     recs = sorted([r for part in parts for r in part], key=lambda r: int(r["seed"]))
     P = len(recs)
     S = recs[0]["static_rects"].shape[0]
@@ -774,8 +830,9 @@ def make_pool(config_name, n_seeds, jobs, seed0=0):
         out["init_traj_len"][i] = len(r["init_traj"])
     meta = dict(config=config_name, n_seeds=n_seeds, seed0=seed0, kept=P, S=S, R=R,
                 kwargs=json.loads(json.dumps(CONFIGS[config_name]["kwargs"], default=str)))
+    out.update(extra)
     out["meta"] = np.array(json.dumps(meta))
-    path = os.path.join(GOLDEN, "pool_%s.npz" % config_name)
+    path = os.path.join(GOLDEN, "pool_%s.npz" % (name or config_name))
     np.savez_compressed(path, **out)
     print("pool", config_name, "kept", P, "of", n_seeds, "->", path, os.path.getsize(path), "bytes")
 
@@ -785,10 +842,18 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--pool", type=int, default=0, help="also (re)generate scenario pools with this many seeds")
     ap.add_argument("--pool-config", default="B")
+    ap.add_argument("--pool-seeds", default=None, metavar="LIST", help="record a pool for these python seeds instead (\"0:42,147,302\"; LO:HI half open), "
+                    "one child process with a time limit per seed; needs --pool-name")
+    ap.add_argument("--pool-name", default=None, help="write pool_NAME.npz (default: the name of the config)")
+    ap.add_argument("--seed-timeout", type=int, default=120, help="seconds one reset() of --pool-seeds may take")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--no-episodes", action="store_true")
     ap.add_argument("--fuzz", default=None, metavar="LO:HI", help="record the configs of tests/fuzz_configs.py for these seeds instead (fuzz_s{seed}.npz)")
     a = ap.parse_args()
+    if a.pool_seeds:
+        assert a.pool_name, "--pool-seeds writes a pool of its own: give it a --pool-name"
+        make_pool(a.pool_config, 0, a.jobs, seeds=parse_seeds(a.pool_seeds), name=a.pool_name, seed_limit=a.seed_timeout)
+        return
     if a.fuzz:
         lo, hi = (int(x) for x in a.fuzz.split(":"))
         import multiprocessing as mp

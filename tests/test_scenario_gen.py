@@ -6,6 +6,7 @@ Pinned bit-exactly: which seeds yield a usable scenario, walls + rocks, robots, 
 several equal-cost routes dstar.py returns depends on CPython object ids (set iteration order), so identity of the
 route is checked statistically (>= 99 % here) and a scenario whose route differs is compared up to the route."""
 import ctypes as C
+import functools
 import json
 import os
 import shutil
@@ -17,7 +18,8 @@ import pytest
 from continiousenvironment_follower_leader_amd import _lib, abi
 from continiousenvironment_follower_leader_amd.scenario import generate_scenarios, scen_params
 from golden_util import GOLDEN, config_for, episode_names, load_episode, scenario_arrays
-from test_scenario_gen_device import SEEDS
+import planner_numpy
+from test_scenario_gen_device import (DENSE, DRY_D, LOST_D, SEEDS, check_against_pool_d_long, check_route_cap, load_pool_d_long, long_cfg)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -121,6 +123,77 @@ def test_generator_route_properties_and_threads():
         assert a["init_traj_len"][i] == int(np.float32(d) / (sp.trajectory_saving_period * sp.leader_max_speed)) or True
 
 
+# ---- long routes and the planner's two "not found" exits (the seed lists, configs and shared criteria: test_scenario_gen_device.py) -----------
+@functools.lru_cache(maxsize=None)
+def _long_worlds(name):
+    """Seeds 0..4095 of config D / 0..3999 of a dense variant, one pass of the 16-thread generator; shared by the tests below, read only."""
+    cfg = long_cfg(name)
+    g = generate_scenarios(cfg, np.arange(4096 if name == "D" else 4000), n_threads=16)
+    for v in g.values():
+        v.setflags(write=False)
+    return cfg, g
+
+
+def test_generator_matches_reference_pool_long_routes():
+    """The reference's reset() on seeds 0..41 of config D and on the 22 seeds whose route costs more than rows + cols + 8."""
+    z, cfg = load_pool_d_long()
+    g = generate_scenarios(cfg, z["requested_seed"].astype(np.int64), n_threads=8)
+    check_against_pool_d_long(g, z, cfg)
+
+
+def test_generator_unreachable_finish_point():
+    """The open list runs dry: not found, empty route, unusable (the reference's planner would not return)."""
+    _, g = _long_worlds("D")
+    for s in DRY_D:
+        assert int(g["status"][s]) == abi.SCEN_DONE_AT_RESET and g["route_len"][s] == 0 and not g["usable"][s], s
+        assert not g["route"][s].any()
+
+
+def test_generator_long_routes_found_nothing_else_changes():
+    """Against the status bytes recorded while the open list stopped at rows + cols + 8 buckets (tests/golden/gen_status_D_capped.npz):
+    the 22 seeds of LOST_D, "not found" there, are found and usable; every other seed of 0..4095 keeps its status byte."""
+    _, g = _long_worlds("D")
+    before = np.load(GOLDEN + "/gen_status_D_capped.npz")["status"]
+    changed = np.nonzero(before != g["status"])[0]
+    assert changed.tolist() == list(LOST_D)
+    assert (before[changed] == abi.SCEN_DONE_AT_RESET).all() and (g["status"][changed] == abi.SCEN_FOUND).all() and g["usable"][changed].all()
+    assert int(((g["status"] & abi.SCEN_FOUND) != 0).sum()) == int(((before & abi.SCEN_FOUND) != 0).sum()) + len(LOST_D)
+
+
+def test_generator_route_cap_truncates_long_route():
+    check_route_cap(*[generate_scenarios(long_cfg("D", cap), [2369], n_threads=1) for cap in (256, 512)])
+
+
+@pytest.mark.parametrize("name", ["D"] + sorted(DENSE))
+def test_generator_routes_are_shortest_paths(name):
+    """Every found route against tests/planner_numpy.py: the cheap checks (leader's cell, 8-connected, no blocked cell) on all of them, the
+    heapq Dijkstra on the 24 longest and on every k-th of the rest (48 at the most; 0.1-0.2 s each)."""
+    cfg, g = _long_worlds(name)
+    sp = scen_params(cfg)
+    sg = sp.step_grid
+    found = np.nonzero(((g["status"][:4000] & abi.SCEN_FOUND) != 0) & (g["route_len"][:4000] > 0))[0]
+    assert not (g["status"][found] & abi.SCEN_ROUTE_OVERFLOW).any()
+    order = found[np.argsort(-g["route_len"][found], kind="stable")]
+    rest = order[24:]
+    picked = set(order[:24].tolist()) | set(rest[::max(1, -(-len(rest) // 24))].tolist())
+    assert len(picked) <= 48
+    checked, longest = 0, 0.0
+    for i in found.tolist():
+        blocked = planner_numpy.inflated_grid(g["static_rects"][i], sp)
+        cells = planner_numpy.route_cells(g["route"][i], g["route_len"][i], sg)
+        planner_numpy.check_route_cells(cells, blocked, g["robot_pos"][i, 0], sg)
+        if i in picked:
+            try:
+                cost, _ = planner_numpy.check_route_optimal(cells, blocked)
+            except AssertionError as e:
+                raise AssertionError("seed %d: %s" % (i, e))
+            checked += 1
+            longest = max(longest, cost)
+    print("%s: %d found worlds, %d against Dijkstra, longest checked route costs %.2f (rows + cols + 8 = %d)"
+          % (name, len(found), checked, longest, sp.width // sg + sp.height // sg + 8))
+    assert checked >= 40, checked
+
+
 @pytest.fixture(scope="module")
 def policy_program(tmp_path_factory):
     """tests/host/scenario_policy_main.cpp + csrc/ftl_scenario.cpp built with FTL_SCEN_DEVICE_POLICY under AddressSanitizer and UBSan: the
@@ -137,7 +210,8 @@ def policy_program(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("name", ["B_s1_chase", "Bmep_s2_chase", "Btraj_s3_chase"])     # one finish point, three, a caller's route
+# one finish point, three, a caller's route; D: 100 rocks -- the planner's bucket array grows past rows + cols + 8 (LOST_D, DRY_D)
+@pytest.mark.parametrize("name", ["B_s1_chase", "Bmep_s2_chase", "Btraj_s3_chase", "D_s2_chase"])
 def test_device_policy_matches_product_on_cpu(policy_program, tmp_path, name):
     """What lane 0 of the device generator computes (csrc/ftl_scenario_core.hpp with DevicePolicy) equals the product's host generator
     (HostPolicy: glibc, no cap) on the seeds of test_scenario_gen_device.py -- every array, every status byte, no FTL_SCEN_GEN_LIMIT --
@@ -146,6 +220,7 @@ def test_device_policy_matches_product_on_cpu(policy_program, tmp_path, name):
     cfg = config_for(meta, scen_route_len=256)
     sp = scen_params(cfg)
     seeds = np.ascontiguousarray(SEEDS, np.int64)
+    assert set(LOST_D) | set(DRY_D) <= set(seeds.tolist())          # (D: where a dangling reference into the growing bucket array would show)
     fixed = np.ctypeslib.as_array(C.cast(sp.fixed_route, C.POINTER(C.c_double)), (sp.fixed_route_len * 2,)) if sp.planner == 2 else np.zeros(0)
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
     src.write_bytes(bytes(cfg.c) + bytes(sp) + np.int64(len(seeds)).tobytes() + seeds.tobytes() + fixed.astype(np.float64).tobytes())

@@ -19,6 +19,73 @@ KEYS_EXACT = ("static_rects", "robot_pos", "robot_dir", "robot_rect", "route", "
 HOST_CONFIGS = ("B_s1_chase", "B3_s8_chase", "B6_s2_chase", "D_s2_chase", "E_s3_chase", "F_s1_chase", "Bmep_s2_chase", "Btraj_s3_chase")
 SEEDS = np.concatenate([np.arange(4096), [-1, -2, -7, -4097, -(1 << 40) - 3, 1 << 32, (1 << 32) + 5, (1 << 40) + 11, (1 << 62) + 1]])
 
+# ---- long routes.  Config D (100 rocks on 150 x 100 cells), seeds 0..4095: the 22 whose shortest route costs more than rows + cols + 8 =
+# 258 (256.88 .. 370.35, the last moves before the start push keys past 258) -- the reference finds them, a planner whose open list ends at
+# rows + cols + 8 buckets reports "not found" -- and the 5 whose finish point the leader cannot reach although it lies in a free cell (the
+# open list runs dry after keys past 258; the reference's planner would not return there).
+LOST_D = (147, 302, 409, 758, 764, 955, 1254, 1457, 1674, 1747, 1775, 2369, 2509, 2513, 2515, 2562, 2680, 3144, 3546, 3558, 3935, 4087)
+DRY_D = (1901, 3441, 3490, 3655, 3766)
+# config B's kwargs with more rocks: keys beyond rows + cols + 8 on 11 / 7 / 4 / 1 of seeds 0..3999; at 160 rocks 15 worlds in 16 end with a dry
+# open list
+DENSE = {"rocks120_grid20": dict(obstacle_number=120, step_grid=20),
+         "rocks60_1000x1000": dict(obstacle_number=60, game_width=1000, game_height=1000),
+         "rocks200_margin05": dict(obstacle_number=200, leader_margin=0.5),
+         "rocks160": dict(obstacle_number=160)}
+LONG_ROUTE_CAP = 512
+
+
+def long_cfg(name, route_cap=LONG_ROUTE_CAP):
+    """Config D ("D": the kwargs of episode_D_s2_chase) or one of DENSE, with room for routes of `route_cap` points."""
+    if name == "D":
+        return config_for(load_episode("D_s2_chase")[1], scen_route_len=route_cap)
+    z = np.load(GOLDEN + "/pool_B.npz")
+    return config_for(dict(kwargs=dict(json.loads(str(z["meta"]))["kwargs"], **DENSE[name]), post=None), scen_route_len=route_cap)
+
+
+def load_pool_d_long():
+    z = np.load(GOLDEN + "/pool_D_long.npz")
+    meta = json.loads(str(z["meta"]))
+    assert set(LOST_D) <= set(z["requested_seed"].tolist()) and not set(DRY_D) & set(z["requested_seed"].tolist())
+    return z, config_for(dict(kwargs=meta["kwargs"], post=load_episode("D_s2_chase")[1]["post"]), scen_route_len=int(z["route_len"].max()))
+
+
+def check_against_pool_d_long(g, z, cfg):
+    """`g`: a generator's numpy arrays for z["requested_seed"], row for row, against what the reference's reset() built for these seeds
+    (tests/golden/pool_D_long.npz: seeds 0..41 and LOST_D), by the criteria of test_generator_matches_reference_pool."""
+    req = z["requested_seed"].tolist()
+    assert np.array_equal((g["status"] & abi.SCEN_FOUND) != 0, z["found"]), np.asarray(req)[((g["status"] & abi.SCEN_FOUND) != 0) != z["found"]]
+    assert z["found"][[req.index(s) for s in LOST_D]].all()
+    assert np.asarray(req)[g["usable"]].tolist() == z["seed"].tolist()
+    R, same_route = cfg.n_robots, []
+    for i, seed in enumerate(z["seed"].tolist()):
+        s = req.index(seed)
+        assert np.array_equal(g["static_rects"][s], z["static_rects"][i]), ("walls/rocks", seed)
+        rl = z["route_len"][i]
+        r_ref, r_got = z["route"][i, :rl].astype(np.float64), g["route"][s, :g["route_len"][s]]
+        assert np.array_equal(r_ref[0], r_got[0]) and np.abs(r_ref[-1] - r_got[-1]).max() <= 10, ("route ends", seed)
+        assert abs(_route_cost(r_ref) - _route_cost(r_got)) < 1e-6, ("route cost", seed, _route_cost(r_ref), _route_cost(r_got))
+        assert np.array_equal(g["robot_pos"][s][[0] + list(range(2, R))], z["robot_pos"][i][[0] + list(range(2, R))])
+        if len(r_ref) == len(r_got) and np.array_equal(r_ref, r_got):
+            same_route.append(seed)
+            assert np.array_equal(g["robot_pos"][s], z["robot_pos"][i]), ("robots", seed)
+            assert np.array_equal(g["robot_dir"][s], z["robot_dir"][i]), ("directions", seed)
+            assert np.array_equal(g["robot_rect"][s], z["robot_rect"][i].astype(np.int32)), ("hitboxes", seed)
+            n = z["init_traj_len"][i]
+            assert g["init_traj_len"][s] == n and np.array_equal(g["init_traj"][s, :n], z["init_traj"][i, :n]), ("trajectory", seed)
+    print("pool_D_long: %d worlds, %d with the reference's route point for point (%d of the %d long ones)"
+          % (len(z["seed"]), len(same_route), len(set(same_route) & set(LOST_D)), len(LOST_D)))
+    return same_route
+
+
+def check_route_cap(g256, g512):
+    """Seed 2369 of config D (a route of 331 points) generated with room for 256 and for 512 points: the short run is FOUND | ROUTE_OVERFLOW,
+    not usable, and holds the first 256 points of the long one."""
+    assert int(g512["status"][0]) == abi.SCEN_FOUND and bool(g512["usable"][0]) and 256 < int(g512["route_len"][0]) <= 512
+    assert int(g256["status"][0]) == abi.SCEN_FOUND | abi.SCEN_ROUTE_OVERFLOW
+    assert not bool(g256["usable"][0])
+    assert int(g256["route_len"][0]) == 256 and g256["route"].shape[1] == 256
+    assert np.array_equal(g256["route"][0], g512["route"][0, :256])
+
 
 def _pool_cfg(**over):
     z = np.load(GOLDEN + "/pool_B.npz")
@@ -151,6 +218,38 @@ def test_device_matches_reference_pool():
             n = z["init_traj_len"][i]
             assert g["init_traj_len"][s] == n and np.array_equal(g["init_traj"][s, :n], z["init_traj"][i, :n]), ("trajectory", s)
     assert same_route >= 0.99 * len(z["seed"]), same_route
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(DENSE))
+def test_device_matches_host_generator_dense(name):
+    """Dense rock fields: routes whose keys pass rows + cols + 8, and (rocks160) worlds that mostly end with a dry open list."""
+    d, h = _compare_with_host(long_cfg(name), np.arange(1024))
+    found = (h["status"] & abi.SCEN_FOUND) != 0
+    assert 50 <= found.sum() <= 1000, found.sum()              # both exits of the planner are taken
+
+
+@pytest.mark.gpu
+def test_device_matches_host_generator_long_routes_d():
+    seeds = np.array(list(LOST_D) + list(DRY_D) + list(range(256)))
+    d, h = _compare_with_host(long_cfg("D"), seeds)
+    assert (d["status"][:len(LOST_D)] == abi.SCEN_FOUND).all() and d["usable"][:len(LOST_D)].all()
+    assert d["route_len"][:len(LOST_D)].min() > 180             # a cost past 256 takes more than 256 / sqrt 2 moves
+    dry = slice(len(LOST_D), len(LOST_D) + len(DRY_D))
+    assert not (d["status"][dry] & abi.SCEN_FOUND).any() and (d["route_len"][dry] == 0).all() and not d["usable"][dry].any()
+
+
+@pytest.mark.gpu
+def test_device_route_cap_truncates_long_route():
+    g = [{k: v.cpu().numpy() for k, v in generate_scenarios_device(long_cfg("D", cap), [2369], "cuda:0").items()} for cap in (256, 512)]
+    check_route_cap(*g)
+
+
+@pytest.mark.gpu
+def test_device_matches_reference_pool_long():
+    z, cfg = load_pool_d_long()
+    g = {k: v.cpu().numpy() for k, v in generate_scenarios_device(cfg, z["requested_seed"].astype(np.int64), "cuda:0").items()}
+    check_against_pool_d_long(g, z, cfg)
 
 
 @pytest.mark.gpu
