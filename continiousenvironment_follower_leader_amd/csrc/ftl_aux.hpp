@@ -150,7 +150,8 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_AUX_WPE) ftl_aux_kernel(const Ft
             int slot = newest - a; slot += slot < 0 ? P.hmax : 0;
             for (int w = 0; w < 2; w++) if ((passes >> w) & 1) { base = min(base, s_winall[4 * slot + 2 * w]); top = max(top, s_winall[4 * slot + 2 * w + 1]); }
         }
-        const bool staged = nvalid > 0 && top - base <= FTL_COMPAS_STAGE;      // (the v1 tracker's corridor is never trimmed: it can outgrow the stage)
+        const bool staged = nvalid > 0 && top - base <= FTL_COMPAS_STAGE;      // (a v2 tracker that saves every scan on a long corridor_length outgrows the stage,
+                                                                                // as does the never-trimmed corridor of the v1 tracker)
         if (staged) for (int p = base + lane; p < top; p += FTL_WAVE) {
             const double4 q = *reinterpret_cast<const double4*>(corr_slot(P, env, p));
             *reinterpret_cast<double4*>(s_c64 + 4 * (p - base)) = q;
@@ -197,7 +198,8 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_AUX_WPE) ftl_aux_kernel(const Ft
             const int n_wall = nsnap > 0 ? 2 * max(umax - umin - 1, 0) : 0;
             const int n_items = n_wall + 2 * nsnap;
             // one item per lane -- a wall shared by every snapshot whose window holds both of its points, or an end cap of ONE snapshot --
-            // against its candidate rays (the wall stays in registers; N <= 36)
+            // against its candidate rays (the wall stays in registers; N <= 36: make_config admits 12, 20, 24 or 36 rays -- ftl_create's validate() only
+            // bounds the count by 1024, and nothing here depends on it)
             for (int item = lane; item < n_items; item += FTL_WAVE) {
                 double ax, ay, bx, by; unsigned sm = 0; int cls;
                 if (item < n_wall) {
@@ -447,10 +449,17 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_AUX_WPE) ftl_aux_kernel(const Ft
                     // atan2 of (|cross|, dot) gives that angle to ~3e-7 rad (the reference's own arccos(dot / norms) is within 2e-8 of it);
                     // unless it lies within 4e-6 rad of a sector boundary, or the point sits within 1e-9 of the follower's side-to-side
                     // axis (where "ahead" is decided), the sector is settled without the two float64 arccos of the reference expression.
+                    // One more case is left to that expression: a point straight behind the follower, or straight to either side.  There
+                    // |dot| and dist * norm agree to rounding (dist is a float32 norm when the slice is float32: 1.5e-7 relative), the
+                    // quotient can leave [-1, 1], and np.arccos returns nan: a nan `ad` is not `> pi / 2`, so the point behind counts as one
+                    // ahead, and a nan `ar` lies in no sector.  (The v1 tracker keeps the follower's start position in its history: a
+                    // follower that drives straight has it exactly behind.)  A quotient above +1 in `ad` changes nothing: not behind either way.
                     const float ang = atan2f(fabsf((float)(vx * rvy - vy * rvx)), (float)dot_r);
                     const float qf = ang * inv_sa;
                     const float tf = floorf(qf);
-                    const bool settled = dist > 0.0 && fabs(dot_d) > 1e-9 * dist && (qf - tf) > 4e-6f * inv_sa && (tf + 1.0f - qf) > 4e-6f * inv_sa;
+                    const double lim = dist * (1.0 - 1e-6);
+                    const bool settled = dist > 0.0 && fabs(dot_d) > 1e-9 * dist && dot_d > -lim && fabs(dot_r) < lim
+                                         && (qf - tf) > 4e-6f * inv_sa && (tf + 1.0f - qf) > 4e-6f * inv_sa;
                     if (settled) {
                         const int t = (int)tf;
                         if (dot_d > 0.0 && t < S) atomicMin(&s_rad[t], __float_as_uint((float)dist));     // behind the follower: ar < 0, no sector

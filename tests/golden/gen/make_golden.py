@@ -236,6 +236,37 @@ CONFIGS.update({
 })
 
 
+# ---- the capacity edges of the aux kernel (csrc/ftl_aux.hpp) and of the v1 tracker: configs L, C and T stretched until the arrays outgrow
+# a wavefront, the LDS stage and the 16-bit index split
+CONFIGS.update({
+    # 361 angles x 181 points = 65,341 (angle, point) pairs, the detectors at the reference's own defaults (180 sectors, 100 positions),
+    # a 720-sector radar, a 100-position vector detector
+    "L_edge": dict(kwargs=dict(bear_number=2, follower_sensors=OrderedDict([
+        ("LeaderPositionsTracker_v2", dict(SENSORS_B["LeaderPositionsTracker_v2"])),
+        ("lidar_dense", {"sensor_class": "LaserSensor", "available_angle": 360, "angle_step": 1, "points_number": 181, "sensor_range": 5,
+                         "return_only_distances": True}),
+        ("radar_default", {"sensor_class": "LeaderTrackDetector_radar"}),
+        ("track_long", {"sensor_class": "LeaderTrackDetector_vector", "position_sequence_length": 100, "detectable_positions": "new"}),
+        ("radar_wide", {"sensor_class": "LeaderTrackDetector_radar", "detectable_positions": "near", "radar_sectors_number": 720}),
+        ("LeaderCorridor_lasers_all", dict(SENSORS_B["LeaderCorridor_lasers_all"]))])), post=None),
+    # config C with a point saved every frame and a 600 px corridor: the corridor window of a snapshot passes 128 points
+    "C_long": dict(kwargs=dict(bear_number=1, follower_sensors=OrderedDict([
+        ("compas_first", dict(CONFIGS["C"]["kwargs"]["follower_sensors"]["compas_first"], lasers_count=36, laser_length=150, max_prev_obs=8)),
+        ("LeaderPositionsTracker_v2", dict(SENSORS_B["LeaderPositionsTracker_v2"], saving_period=1, corridor_length=600)),
+        ("LeaderCorridor_lasers_all", dict(SENSORS_B["LeaderCorridor_lasers_all"])),
+        ("LeaderCorridor_lasers_compas", dict(CONFIGS["C"]["kwargs"]["follower_sensors"]["LeaderCorridor_lasers_compas"], lasers_count=24,
+                                              laser_length=120, max_prev_obs=5))])), post=None),
+    # the v1 tracker saving every frame and eating nothing: its history passes 100 points (a Prev or compas sensor raises on this
+    # tracker, see config T)
+    "T_noeat": dict(kwargs=dict(bear_number=1, follower_sensors=OrderedDict([
+        ("LeaderPositionsTracker", {"sensor_class": "LeaderPositionsTracker", "saving_period": 1, "eat_close_points": False}),
+        ("lasers_now", dict(CONFIGS["T"]["kwargs"]["follower_sensors"]["lasers_now"])),
+        ("track_old", {"sensor_class": "LeaderTrackDetector_vector", "position_sequence_length": 100, "detectable_positions": "old"}),
+        ("radar_near", {"sensor_class": "LeaderTrackDetector_radar", "detectable_positions": "near", "radar_sectors_number": 180})])),
+        post=None),
+})
+
+
 def import_reference():
     import pygame  # stand-in
     with contextlib.redirect_stdout(io.StringIO()):
@@ -675,6 +706,9 @@ EPISODES = [
     ("Lfps1_s2_chase", "L_fps1", 2, "chase", 100),
     ("Lfps40_s2_chase", "L_fps40", 2, "chase", 40),
     ("Brf12_s5_chase", "B_rf12", 5, "chase", 80),
+    ("Ledge_s2_chase", "L_edge", 2, "chase", 40),
+    ("Clong_s1_chase", "C_long", 1, "chase", 80),
+    ("Tnoeat_s3_chase", "T_noeat", 3, "chase", 170),
 ]
 
 

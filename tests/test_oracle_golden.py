@@ -32,3 +32,19 @@ def test_golden_covers_terminal_modes():
     assert (2, 4, 2) in seen      # success
     assert (3, 0, 0) in seen      # finished_by_time
     assert (1, 2, 0) in seen      # low_reward
+
+
+def test_golden_reaches_the_staging_edges():
+    """The three records made for the capacity edges of csrc/ftl_aux.hpp reach them (a regenerated fixture must not quietly miss its
+    target): a corridor longer than the 128 points the compas sensors stage, a v1 history longer than the 100 positions its detector
+    takes, a dense lidar with at least 30 rays stopped short of its range."""
+    z, _ = load_episode("Clong_s1_chase")
+    assert z["dbg:trk"][:, 2].max() > 128
+    z, _ = load_episode("Tnoeat_s3_chase")
+    assert z["dbg:trk"][:, 1].max() > 100
+    z, meta = load_episode("Ledge_s2_chase")
+    cfg = config_for(meta)
+    a = [a for a in cfg.aux if a.name == "lidar_dense"][0]
+    assert a.params["n_angles"] * a.params["points_number"] == 65341
+    short = (z["obs:aux:lidar_dense"] < a.params["range_px"] * (1 - 1e-3)).sum(1)
+    assert z["obs:aux:lidar_dense"].shape[1] == 361 and short.max() >= 30
