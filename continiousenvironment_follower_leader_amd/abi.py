@@ -241,6 +241,27 @@ class GuidedBuffers(C.Structure):
                                          ("search_bl", C.c_void_p), ("search_bl_bytes", C.c_size_t), ("cap", C.c_int32), ("_pad", C.c_int32)]
 
 
+# the MLP policy population (include/ftl.h, ftl_mlp_act): the limits of a net and the staging sizes of ftl_mlp_kernel (csrc/ftl_mlp.hpp)
+FTL_MLP_MAX_LAYERS, FTL_MLP_MAX_WIDTH, FTL_MLP_MAX_IN = 4, 256, 4096
+FTL_MLP_ENV_TILE, FTL_MLP_K_CHUNK, FTL_MLP_W_STAGE, FTL_MLP_ENVS_PER_WAVE, FTL_MLP_NEURON_BLOCK, FTL_MLP_THREADS = 32, 64, 4096, 16, 16, 256
+
+
+def mlp_param_count(widths):
+    """Floats of one weight set (``ftl_mlp_param_count``): per layer W ``[in][out]`` then b ``[out]``."""
+    return sum((int(a) + 1) * int(b) for a, b in zip(widths[:-1], widths[1:]))
+
+
+def mlp_chunk_rows(w_out):
+    """Input rows of a layer with ``w_out`` neurons that ftl_mlp_kernel stages at a time (``chunk_rows`` of csrc/ftl_mlp.hpp)."""
+    return min(FTL_MLP_K_CHUNK, FTL_MLP_W_STAGE // int(w_out)) & ~3
+
+
+class Mlp(C.Structure):
+    """ftl_mlp: the parameters of a policy population, its shape and which envs use which weight set."""
+    _fields_ = [("params", C.c_void_p), ("set_stride", C.c_int64), ("n_sets", C.c_int32), ("n_layers", C.c_int32),
+                ("width", C.c_int32 * (FTL_MLP_MAX_LAYERS + 1)), ("env_first", C.c_int32), ("envs_per_set", C.c_int32), ("_pad", C.c_int32)]
+
+
 class EpisodeRecord(C.Structure):
     """ftl_episode_record: one row per entry of an episode queue, written once (``RECORD_DTYPE`` is the same row for numpy)."""
     _fields_ = [("state", C.c_int32), ("scenario", C.c_int32), ("env", C.c_int32), ("frames", C.c_int32), ("calls", C.c_int32),

@@ -179,7 +179,7 @@ static int baseline_rollout(const char* name, ftl_handle* h, int32_t T, int32_t 
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(baseline actions): ") + hipGetErrorString(e));
     }
     const dim3 grid((unsigned)((h->P.n_envs + 255) / 256));
-    return rollout_loop(h, FTL_ACTION_BOX2, T + tail, gamma, out, ro, flags, stream, [&](int32_t t) {
+    return rollout_loop(h, FTL_ACTION_BOX2, T + tail, gamma, out, ro, flags, false, stream, [&](int32_t t) {
         b.action = actions ? (double*)((char*)actions + (int64_t)t * step_bytes) : h->bl_action;
         if (t < guided) {
             g.resid = (const double*)((const char*)resid + (int64_t)t * resid_step_bytes);

@@ -1,0 +1,261 @@
+// ftl_mlp.hpp -- a dense feed-forward policy, or a population of them (one weight set per block of envs), on the device: the forward
+// pass from every env's policy_obs row to its encoded action (ftl_mlp_act) and T closed-loop steps with one call (ftl_rollout_mlp); the
+// numerics contract is in include/ftl.h.  Included by ftl_abi.hip after ftl_baseline.hpp (same translation unit: it reads the handle,
+// shares the handle's action scratch with the baseline and hands its act kernel to rollout_loop, which owns the steps and the fold).
+//
+// ftl_mlp_kernel: one workgroup of 256 threads per tile of up to FTL_MLP_ENV_TILE envs of ONE weight set (a tile ends at a set
+// boundary), all layers in one launch.  The activations of the tile stay in LDS between the layers ([env][act_stride] floats); nothing
+// but the input row and the action touches global memory per env.  A layer's weights are staged in LDS in chunks of kc input rows,
+// kc = min(FTL_MLP_K_CHUNK, FTL_MLP_W_STAGE / w_out) rounded down to a multiple of 4, and with them, for the first layer, the same kc
+// columns of the tile's policy_obs rows.  The products go through v_mfma_f32_16x16x4_f32: a wave owns FTL_MLP_ENVS_PER_WAVE envs (wave & 1
+// picks the half of the tile) and every second block of FTL_MLP_NEURON_BLOCK neurons (wave >> 1 picks the parity), the accumulator tile of
+// a block starts at the bias (the C operand), and one instruction advances all 256 chains of the block by 4 k in ascending order -- on
+// this hardware bit for bit the fmaf chain of the contract: tests/test_gpu_mlp.py pins it to the twin, on random nets and on rows built so
+// that a tie decided by the third operand and subnormal operands, sums and results reach the action (test_act_keeps_ties_and_subnormals).  The k left
+// over when a layer's input width is no multiple of 4 are plain fmaf on the same accumulators.  Per 4 k a wave reads one x and one
+// weight per lane and block from LDS.  Rows past the tile's last env and columns past w_out compute on whatever the stage holds: an MFMA
+// output depends on its own row and column only, and they are never stored.
+//
+// Weight traffic: a tile reads its set once from L2, ftl_mlp_param_count * 4 bytes per FTL_MLP_ENV_TILE envs (about 2 KB per env for
+// 180-64-64-2), against the whole set per env of a wave-per-env form.
+#include <hip/hip_runtime.h>
+
+#define FTL_MLP_ENV_TILE 32           // envs of one workgroup
+#define FTL_MLP_K_CHUNK 64            // input rows of a layer staged at a time, at most
+#define FTL_MLP_W_STAGE 4096          // floats of the weight stage: a chunk is kc rows of w_out floats, kc * w_out <= this
+#define FTL_MLP_ENVS_PER_WAVE 16      // rows of an MFMA tile
+#define FTL_MLP_NEURON_BLOCK 16       // columns of an MFMA tile
+#define FTL_MLP_THREADS 256
+
+namespace ftlmlp {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int TILE = FTL_MLP_ENV_TILE, KC = FTL_MLP_K_CHUNK, EPW = FTL_MLP_ENVS_PER_WAVE, NB = FTL_MLP_NEURON_BLOCK, WAVES = FTL_MLP_THREADS / 64;
+constexpr int GROUPS = TILE / EPW, PARITIES = WAVES / GROUPS;           // env groups of a tile; waves that share a group's neuron blocks
+constexpr int BPW = FTL_MLP_MAX_WIDTH / NB / PARITIES;                  // neuron blocks of a wave, at most
+constexpr int XS = KC + 2;             // row stride of the staged input chunk, and act_stride % 32 == 2 too: 16 rows x 2 k hit 32 banks
+static_assert(EPW == 16 && NB == 16 && GROUPS * PARITIES == WAVES && BPW * PARITIES * NB == FTL_MLP_MAX_WIDTH &&
+              FTL_MLP_W_STAGE / FTL_MLP_MAX_WIDTH >= 4 && KC % 4 == 0 && TILE * 8 == FTL_MLP_THREADS, "staging sizes");
+
+struct Args {
+    const float* obs;          // policy_obs: [n_envs][width[0]]
+    const float* params; int64_t set_stride;
+    int32_t n_envs, n_layers, width[FTL_MLP_MAX_LAYERS + 1], env_first, envs_per_set;
+    int32_t len0, tiles0, tiles_per_set;       // tile -> (set, envs): envs of the first (possibly cut) set, its tiles, the tiles of a whole set
+    int32_t act_stride;        // floats per env row of the activations in LDS: the widest of width[1 ..] rounded up to 32, plus 2
+    int32_t head;              // FTL_ACTION_*
+    double lo0, hi0, lo1, hi1;
+    void* action;
+};
+
+__host__ __device__ inline int chunk_rows(int w_out) {
+    const int by_stage = FTL_MLP_W_STAGE / w_out;
+    return (by_stage < KC ? by_stage : KC) & ~3;
+}
+
+__device__ __forceinline__ double box_head(float y, double lo, double hi) {
+    const double u = fmin(fmax((double)y, -1.0), 1.0);
+    const double s = (u + 1.0) * 0.5;
+    const double w = hi - lo;
+    const double a = lo + s * w;
+    return fmin(fmax(a, lo), hi);
+}
+
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) {
+    extern __shared__ float4 mlp_lds[];
+    float* act = reinterpret_cast<float*>(mlp_lds);            // [TILE][act_stride]
+    float* xs = act + TILE * a.act_stride;                      // [TILE][XS]: a chunk of the input rows (first layer)
+    float* ws = xs + TILE * XS;                                 // [kc][w_out]: a chunk of the layer's weights (+ 64 floats never used)
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, lk = lane >> 4;
+    const int g = wave % GROUPS, par = wave / GROUPS;
+    const int row_a = g * EPW + li;                             // the env whose x this lane feeds to the MFMA (A[i = lane & 15][k = lane >> 4])
+    const int row_d = g * EPW + 4 * lk;                         // the first of the 4 envs whose results it holds (D[4 * (lane >> 4) + r][lane & 15])
+    // the tile's set and envs
+    int set = a.env_first / a.envs_per_set, start, end;
+    if ((int)blockIdx.x < a.tiles0) { start = (int)blockIdx.x * TILE; end = a.len0; }
+    else {
+        const int b = (int)blockIdx.x - a.tiles0, m = b / a.tiles_per_set;
+        const int64_t seg = (int64_t)a.len0 + (int64_t)m * a.envs_per_set, seg_end = seg + a.envs_per_set;
+        set += 1 + m;
+        start = (int)seg + (b % a.tiles_per_set) * TILE;
+        end = seg_end < (int64_t)a.n_envs ? (int)seg_end : a.n_envs;
+    }
+    const int tile_n = end - start < TILE ? end - start : TILE;
+    const bool busy = g * EPW < tile_n;                         // this wave has envs
+    const float* P = a.params + (int64_t)set * a.set_stride;
+    const int w0 = a.width[0];
+    for (int l = 0; l < a.n_layers; l++) {
+        const int w_in = a.width[l], w_out = a.width[l + 1], nblk = (w_out + NB - 1) / NB;
+        const float* W = P;
+        const float* bias = W + (size_t)w_in * w_out;
+        P = bias + w_out;
+        f32x4 acc[BPW];
+#pragma unroll
+        for (int m = 0; m < BPW; m++) {
+            const int j = (par + PARITIES * m) * NB + li;
+            const float b = j < w_out ? bias[j] : 0.0f;
+            acc[m] = f32x4{b, b, b, b};
+        }
+        const int kc = chunk_rows(w_out);
+        const int xstride = l == 0 ? XS : a.act_stride;
+        for (int k0 = 0; k0 < w_in; k0 += kc) {
+            const int kn = w_in - k0 < kc ? w_in - k0 : kc;
+            __syncthreads();                                    // the chunk before this one has been read (and, k0 == 0, the layer before written)
+            for (int idx = t; idx < kn * w_out; idx += FTL_MLP_THREADS) ws[idx] = W[(size_t)k0 * w_out + idx];
+            if (l == 0) {
+                const int e = t >> 3;                           // 8 threads per env of the tile
+                if (e < tile_n)
+                    for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = a.obs[(size_t)(start + e) * w0 + k0 + kk];
+            }
+            __syncthreads();
+            if (!busy) continue;
+            const float* x = l == 0 ? xs : act + k0;
+            const float* xa = x + row_a * xstride + lk;
+            const float* xd = x + row_d * xstride;
+            int kk = 0;
+            for (; kk + 4 <= kn; kk += 4) {
+                const float av = xa[kk];
+                const float* wrow = ws + (kk + lk) * w_out + li;          // B[k = lane >> 4][j = lane & 15]; columns past w_out read on into the stage
+#pragma unroll
+                for (int m = 0; m < BPW; m++) {
+                    const int jb = par + PARITIES * m;
+                    if (jb < nblk) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wrow[jb * NB], acc[m], 0, 0, 0);      // (wave-uniform)
+                }
+            }
+            for (; kk < kn; kk++) {                              // w_in % 4 rows at the layer's end
+#pragma unroll
+                for (int m = 0; m < BPW; m++) {
+                    const int jb = par + PARITIES * m;
+                    if (jb >= nblk) continue;
+                    const float w = ws[kk * w_out + jb * NB + li];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) acc[m][r] = __builtin_fmaf(xd[r * xstride + kk], w, acc[m][r]);
+                }
+            }
+        }
+        __syncthreads();                                        // every wave has read this layer's input
+        const bool hidden = l + 1 < a.n_layers;
+#pragma unroll
+        for (int m = 0; m < BPW; m++) {
+            const int j = (par + PARITIES * m) * NB + li;
+            if (j >= w_out) continue;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float v = acc[m][r];
+                act[(row_d + r) * a.act_stride + j] = hidden ? (v > 0.0f ? v : 0.0f) : v;
+            }
+        }
+    }
+    __syncthreads();
+    if (t >= tile_n) return;
+    const float* y = act + t * a.act_stride;
+    const size_t e = (size_t)start + t;
+    if (a.head == FTL_ACTION_DISCRETE) {
+        int k = 0;
+        for (int j = 1; j < 5; j++) if (y[j] > y[k]) k = j;
+        static_cast<int32_t*>(a.action)[e] = k;
+    } else if (a.head == FTL_ACTION_BOX2) {
+        static_cast<double*>(a.action)[2 * e] = box_head(y[0], a.lo0, a.hi0);
+        static_cast<double*>(a.action)[2 * e + 1] = box_head(y[1], a.lo1, a.hi1);
+    } else static_cast<double*>(a.action)[e] = box_head(y[0], a.lo1, a.hi1);
+}
+
+}  // namespace ftlmlp
+
+// floats of one weight set; -1 outside the limits of include/ftl.h
+static int64_t mlp_param_count(const int32_t* w, int32_t L) {
+    if (!w || L < 1 || L > FTL_MLP_MAX_LAYERS) return -1;
+    int64_t n = 0;
+    for (int l = 0; l <= L; l++)
+        if (w[l] < 1 || w[l] > (l == 0 ? FTL_MLP_MAX_IN : FTL_MLP_MAX_WIDTH)) return -1;
+    for (int l = 1; l <= L; l++) n += ((int64_t)w[l - 1] + 1) * w[l];
+    return n;
+}
+
+static size_t mlp_action_bytes(int32_t head) { return head == FTL_ACTION_BOX2 ? 16 : head == FTL_ACTION_TURN ? 8 : 4; }
+
+// the checks of the net that ftl_mlp_act and ftl_rollout_mlp share (check_ready comes after the caller's own, so that a missing state is the
+// last thing reported); fills the kernel's arguments but for `action`, its grid and its LDS bytes
+static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, ftlmlp::Args& a, unsigned& grid, size_t& lds) {
+    if (!h || !out || !net || !net->params) return fail(FTL_E_INVALID, "null argument");
+    const int32_t L = net->n_layers;
+    if (L < 1) return fail(FTL_E_INVALID, "mlp: n_layers must be at least 1");
+    if (L > FTL_MLP_MAX_LAYERS) return fail(FTL_E_UNSUPPORTED, "mlp: more than FTL_MLP_MAX_LAYERS layers");
+    for (int l = 0; l <= L; l++) {
+        if (net->width[l] < 1) return fail(FTL_E_INVALID, "mlp: every width must be at least 1");
+        if (net->width[l] > (l == 0 ? FTL_MLP_MAX_IN : FTL_MLP_MAX_WIDTH))
+            return fail(FTL_E_UNSUPPORTED, l == 0 ? "mlp: input width beyond FTL_MLP_MAX_IN" : "mlp: layer width beyond FTL_MLP_MAX_WIDTH");
+    }
+    const int32_t wl = net->width[L];
+    if (wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "mlp: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
+    if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "mlp: params must be 4-byte aligned");
+    if (net->set_stride < mlp_param_count(net->width, L)) return fail(FTL_E_INVALID, "mlp: set_stride below ftl_mlp_param_count");
+    if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "mlp: n_sets and envs_per_set must be at least 1, env_first at least 0");
+    const int64_t n = h->P.n_envs, eps = net->envs_per_set, first = net->env_first;
+    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, "mlp: the handle's last env lies beyond the last weight set");
+    if (!out->policy_obs || h->P.pol_h <= 0 || h->P.pol_width <= 0) return fail(FTL_E_INVALID, "mlp: the policy reads policy_obs (ftl_outputs.policy_obs, a config with a sensor for it)");
+    if ((int64_t)net->width[0] != (int64_t)h->P.pol_h * h->P.pol_width) return fail(FTL_E_INVALID, "mlp: width[0] must be H * W of policy_obs");
+    a.obs = out->policy_obs; a.params = net->params; a.set_stride = net->set_stride;
+    a.n_envs = (int32_t)n; a.n_layers = L; a.env_first = net->env_first; a.envs_per_set = net->envs_per_set;
+    int wmax = 0;
+    for (int l = 0; l <= FTL_MLP_MAX_LAYERS; l++) {
+        a.width[l] = l <= L ? net->width[l] : 0;
+        if (l >= 1 && a.width[l] > wmax) wmax = a.width[l];
+    }
+    a.act_stride = ((wmax + 31) & ~31) + 2;
+    const int64_t tile = FTL_MLP_ENV_TILE;
+    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0;
+    a.len0 = (int32_t)len0; a.tiles0 = (int32_t)((len0 + tile - 1) / tile); a.tiles_per_set = (int32_t)((eps + tile - 1) / tile);
+    grid = (unsigned)(a.tiles0 + (rem / eps) * a.tiles_per_set + (rem % eps + tile - 1) / tile);
+    lds = ((size_t)FTL_MLP_ENV_TILE * a.act_stride + (size_t)FTL_MLP_ENV_TILE * ftlmlp::XS + FTL_MLP_W_STAGE + 64) * sizeof(float);
+    a.head = wl == 2 ? FTL_ACTION_BOX2 : wl == 1 ? FTL_ACTION_TURN : FTL_ACTION_DISCRETE;
+    const ftl_robot_params& f = h->P.cfg.follower;
+    a.lo0 = f.min_speed; a.hi0 = f.max_speed; a.lo1 = -f.max_rotation_speed; a.hi1 = f.max_rotation_speed;
+    a.action = nullptr;
+    return FTL_OK;
+}
+
+extern "C" {
+
+size_t ftl_sizeof_mlp(void) { return sizeof(ftl_mlp); }
+
+int64_t ftl_mlp_param_count(const int32_t* widths, int32_t n_layers) { return mlp_param_count(widths, n_layers); }
+
+int ftl_mlp_act(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, void* action, void* stream) {
+    if (!action) return fail(FTL_E_INVALID, "null argument");
+    ftlmlp::Args a; unsigned grid; size_t lds;
+    if (int rc = mlp_args(h, out, net, a, grid, lds)) return rc;
+    if (((uintptr_t)action) & (a.head == FTL_ACTION_DISCRETE ? 3 : 7)) return fail(FTL_E_INVALID, "ftl_mlp_act: action not aligned to its element");
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    a.action = action;
+    hipLaunchKernelGGL(ftlmlp::ftl_mlp_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+    return launched();
+}
+
+int ftl_rollout_mlp(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_mlp* net,
+                    void* actions, int64_t step_bytes, uint32_t flags, void* stream) {
+    if (!h || !out || !net) return fail(FTL_E_INVALID, "null argument");
+    if (flags & FTL_STEP_NO_SENSORS)
+        return fail(FTL_E_INVALID, "ftl_rollout_mlp refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
+    if (int rc = rollout_check("ftl_rollout_mlp", ro, T, 0, flags)) return rc;
+    ftlmlp::Args a; unsigned grid; size_t lds;
+    if (int rc = mlp_args(h, out, net, a, grid, lds)) return rc;
+    const int64_t block = (int64_t)h->P.n_envs * (int64_t)mlp_action_bytes(a.head);
+    if (actions && step_bytes < block) return fail(FTL_E_INVALID, "ftl_rollout_mlp: step_bytes below one block of encoded actions");
+    if (actions && ((((uintptr_t)actions) | (uintptr_t)step_bytes) & (a.head == FTL_ACTION_DISCRETE ? 3 : 7)))
+        return fail(FTL_E_INVALID, "ftl_rollout_mlp: actions and step_bytes not aligned to the action element");
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (!actions && !h->bl_action) {                            // (16 bytes per env: any encoding fits the baseline's scratch)
+        hipError_t e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
+        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(policy actions): ") + hipGetErrorString(e));
+    }
+    return rollout_loop(h, a.head, T, gamma, out, ro, 0, true, stream, [&](int32_t t) {
+        a.action = actions ? (void*)((char*)actions + (int64_t)t * step_bytes) : (void*)h->bl_action;
+        hipLaunchKernelGGL(ftlmlp::ftl_mlp_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+        return a.action;
+    });
+}
+
+}  // extern "C"

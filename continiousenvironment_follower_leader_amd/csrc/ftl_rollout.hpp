@@ -1,7 +1,8 @@
 // ftl_rollout.hpp -- T steps of an open-loop action sequence with one call (ftl_rollout, include/ftl.h), and the one rollout loop of the
-// library: rollout_loop, which ftl_rollout calls with a pointer into the caller's sequence as the action of step t and ftl_baseline.hpp
-// (ftl_rollout_baseline, ftl_rollout_guided) with the follower's act kernel.  Included by ftl_abi.hip after ftl_step_final (same
-// translation unit: it reads the handle and calls launch()).
+// library: rollout_loop, which ftl_rollout calls with a pointer into the caller's sequence as the action of step t, ftl_baseline.hpp
+// (ftl_rollout_baseline, ftl_rollout_guided) with the follower's act kernel and ftl_mlp.hpp (ftl_rollout_mlp) with the policy's forward
+// kernel and a scan in every step.  Included by ftl_abi.hip after ftl_step_final (same translation unit: it reads the handle and calls
+// launch()).
 //
 // The rollout is T launches of a step without auto-reset -- the first T - 1 of them without the sensor kernels -- and, after each frame
 // launch, ftl_rollout_fold_kernel: one thread per env adds the step's discounted reward to the env's return while its episode runs.  The
@@ -53,11 +54,12 @@ static int rollout_check(const char* name, const ftl_rollout_outputs* ro, int32_
     return FTL_OK;
 }
 
-// The rollout loop of every entry, after its checks and set_device: T steps on `stream`, the first T - 1 of them blind, each followed by
-// the fold.  action(t) enqueues whatever decides step t and returns what the step reads: [n_envs][2] doubles, or the encoded actions.
+// The rollout loop of every entry, after its checks and set_device: T steps on `stream`, each followed by the fold.  scan_every false: the
+// first T - 1 steps are blind and the last one takes `flags`; true (a policy that reads the sensors: ftl_rollout_mlp): every step takes
+// `flags`.  action(t) enqueues whatever decides step t and returns what the step reads: [n_envs][2] doubles, or the encoded actions.
 template <typename Action>
 static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
-                        uint32_t flags, void* stream, Action action) {
+                        uint32_t flags, bool scan_every, void* stream, Action action) {
     if (!h->ro_alive) {
         hipError_t e = hipMalloc((void**)&h->ro_alive, align_up((size_t)h->P.n_envs, 256));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(rollout scratch): ") + hipGetErrorString(e));
@@ -74,7 +76,7 @@ static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma
     h->last_lasers = h->P.lasers_len > 0 ? out->lasers : nullptr;
     for (int32_t t = 0; t < T; t++) {
         call.action = (const double*)action(t);
-        call.flags = (t < T - 1) ? (uint32_t)FTL_STEP_NO_SENSORS : flags;
+        call.flags = (t < T - 1 && !scan_every) ? (uint32_t)FTL_STEP_NO_SENSORS : flags;
         // (a two-stream handle forks after what action(t) enqueued, and the caller's stream has joined the side stream before the fold)
         if (int rc = launch(h, call, stream)) return rc;
         hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -94,7 +96,7 @@ int ftl_rollout(ftl_handle* h, const void* actions, int64_t step_bytes, int32_t 
     if (encoding < FTL_ACTION_BOX2 || encoding > FTL_ACTION_TURN) return fail(FTL_E_INVALID, "unknown action encoding");
     if (int rc = check_ready(h, out)) return rc;
     if (int rc = set_device(h)) return rc;
-    return rollout_loop(h, encoding, T, gamma, out, ro, flags, stream, [&](int32_t t) { return (const char*)actions + (int64_t)t * step_bytes; });
+    return rollout_loop(h, encoding, T, gamma, out, ro, flags, false, stream, [&](int32_t t) { return (const char*)actions + (int64_t)t * step_bytes; });
 }
 
 }  // extern "C"

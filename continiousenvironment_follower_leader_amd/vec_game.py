@@ -293,6 +293,17 @@ class _BatchBase:
             raise ValueError("rollout_guided() takes a BaselineFollower of this batch")
         return follower.rollout_guided(resid, tail, gamma, sensors, record)
 
+    def rollout_mlp(self, policy, T, gamma=1.0, record=False):
+        """``T`` closed-loop steps of a feed-forward policy population with one call and no host round trip (``ftl_rollout_mlp``):
+        ``rollout`` with the action of every step decided on the stream by ``policy`` (an ``mlp.MlpPolicy`` of this batch) from the
+        ``policy_obs`` the step before it wrote -- so the outputs must hold the observation of the current state, and every step scans.
+        Returns ``(ret, steps, status)`` as ``rollout`` does, plus with ``record=True`` the ``[T, N, ...]`` actions that were played, in
+        the config's encoding.  Bit-identical to ``T`` times ``policy.act()`` + ``step()``, and in env state and returns to ``rollout`` on
+        the recorded actions.  Does not join a pipelined batch, like ``step``."""
+        if getattr(policy, "batch", None) is not self or not hasattr(policy, "widths"):
+            raise ValueError("rollout_mlp() takes an MlpPolicy of this batch")
+        return policy.rollout(T, gamma, record)
+
     def terminated_truncated(self):
         """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
         truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap

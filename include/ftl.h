@@ -813,6 +813,66 @@ int ftl_guided_fanout(const ftl_handle* real, const ftl_handle* search, int32_t 
 int ftl_search_guided(ftl_handle* real, ftl_handle* search, const ftl_search_params* p, uint64_t call, int32_t warm, int32_t tail,
                       const ftl_guided_buffers* gb, void* stream);
 
+/* ---- MLP policy population: a dense feed-forward net, or one net per block of envs, as a policy and as closed-loop rollouts ----------
+ * The consumer of ftl_outputs.policy_obs on the device: ftl_mlp_act (ftl_mlp_kernel, csrc/ftl_mlp.hpp, one launch, asynchronous on
+ * `stream`) reads every env's policy_obs row and writes its action in the encoding the head width implies; ftl_rollout_mlp closes the
+ * loop over T steps with one call.  The arithmetic is fixed operation by operation, so the device equals a numpy twin bit for bit
+ * (tests/mlp_numpy.py).
+ *
+ * Net         L = n_layers layers, 1 <= L <= FTL_MLP_MAX_LAYERS; widths width[0 .. L], width[0] the input and width[L] the head width;
+ *             width[0] in 1 .. FTL_MLP_MAX_IN, every other width in 1 .. FTL_MLP_MAX_WIDTH.  L = 1 is a linear policy.  Beyond these
+ *             limits: FTL_E_UNSUPPORTED before any device work.
+ * Parameters  float32 in DEVICE memory, 4-byte aligned: n_sets >= 1 sets, set s at params + s * set_stride (in floats).  One set holds,
+ *             layer by layer (l = 1 .. L), W_l as [width[l-1]][width[l]] row-major (input index outer) followed by b_l[width[l]]:
+ *             ftl_mlp_param_count(width, L) = sum_l (width[l-1] + 1) * width[l] floats; set_stride >= that.
+ * Input       x = env e's policy_obs row flattened, [H][W] -> H * W float32; width[0] must equal H * W of the handle.
+ * Neuron j of layer l is a k-ordered float32 fused chain that starts at the bias:
+ *                 acc = b[j];  for k = 0 .. width[l-1] - 1:  acc = fmaf(x[k], W[k][j], acc)
+ *             one rounding per step, no split-K, no tree, no wider accumulator; f32 subnormals are kept.  Hidden layers (l < L) then apply
+ *             acc > 0 ? acc : 0.0f, which maps NaN and -0 to +0.  The head layer (l = L) has no activation: y_j = acc.
+ * Heads       lo / hi are the bounds of the config's action Box (follower.min_speed / max_speed for the speed, -/+ max_rotation_speed for the
+ *             rotation: those of ftl_search_sample and of the env's own clip).  Every operation below is one float64 rounding, fmin / fmax as
+ *             in C (a NaN operand yields the other one):
+ *   width[L] = 2  FTL_ACTION_BOX2      u = fmin(fmax((double)y_j, -1.0), 1.0);  a_j = lo_j + ((u + 1.0) * 0.5) * (hi_j - lo_j);
+ *                                      a_j = fmin(fmax(a_j, lo_j), hi_j); j = 0 the speed, j = 1 the rotation; written as f64 [n][2].
+ *   width[L] = 1  FTL_ACTION_TURN      the same map of y_0 with the rotation bounds (Box(1) of constant_follower_speed); f64 [n].
+ *   width[L] = 5  FTL_ACTION_DISCRETE  k = 0; for j = 1 .. 4: if (y_j > y_k) k = j -- the first maximum; a NaN never beats anything; int32 [n].
+ *             Any other head width: FTL_E_INVALID.  (The handle does not know which action space the caller's config declares: the head
+ *             width chooses the encoding, and the Python wrapper refuses a head that does not fit the config.)
+ * Weight set  env e of the handle uses set (env_first + e) / envs_per_set: contiguous equal blocks of the WHOLE batch, env_first being the
+ *             handle's first env in it (0 for a lone handle, the part's first row for a part of a pipelined batch), so a set may straddle
+ *             two parts.  (env_first + n_envs - 1) / envs_per_set < n_sets, else FTL_E_INVALID.  A workgroup's tile of envs never crosses a
+ *             set boundary, so it stages one set's weights.
+ *
+ * ftl_rollout_mlp is ftl_rollout with the action of step t produced on the stream by the act kernel from the policy_obs step t - 1 (or
+ * the last reset / step / scan) wrote: T steps without auto-reset, EVERY one of them with its sensor kernels -- the next decision reads
+ * them -- each followed by ftl_rollout_fold_kernel.  flags must be 0: FTL_STEP_NO_SENSORS would blind the policy and is refused with a
+ * message that says so.  actions == NULL: the actions go to a scratch the handle owns; otherwise block t (in the head's encoding: 16, 8 or
+ * 4 bytes per env) is written at actions + t * step_bytes.  It is bit-identical -- `out`, `ro`, every state byte -- to T iterations of
+ * ftl_mlp_act + ftl_step_encoded + fold, and its env state and `ro` are those of ftl_rollout on the recorded actions.
+ * FTL_E_INVALID before any device work: NULL pointers, out->policy_obs NULL (or a handle whose config has no sensor for it),
+ * width[0] != H * W, params not 4-byte aligned, set_stride below the param count, n_sets < 1, envs_per_set < 1, env_first < 0, a set index
+ * out of range, a head width other than 1 / 2 / 5, T <= 0, any flag, step_bytes below one block when `actions` is given; FTL_E_STATE as for
+ * the baseline. */
+#define FTL_MLP_MAX_LAYERS 4
+#define FTL_MLP_MAX_WIDTH 256
+#define FTL_MLP_MAX_IN 4096
+typedef struct ftl_mlp {
+    const float* params;       /* DEVICE, [n_sets] sets of set_stride floats */
+    int64_t  set_stride;       /* floats between two sets */
+    int32_t  n_sets;
+    int32_t  n_layers;
+    int32_t  width[FTL_MLP_MAX_LAYERS + 1];
+    int32_t  env_first;        /* index of the handle's env 0 in the whole batch */
+    int32_t  envs_per_set;
+    int32_t  _pad;
+} ftl_mlp;
+size_t ftl_sizeof_mlp(void);
+int64_t ftl_mlp_param_count(const int32_t* widths, int32_t n_layers);   /* floats of one set; -1 outside the limits above or on NULL */
+int ftl_mlp_act(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, void* action, void* stream);
+int ftl_rollout_mlp(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_mlp* net,
+                    void* actions /* [T] blocks in the head's encoding, or NULL */, int64_t step_bytes, uint32_t flags /* 0 */, void* stream);
+
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
  * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
