@@ -25,6 +25,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_rollout.hpp"),
            os.path.join(_PKG, "csrc", "ftl_baseline.hpp"),
            os.path.join(_PKG, "csrc", "ftl_mlp.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_collect.hpp"),
            os.path.join(_PKG, "csrc", "ftl_search.hpp"),
            os.path.join(_PKG, "csrc", "ftl_guided.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
@@ -153,6 +154,13 @@ def load():
     lib.ftl_rollout_mlp.argtypes = [vp, i32, C.c_double, C.POINTER(abi.Outputs), C.POINTER(abi.RolloutOutputs), C.POINTER(abi.Mlp), vp, C.c_int64,
                                     u32, vp]
     lib.ftl_rollout_mlp.restype = C.c_int
+    lib.ftl_sizeof_collect_buffers.restype = C.c_size_t
+    lib.ftl_mlp_sample.argtypes = [vp, C.POINTER(abi.Outputs), C.POINTER(abi.Mlp), vp, vp, vp, vp, vp, vp]
+    lib.ftl_mlp_sample.restype = C.c_int
+    lib.ftl_collect_mlp.argtypes = [vp, i32, C.POINTER(abi.Outputs), C.POINTER(abi.Mlp), C.POINTER(abi.CollectBuffers), u32, vp]
+    lib.ftl_collect_mlp.restype = C.c_int
+    lib.ftl_gae.argtypes = [vp, i32, i32, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, C.c_double, vp, vp, vp]
+    lib.ftl_gae.restype = C.c_int
     lib.ftl_sizeof_episode_record.restype = C.c_size_t
     lib.ftl_sizeof_episode_queue.restype = C.c_size_t
     lib.ftl_set_episode_queue.argtypes = [vp, C.POINTER(abi.EpisodeQueueC)]
@@ -198,6 +206,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_search_select", "ftl_search",
            "ftl_sizeof_guided_buffers", "ftl_baseline_act_guided", "ftl_rollout_guided", "ftl_guided_fanout", "ftl_search_guided",
            "ftl_sizeof_mlp", "ftl_mlp_param_count", "ftl_mlp_act", "ftl_rollout_mlp",
+           "ftl_sizeof_collect_buffers", "ftl_mlp_sample", "ftl_collect_mlp", "ftl_gae",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -262,6 +262,18 @@ class Mlp(C.Structure):
                 ("width", C.c_int32 * (FTL_MLP_MAX_LAYERS + 1)), ("env_first", C.c_int32), ("envs_per_set", C.c_int32), ("_pad", C.c_int32)]
 
 
+# the kinds of a recorded transition (include/ftl.h, ftl_collect_mlp): kind[t][e] of ftl_collect_buffers, read by ftl_gae
+FTL_TR_STEP, FTL_TR_TERMINATED, FTL_TR_TRUNCATED, FTL_TR_VOID = 0, 1, 2, 3
+
+
+class CollectBuffers(C.Structure):
+    """ftl_collect_buffers: where ftl_collect_mlp records a trajectory (block t of an array at base + t * its ``*_step_bytes``)."""
+    _fields_ = [("obs", C.c_void_p), ("head", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("kind", C.c_void_p),
+                ("noise", C.c_void_p), ("sigma", C.c_void_p),
+                ("obs_step_bytes", C.c_int64), ("head_step_bytes", C.c_int64), ("action_step_bytes", C.c_int64),
+                ("reward_step_bytes", C.c_int64), ("kind_step_bytes", C.c_int64), ("noise_step_bytes", C.c_int64)]
+
+
 class EpisodeRecord(C.Structure):
     """ftl_episode_record: one row per entry of an episode queue, written once (``RECORD_DTYPE`` is the same row for numpy)."""
     _fields_ = [("state", C.c_int32), ("scenario", C.c_int32), ("env", C.c_int32), ("frames", C.c_int32), ("calls", C.c_int32),

@@ -16,6 +16,12 @@
 // weight per lane and block from LDS.  Rows past the tile's last env and columns past w_out compute on whatever the stage holds: an MFMA
 // output depends on its own row and column only, and they are never stored.
 //
+// ftl_mlp_sample_kernel is the same body (mlp_body<true>) with three optional additions, each a pointer of ftlmlp::Sample: the threads that
+// stage a chunk of the tile's policy_obs rows store the same floats to obs_rec (the row is read from HBM once and written once), the raw
+// head outputs go to head_rec before any map, and the head map adds the caller's noise (include/ftl.h: ftl_mlp_sample).  ftl_collect_mlp
+// plays T such decisions through episode boundaries and records a trajectory (ftl_collect_record_kernel); ftl_gae_kernel turns its rewards
+// and kinds and the caller's values into advantages.
+//
 // Weight traffic: a tile reads its set once from L2, ftl_mlp_param_count * 4 bytes per FTL_MLP_ENV_TILE envs (about 2 KB per env for
 // 180-64-64-2), against the whole set per env of a wave-per-env form.
 #include <hip/hip_runtime.h>
@@ -53,15 +59,31 @@ __host__ __device__ inline int chunk_rows(int w_out) {
     return (by_stage < KC ? by_stage : KC) & ~3;
 }
 
-__device__ __forceinline__ double box_head(float y, double lo, double hi) {
-    const double u = fmin(fmax((double)y, -1.0), 1.0);
+struct Sample {               // what ftl_mlp_sample_kernel adds to ftl_mlp_kernel; every pointer may be null
+    const float* noise;       // [n_envs][width[L]]
+    const float* sigma;       // [n_sets][width[L]] (Box heads)
+    float* head_rec;          // [n_envs][width[L]]: y before any map
+    float* obs_rec;           // [n_envs][width[0]]: the policy_obs rows as the first layer staged them
+};
+
+__device__ __forceinline__ double box_map(double z, double lo, double hi) {
+    const double u = fmin(fmax(z, -1.0), 1.0);
     const double s = (u + 1.0) * 0.5;
     const double w = hi - lo;
     const double a = lo + s * w;
     return fmin(fmax(a, lo), hi);
 }
 
-__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) {
+__device__ __forceinline__ double box_head(float y, double lo, double hi) { return box_map((double)y, lo, hi); }
+
+// z = y + sigma * noise: the product of two float32 is exact in float64, the sum is the one rounding
+__device__ __forceinline__ double box_sample(float y, float sigma, float noise, double lo, double hi) {
+    const double p = (double)sigma * (double)noise;
+    return box_map((double)y + p, lo, hi);
+}
+
+template <bool SAMPLE>
+__device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
     extern __shared__ float4 mlp_lds[];
     float* act = reinterpret_cast<float*>(mlp_lds);            // [TILE][act_stride]
     float* xs = act + TILE * a.act_stride;                      // [TILE][XS]: a chunk of the input rows (first layer)
@@ -104,8 +126,13 @@ __global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) 
             for (int idx = t; idx < kn * w_out; idx += FTL_MLP_THREADS) ws[idx] = W[(size_t)k0 * w_out + idx];
             if (l == 0) {
                 const int e = t >> 3;                           // 8 threads per env of the tile
-                if (e < tile_n)
-                    for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = a.obs[(size_t)(start + e) * w0 + k0 + kk];
+                if (e < tile_n) {
+                    const size_t row = (size_t)(start + e) * w0 + k0;
+                    if (SAMPLE && sm.obs_rec)
+                        for (int kk = t & 7; kk < kn; kk += 8) { const float v = a.obs[row + kk]; xs[e * XS + kk] = v; sm.obs_rec[row + kk] = v; }
+                    else
+                        for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = a.obs[row + kk];
+                }
             }
             __syncthreads();
             if (!busy) continue;
@@ -150,6 +177,30 @@ __global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) 
     if (t >= tile_n) return;
     const float* y = act + t * a.act_stride;
     const size_t e = (size_t)start + t;
+    if (SAMPLE) {
+        const int wl = a.width[a.n_layers];
+        if (sm.head_rec)
+            for (int j = 0; j < wl; j++) sm.head_rec[e * wl + j] = y[j];
+        if (sm.noise) {
+            const float* nz = sm.noise + e * wl;
+            if (a.head == FTL_ACTION_DISCRETE) {                // s_j = y_j + noise_j in float64; the first maximum, a NaN never beats anything
+                int k = 0;
+                double best = (double)y[0] + (double)nz[0];
+                for (int j = 1; j < 5; j++) {
+                    const double sj = (double)y[j] + (double)nz[j];
+                    if (sj > best) { best = sj; k = j; }
+                }
+                static_cast<int32_t*>(a.action)[e] = k;
+            } else {
+                const float* sg = sm.sigma + (size_t)set * wl;
+                if (a.head == FTL_ACTION_BOX2) {
+                    static_cast<double*>(a.action)[2 * e] = box_sample(y[0], sg[0], nz[0], a.lo0, a.hi0);
+                    static_cast<double*>(a.action)[2 * e + 1] = box_sample(y[1], sg[1], nz[1], a.lo1, a.hi1);
+                } else static_cast<double*>(a.action)[e] = box_sample(y[0], sg[0], nz[0], a.lo1, a.hi1);
+            }
+            return;
+        }
+    }
     if (a.head == FTL_ACTION_DISCRETE) {
         int k = 0;
         for (int j = 1; j < 5; j++) if (y[j] > y[k]) k = j;
@@ -159,6 +210,10 @@ __global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) 
         static_cast<double*>(a.action)[2 * e + 1] = box_head(y[1], a.lo1, a.hi1);
     } else static_cast<double*>(a.action)[e] = box_head(y[0], a.lo1, a.hi1);
 }
+
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) { mlp_body<false>(a, Sample{}); }
+
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_sample_kernel(const Args a, const Sample sm) { mlp_body<true>(a, sm); }
 
 }  // namespace ftlmlp
 
@@ -215,6 +270,15 @@ static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, f
     return FTL_OK;
 }
 
+// what ftl_mlp_sample and ftl_collect_mlp check of the sampling pointers alike; `name` heads the messages
+static int mlp_sample_check(const char* name, int32_t head, const float* noise, const float* sigma, const float* head_rec, const float* obs_rec) {
+    if (noise && !sigma && head != FTL_ACTION_DISCRETE)
+        return fail(FTL_E_INVALID, std::string(name) + ": a Box head with noise needs sigma (z = y + sigma * noise)");
+    if ((((uintptr_t)noise) | ((uintptr_t)sigma) | ((uintptr_t)head_rec) | ((uintptr_t)obs_rec)) & 3)
+        return fail(FTL_E_INVALID, std::string(name) + ": noise, sigma, head and obs must be 4-byte aligned");
+    return FTL_OK;
+}
+
 extern "C" {
 
 size_t ftl_sizeof_mlp(void) { return sizeof(ftl_mlp); }
@@ -230,6 +294,21 @@ int ftl_mlp_act(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, void*
     if (int rc = set_device(h)) return rc;
     a.action = action;
     hipLaunchKernelGGL(ftlmlp::ftl_mlp_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+    return launched();
+}
+
+int ftl_mlp_sample(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, const float* noise, const float* sigma, float* head_rec,
+                   float* obs_rec, void* action, void* stream) {
+    if (!action) return fail(FTL_E_INVALID, "null argument");
+    ftlmlp::Args a; unsigned grid; size_t lds;
+    if (int rc = mlp_args(h, out, net, a, grid, lds)) return rc;
+    if (((uintptr_t)action) & (a.head == FTL_ACTION_DISCRETE ? 3 : 7)) return fail(FTL_E_INVALID, "ftl_mlp_sample: action not aligned to its element");
+    if (int rc = mlp_sample_check("ftl_mlp_sample", a.head, noise, sigma, head_rec, obs_rec)) return rc;
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    a.action = action;
+    const ftlmlp::Sample sm{noise, sigma, head_rec, obs_rec};
+    hipLaunchKernelGGL(ftlmlp::ftl_mlp_sample_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
     return launched();
 }
 

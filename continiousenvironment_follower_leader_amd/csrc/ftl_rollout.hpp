@@ -1,7 +1,8 @@
 // ftl_rollout.hpp -- T steps of an open-loop action sequence with one call (ftl_rollout, include/ftl.h), and the one rollout loop of the
 // library: rollout_loop, which ftl_rollout calls with a pointer into the caller's sequence as the action of step t, ftl_baseline.hpp
 // (ftl_rollout_baseline, ftl_rollout_guided) with the follower's act kernel and ftl_mlp.hpp (ftl_rollout_mlp) with the policy's forward
-// kernel and a scan in every step.  Included by ftl_abi.hip after ftl_step_final (same translation unit: it reads the handle and calls
+// kernel and a scan in every step, and ftl_collect.hpp (ftl_collect_mlp) with the sampling kernel, no fold, next-step reset and a record
+// kernel after every step.  Included by ftl_abi.hip after ftl_step_final (same translation unit: it reads the handle and calls
 // launch()).
 //
 // The rollout is T launches of a step without auto-reset -- the first T - 1 of them without the sensor kernels -- and, after each frame
@@ -57,19 +58,26 @@ static int rollout_check(const char* name, const ftl_rollout_outputs* ro, int32_
 // The rollout loop of every entry, after its checks and set_device: T steps on `stream`, each followed by the fold.  scan_every false: the
 // first T - 1 steps are blind and the last one takes `flags`; true (a policy that reads the sensors: ftl_rollout_mlp): every step takes
 // `flags`.  action(t) enqueues whatever decides step t and returns what the step reads: [n_envs][2] doubles, or the encoded actions.
-template <typename Action>
-static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
-                        uint32_t flags, bool scan_every, void* stream, Action action) {
+// ro == nullptr: no fold (ftl_collect_mlp keeps a record per step instead of a sum, and is the one caller whose `flags` may carry
+// FTL_STEP_NEXT_RESET).  post(t) enqueues whatever follows step t and its fold on `stream`, and returns an error code.
+static int rollout_scratch(ftl_handle* h) {
     if (!h->ro_alive) {
         hipError_t e = hipMalloc((void**)&h->ro_alive, align_up((size_t)h->P.n_envs, 256));
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(rollout scratch): ") + hipGetErrorString(e));
     }
+    return FTL_OK;
+}
+
+template <typename Action, typename Post>
+static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                        uint32_t flags, bool scan_every, void* stream, Action action, Post post) {
+    if (int rc = rollout_scratch(h)) return rc;
     ftlro::Args a;
     a.env_int = h->P.env_int; a.rec_stride = h->P.rec_stride; a.n_envs = h->P.n_envs;
     a.reward = out->reward; a.done = out->done; a.status = out->status;
-    a.ro = *ro; a.alive = h->ro_alive; a.disc = 1.0; a.first = 1;
+    a.ro = ro ? *ro : ftl_rollout_outputs{}; a.alive = h->ro_alive; a.disc = 1.0; a.first = 1;
     const dim3 grid((unsigned)((h->P.n_envs + 255) / 256));
-    hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    if (ro) hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
     a.first = 0;
     FtlCall call = make_call(h, 0, out);
     call.action_kind = encoding;
@@ -79,10 +87,18 @@ static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma
         call.flags = (t < T - 1 && !scan_every) ? (uint32_t)FTL_STEP_NO_SENSORS : flags;
         // (a two-stream handle forks after what action(t) enqueued, and the caller's stream has joined the side stream before the fold)
         if (int rc = launch(h, call, stream)) return rc;
-        hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+        if (ro) hipLaunchKernelGGL(ftlro::ftl_rollout_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
         a.disc = a.disc * gamma;                                // disc_{t+1} = disc_t * gamma, one rounding each
+        if (int rc = post(t)) return rc;
     }
     return launched();
+}
+
+// (the rollouts that fold and have nothing to add after a step)
+template <typename Action>
+static int rollout_loop(ftl_handle* h, int32_t encoding, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro,
+                        uint32_t flags, bool scan_every, void* stream, Action action) {
+    return rollout_loop(h, encoding, T, gamma, out, ro, flags, scan_every, stream, action, [](int32_t) { return (int)FTL_OK; });
 }
 
 extern "C" {

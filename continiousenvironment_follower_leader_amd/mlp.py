@@ -3,7 +3,12 @@ of every env (``ftl_mlp_act``), and closes the loop over T steps with one call (
 ``n_sets`` weight sets, consecutive equal blocks of envs use consecutive sets: a 65,536-env batch scores 1,024 population members on 64
 envs each in one rollout, which is all a gradient-free method (evolution strategies, the reference's neuroevolution) needs.  The
 arithmetic is fixed operation by operation (the ``ftl_mlp_act`` block of ``include/ftl.h``): ReLU hidden layers, a linear head mapped to
-the config's action space."""
+the config's action space.
+
+For a gradient method (the reference trains with PPO) ``sample()`` adds the caller's noise to the head, ``collect()`` /
+``batch.collect_mlp`` play T such decisions through episode boundaries with one call and leave a ``Trajectory`` on the device
+(``ftl_collect_mlp``), and ``gae()`` turns its rewards and kinds and a critic's values into advantages (``ftl_gae``).  The backward pass
+is torch autograd on the recorded tensors."""
 import ctypes as C
 
 import torch
@@ -37,6 +42,81 @@ def check_widths(cfg, widths):
     if widths[-1] != head:
         raise ValueError("the head of this config's action space is %d wide, not %d" % (head, widths[-1]))
     return widths
+
+
+class Trajectory:
+    """What ``MlpPolicy.collect`` leaves on the device for T steps of N envs (the blocks of ``ftl_collect_buffers``):
+    ``obs`` float32 ``[T+1, N, H*W]`` -- ``obs[t]`` decided step t, ``obs[t+1]`` is its true successor (the terminal observation where the
+    episode ended), ``obs[T]`` what the last step wrote; ``head`` float32 ``[T, N, A]`` the raw head; ``action`` ``[T, N(, 2)]`` what was
+    played, in the config's encoding; ``reward`` float64 ``[T, N]``; ``kind`` uint8 ``[T, N]`` of ``abi.FTL_TR_*``; ``noise`` / ``sigma`` the
+    caller's tensors (or None).  On a pipelined batch the rows of part k are valid on ``stream(k)``: ``join()`` before reading."""
+
+    def __init__(self, obs, head, action, reward, kind, noise=None, sigma=None):
+        self.obs, self.head, self.action, self.reward, self.kind, self.noise, self.sigma = obs, head, action, reward, kind, noise, sigma
+
+    @property
+    def valid(self):
+        """bool ``[T, N]``: a transition to learn from (not the restart step of next-step reset, not a step after the episode's end)."""
+        return self.kind != abi.FTL_TR_VOID
+
+    @property
+    def terminated(self):
+        """bool ``[T, N]``: the step ended the episode with a status other than the time limit (no bootstrap)."""
+        return self.kind == abi.FTL_TR_TERMINATED
+
+    @property
+    def truncated(self):
+        """bool ``[T, N]``: the step ended the episode at the time limit (the bootstrap continues from ``obs[t+1]``)."""
+        return self.kind == abi.FTL_TR_TRUNCATED
+
+
+_GAE_HANDLES = {}
+
+
+def _device_handle(device):
+    """A one-env handle of the default config on ``device``, kept for the process: ``ftl_gae`` reads nothing of a handle but its device."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    if index not in _GAE_HANDLES:
+        from .config import make_config
+        lib, h = _lib.load(), C.c_void_p()
+        _lib.check(lib.ftl_create(C.byref(make_config().c), 1, index, C.byref(h)), lib)
+        _GAE_HANDLES[index] = h
+    return _GAE_HANDLES[index]
+
+
+def gae(traj, values, gamma, lam, out=None):
+    """Generalised advantage estimates and value targets of a trajectory in one launch (``ftl_gae``): ``traj`` is a ``Trajectory`` or a
+    ``(reward f64 [T, N], kind u8 [T, N])`` pair, ``values`` the critic on ``obs[0 .. T]`` as float32 ``[T+1, N]`` (detached; a trailing
+    axis of 1 is accepted).  Returns ``(adv, ret)`` float32 ``[T, N]`` -- ``out=(adv, ret)`` reuses a pair.  VOID rows get 0 and cut the
+    carry, a terminated step does not bootstrap, a truncated one bootstraps from the terminal observation's value.  Float64 inside, one
+    rounding per operation (include/ftl.h)."""
+    reward, kind = (traj.reward, traj.kind) if isinstance(traj, Trajectory) else traj
+    if not (torch.is_tensor(reward) and reward.dtype == torch.float64 and reward.dim() == 2 and reward.is_cuda and reward.is_contiguous()):
+        raise ValueError("reward must be a contiguous float64 [T, N] device tensor")
+    T, N = reward.shape
+    if not (torch.is_tensor(kind) and kind.dtype == torch.uint8 and tuple(kind.shape) == (T, N) and kind.device == reward.device and kind.is_contiguous()):
+        raise ValueError("kind must be a contiguous uint8 [T, N] tensor on reward's device")
+    if T < 1 or N < 1:
+        raise ValueError("gae() needs T >= 1 and N >= 1")
+    if torch.is_tensor(values) and values.dim() == 3 and values.shape[2] == 1:
+        values = values[:, :, 0]
+    if not torch.is_tensor(values) or values.requires_grad:
+        raise ValueError("values must be a detached tensor")
+    values = values.contiguous()
+    if values.dtype != torch.float32 or tuple(values.shape) != (T + 1, N) or values.device != reward.device:
+        raise ValueError("values must be a float32 [T + 1, N] = [%d, %d] tensor on reward's device" % (T + 1, N))
+    if out is None:
+        out = (torch.empty(T, N, dtype=torch.float32, device=reward.device), torch.empty(T, N, dtype=torch.float32, device=reward.device))
+    adv, ret = out
+    for name, t in (("adv", adv), ("ret", ret)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == (T, N) and t.device == reward.device and t.is_contiguous()):
+            raise ValueError("out's %s must be a contiguous float32 [T, N] tensor on reward's device" % name)
+    lib = _lib.load()
+    h = _device_handle(reward.device)
+    stream = C.c_void_p(torch.cuda.current_stream(reward.device).cuda_stream)
+    _lib.check(lib.ftl_gae(h, T, N, reward.data_ptr(), N * 8, kind.data_ptr(), N, values.data_ptr(), float(gamma), float(lam),
+                           adv.data_ptr(), ret.data_ptr(), stream), lib)
+    return adv, ret
 
 
 class MlpPolicy:
@@ -127,6 +207,76 @@ class MlpPolicy:
                                                 (ap + lo * self.row) if record else None, self.n * self.row if record else 0, 0, s), self.lib)
         out = (b.rollout_ret, b.rollout_steps, b.rollout_status)
         return out + (actions,) if record else out
+
+    # ------------------------------------------------------------------ stochastic decisions and recorded trajectories (ftl_mlp_sample, ftl_collect_mlp)
+    def _check_noise(self, noise, sigma, lead=()):
+        """``noise`` (float32 ``lead + [N, A]``) and ``sigma`` (float32 ``[n_sets, A]``) of a sampling call, checked; either may be None."""
+        A = self.widths[-1]
+        for name, t, shape in (("noise", noise, tuple(lead) + (self.n, A)), ("sigma", sigma, (self.n_sets, A))):
+            if t is None:
+                continue
+            if (not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 %s tensor on the batch's device" % (name, list(shape)))
+        if noise is not None and sigma is None and self.encoding != abi.FTL_ACTION_DISCRETE:
+            raise ValueError("a Box head with noise needs sigma (z = y + sigma * noise)")
+
+    def sample(self, noise=None, sigma=None):
+        """One stochastic decision of every env (``ftl_mlp_sample``, one launch per part), beside ``act()``: ``noise`` float32 ``[N, A]``
+        (A the head width) is added to the head before its map -- scaled by ``sigma`` float32 ``[n_sets, A]`` on the Box heads, as a
+        Gumbel draw on Discrete(5) -- and the raw head and the observation rows the kernel read are kept in ``self.head`` ``[N, A]`` and
+        ``self.obs`` ``[N, H * W]``.  ``noise=None`` is ``act()`` bit for bit.  Returns ``action``."""
+        self.batch._need_pool()
+        self._check_noise(noise, sigma)
+        if not hasattr(self, "head"):
+            self.head = torch.zeros(self.n, self.widths[-1], dtype=torch.float32, device=self.device)
+            self.obs = torch.zeros(self.n, self.widths[0], dtype=torch.float32, device=self.device)
+        A, W0 = self.widths[-1], self.widths[0]
+        ap, hp, op = self.action.data_ptr(), self.head.data_ptr(), self.obs.data_ptr()
+        for (g, lo, net), s in zip(self._parts, self._streams(noise)):
+            _lib.check(self.lib.ftl_mlp_sample(g.h, g._out_ref, C.byref(net), (noise.data_ptr() + lo * A * 4) if noise is not None else None,
+                                               sigma.data_ptr() if sigma is not None else None, hp + lo * A * 4, op + lo * W0 * 4,
+                                               ap + lo * self.row, s), self.lib)
+        self._keep = (noise, sigma)
+        return self.action
+
+    def collect(self, T, noise=None, sigma=None, auto_reset="next_step", out=None):
+        """``batch.collect_mlp(self, ...)``."""
+        b, T = self.batch, int(T)
+        b._need_pool()
+        if T < 1:
+            raise ValueError("a trajectory needs T >= 1")
+        if auto_reset is not False and auto_reset != "next_step":
+            raise ValueError('collect() takes auto_reset=False or "next_step": the other modes put the next episode\'s first observation where '
+                             'the terminal one belongs (got %r)' % (auto_reset,))
+        self._check_noise(noise, sigma, lead=(T,))
+        A, W0, N = self.widths[-1], self.widths[0], self.n
+        if out is None:
+            out = Trajectory(obs=torch.empty(T + 1, N, W0, dtype=torch.float32, device=self.device),
+                             head=torch.empty(T, N, A, dtype=torch.float32, device=self.device),
+                             action=torch.empty(T, *self.action.shape, dtype=self.action.dtype, device=self.device),
+                             reward=torch.empty(T, N, dtype=torch.float64, device=self.device),
+                             kind=torch.empty(T, N, dtype=torch.uint8, device=self.device))
+        else:
+            want = dict(obs=((T + 1, N, W0), torch.float32), head=((T, N, A), torch.float32),
+                        action=((T,) + tuple(self.action.shape), self.action.dtype), reward=((T, N), torch.float64), kind=((T, N), torch.uint8))
+            for name, (shape, dtype) in want.items():
+                t = getattr(out, name, None)
+                if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
+                    raise ValueError("out.%s must be a contiguous %s %s tensor on the batch's device" % (name, dtype, list(shape)))
+        out.noise, out.sigma = noise, sigma
+        flags = abi.FTL_STEP_NEXT_RESET if auto_reset == "next_step" else 0
+        for (g, lo, net), s in zip(self._parts, self._streams(noise)):
+            cb = abi.CollectBuffers()
+            cb.obs, cb.head, cb.action = out.obs.data_ptr() + lo * W0 * 4, out.head.data_ptr() + lo * A * 4, out.action.data_ptr() + lo * self.row
+            cb.reward, cb.kind = out.reward.data_ptr() + lo * 8, out.kind.data_ptr() + lo
+            cb.noise = (noise.data_ptr() + lo * A * 4) if noise is not None else None
+            cb.sigma = sigma.data_ptr() if sigma is not None else None
+            cb.obs_step_bytes, cb.head_step_bytes, cb.action_step_bytes = N * W0 * 4, N * A * 4, N * self.row
+            cb.reward_step_bytes, cb.kind_step_bytes, cb.noise_step_bytes = N * 8, N, N * A * 4
+            _lib.check(self.lib.ftl_collect_mlp(g.h, T, g._out_ref, C.byref(net), C.byref(cb), flags, s), self.lib)
+        self._keep = out                                            # (the parts' streams write into it: it outlives the call)
+        return out
 
     def fitness(self):
         """f64[n_sets]: the mean of the last rollout's returns over every set's envs (joins a pipelined batch)."""

@@ -304,6 +304,19 @@ class _BatchBase:
             raise ValueError("rollout_mlp() takes an MlpPolicy of this batch")
         return policy.rollout(T, gamma, record)
 
+    def collect_mlp(self, policy, T, noise=None, sigma=None, auto_reset="next_step", out=None):
+        """``T`` stochastic closed-loop steps of a feed-forward policy population through episode boundaries with one call and no host
+        round trip, recorded for a policy-gradient method (``ftl_collect_mlp``): per step ``policy.sample(noise[t], sigma)``,
+        ``step(auto_reset=...)`` and a record of the reward and of what kind of transition it was.  ``noise`` float32 ``[T, N, A]`` and
+        ``sigma`` float32 ``[n_sets, A]`` as ``MlpPolicy.sample`` takes them (None: the deterministic policy).  ``auto_reset`` is
+        ``"next_step"`` -- ``obs[t+1]`` is the true successor of every transition, and the restart step is marked ``FTL_TR_VOID`` -- or
+        ``False`` (finished envs stay done; every later row is VOID).  Returns an ``mlp.Trajectory`` (``out=`` reuses one of the same
+        shape); ``mlp.gae`` turns it and a critic's values into advantages.  Bit-identical to the loop it replaces.  Does not join a
+        pipelined batch, like ``step``."""
+        if getattr(policy, "batch", None) is not self or not hasattr(policy, "widths"):
+            raise ValueError("collect_mlp() takes an MlpPolicy of this batch")
+        return policy.collect(T, noise, sigma, auto_reset, out)
+
     def terminated_truncated(self):
         """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
         truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap

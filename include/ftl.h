@@ -873,6 +873,93 @@ int ftl_mlp_act(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, void*
 int ftl_rollout_mlp(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_mlp* net,
                     void* actions /* [T] blocks in the head's encoding, or NULL */, int64_t step_bytes, uint32_t flags /* 0 */, void* stream);
 
+/* ---- policy-gradient trajectories: stochastic decisions, T recorded closed-loop steps through episode boundaries, advantages ---------
+ * What a gradient method (the reference trains its followers with PPO) needs of the device: ftl_mlp_sample is ftl_mlp_act with
+ * exploration and a record of what it read and computed, ftl_collect_mlp plays T such decisions with one call and leaves the trajectory
+ * on the device, ftl_gae turns rewards, episode boundaries and the caller's values into advantages and value targets.  The backward
+ * pass is the caller's (torch autograd on the recorded tensors).  No transcendental function runs on the device, so the numpy twin
+ * (tests/collect_numpy.py) stays exact.
+ *
+ * ftl_mlp_sample (ftl_mlp_sample_kernel, csrc/ftl_mlp.hpp: the body of ftl_mlp_kernel, one launch, one decision).  The net, the layers
+ * and the checks are those of ftl_mlp_act; it differs in three places, each optional by pointer (NULL: left out):
+ *   obs_rec   float32 [n][width[0]]: while the first layer stages its chunk of the tile's policy_obs rows, the same threads store the same
+ *             floats here -- the row is read once and written once, there is no copy kernel.
+ *   head_rec  float32 [n][width[L]]: y_j = acc of the head layer, before any map.
+ *   noise     float32 [n][width[L]], the caller's draws (row 0 = env 0 of the handle); sigma float32 [n_sets][width[L]], DEVICE memory (a
+ *             learnable log_std.exp() costs no host synchronisation), indexed by the env's weight set.  Every operation is one float64
+ *             rounding (the unit is built with -ffp-contract=off):
+ *     Box heads (width 2 and 1)  z = (double)y_j + (double)sigma_j * (double)noise_j -- the product of two float32 is exact in float64 --,
+ *                                u = fmin(fmax(z, -1.0), 1.0), and the rest of the head map of ftl_mlp_act unchanged.
+ *     Discrete(5)                s_j = (double)y_j + (double)noise_j: the caller's Gumbel draw; sigma is ignored.  k = 0; for j = 1 .. 4:
+ *                                if (s_j > s_k) k = j -- the first maximum, a NaN never beats anything.
+ *     noise == NULL              bit for bit the action of ftl_mlp_act (as is a noise of zeros with a finite sigma).
+ *   The log-probability of what was played needs no kernel.  Box heads: the action is a deterministic map of z, and under the Gaussian
+ *   z ~ N(y, sigma^2) the density of the draw is logp = sum_j (-0.5 * noise_j^2 - log(sigma_j) - 0.5 * log(2 * pi)); with new parameters
+ *   the same draw is z_j = head_j + sigma_j * noise_j of the RECORD and logp' = sum_j (-0.5 * ((z_j - y'_j) / sigma'_j)^2 - log(sigma'_j)
+ *   - 0.5 * log(2 * pi)).  Discrete(5): logp = log_softmax(head)[action] of the recorded head at the recorded action (Gumbel-max samples
+ *   the softmax).
+ *   FTL_E_INVALID before any device work: what ftl_mlp_act refuses, a Box head with noise but no sigma, and noise / sigma / head_rec /
+ *   obs_rec not 4-byte aligned.
+ *
+ * ftl_collect_mlp: for t = 0 .. T-1 the sample kernel (reading noise block t, writing obs / head / action block t), the step with
+ * `flags` -- every step scans --, then ftl_collect_record_kernel, one thread per env; after step T-1 one device-to-device copy of
+ * policy_obs to obs block T.  One call, asynchronous on `stream`, the loop of ftl_rollout_mlp (csrc/ftl_rollout.hpp: rollout_loop)
+ * without the fold.  Block t of an array lies at base + t * its *_step_bytes, so the parts of a pipelined batch write their rows of one
+ * [T][N] tensor (row 0 of a block = env 0 of the handle).
+ *   flags     0, or FTL_STEP_NEXT_RESET: the call in which an episode ends returns its terminal observation, so obs[t+1] is always the
+ *             true successor of transition t -- the value bootstrap of a time-limit truncation needs no second buffer -- and the restart
+ *             step is a transition to ignore.  FTL_STEP_AUTO_RESET, FTL_STEP_QUEUE_RESET and FTL_STEP_SAMPLE_RESET replace the terminal
+ *             observation in `out` by the next episode's and are refused with a message that says so; FTL_STEP_NO_SENSORS is refused as
+ *             in ftl_rollout_mlp.
+ *   record    reward[t][e] = out->reward[e], and kind[t][e]:
+ *     FTL_TR_VOID        the env's done word was set ON ENTRY to step t.  Under FTL_STEP_NEXT_RESET this is the restart step: its action was
+ *                        ignored, its reward is 0 and obs[t+1] is the new episode's first observation.  Under flags = 0 it is every step
+ *                        after the one that ended the episode.
+ *     FTL_TR_TRUNCATED   the step raised done with mission status FTL_MISSION_FINISHED_BY_TIME
+ *     FTL_TR_TERMINATED  the step raised done with any other status
+ *     FTL_TR_STEP        otherwise
+ *             "Done on entry" is a byte per env in the handle's rollout scratch (the one ftl_rollout_fold_kernel keeps): set from the
+ *             state's done word before step 0 and from out->done after every step, so an env that is done at reset stays VOID until it
+ *             restarts into a live world.
+ *   Contract  `out`, every state byte and every recorded block equal T iterations of ftl_mlp_sample + ftl_step_encoded(flags) + the
+ *             record, bit for bit.  With flags = 0 and noise = NULL the state and `action` equal ftl_rollout_mlp with a record.
+ *   FTL_E_INVALID before any device work: what ftl_mlp_sample refuses, NULL h / out / net / b, a NULL obs / head / action / reward / kind,
+ *   T <= 0, a refused flag, a *_step_bytes below one block of its array ([n][width[0]] f32, [n][width[L]] f32, the encoded actions, [n]
+ *   f64, [n] u8; noise_step_bytes only with noise), base pointers or strides not aligned to their element (4, 4, the action element, 8,
+ *   1, 4).  FTL_E_STATE as for ftl_rollout_mlp.
+ *
+ * ftl_gae (ftl_gae_kernel, one launch, one thread per env, t from T-1 down to 0, loads coalesced over n; the handle only names the
+ * device).  reward / kind are the blocks ftl_collect_mlp wrote (any strides of at least n elements), values is the caller's critic on
+ * obs[0 .. T], float32 [T+1][n] dense; adv and ret are float32 [T][n] dense.  All arithmetic is float64 with one rounding per
+ * operation; gl = gamma * lambda is rounded once on the host; r = reward[t][e], v_t = (double)values[t][e]; the carry c starts at 0.0:
+ *     FTL_TR_VOID        adv = ret = 0.0f; c = 0.0 (and nothing below)
+ *     FTL_TR_TERMINATED  c = r - v_t
+ *     FTL_TR_TRUNCATED   x = gamma * v_{t+1}; y = r + x; c = y - v_t        (v_{t+1}: the value of the terminal observation)
+ *     FTL_TR_STEP        x = gamma * v_{t+1}; y = r + x; d = y - v_t; z = gl * c; c = d + z
+ *     then               adv[t][e] = (float)c; ret[t][e] = (float)(c + v_t)
+ *   Any other kind byte is read as FTL_TR_STEP.  FTL_E_INVALID before any device work: NULL pointers, T <= 0, n <= 0, a stride below n
+ *   elements, reward / reward_step_bytes not 8-byte or values / adv / ret not 4-byte aligned. */
+enum { FTL_TR_STEP = 0, FTL_TR_TERMINATED = 1, FTL_TR_TRUNCATED = 2, FTL_TR_VOID = 3 };
+typedef struct ftl_collect_buffers {   /* DEVICE pointers; block t of an array at base + t * its *_step_bytes */
+    float*   obs;     /* [T+1] blocks [n][width[0]] f32: obs[t] is what decided step t, obs[T] what the last step wrote */
+    float*   head;    /* [T]   blocks [n][width[L]] f32: raw head */
+    void*    action;  /* [T]   blocks in the head's encoding: what was played */
+    double*  reward;  /* [T]   blocks [n] */
+    uint8_t* kind;    /* [T]   blocks [n]: FTL_TR_* */
+    const float* noise;  /* optional, [T] blocks [n][width[L]] */
+    const float* sigma;  /* [n_sets][width[L]]; needed with noise on a Box head */
+    int64_t obs_step_bytes, head_step_bytes, action_step_bytes, reward_step_bytes, kind_step_bytes, noise_step_bytes;
+} ftl_collect_buffers;
+size_t ftl_sizeof_collect_buffers(void);
+int ftl_mlp_sample(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, const float* noise, const float* sigma, float* head_rec,
+                   float* obs_rec, void* action, void* stream);
+int ftl_collect_mlp(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_mlp* net, const ftl_collect_buffers* b,
+                    uint32_t flags /* 0 or FTL_STEP_NEXT_RESET */, void* stream);
+int ftl_gae(const ftl_handle* h /* device only */, int32_t T, int32_t n,
+            const double* reward, int64_t reward_step_bytes, const uint8_t* kind, int64_t kind_step_bytes,
+            const float* values /* [T+1][n], dense */, double gamma, double lambda,
+            float* adv, float* ret /* [T][n], dense */, void* stream);
+
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
  * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
