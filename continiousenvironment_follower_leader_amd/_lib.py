@@ -26,6 +26,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_baseline.hpp"),
            os.path.join(_PKG, "csrc", "ftl_mlp.hpp"),
            os.path.join(_PKG, "csrc", "ftl_collect.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_rnn.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_rnn_math.hpp"),
            os.path.join(_PKG, "csrc", "ftl_search.hpp"),
            os.path.join(_PKG, "csrc", "ftl_guided.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
@@ -161,6 +163,17 @@ def load():
     lib.ftl_collect_mlp.restype = C.c_int
     lib.ftl_gae.argtypes = [vp, i32, i32, vp, C.c_int64, vp, C.c_int64, vp, C.c_double, C.c_double, vp, vp, vp]
     lib.ftl_gae.restype = C.c_int
+    lib.ftl_sizeof_rnn.restype = C.c_size_t
+    lib.ftl_sizeof_rnn_collect_buffers.restype = C.c_size_t
+    lib.ftl_rnn_param_count.argtypes = [C.POINTER(i32), i32, i32, u32]
+    lib.ftl_rnn_param_count.restype = C.c_int64
+    lib.ftl_rnn_act.argtypes = [vp, C.POINTER(abi.Outputs), C.POINTER(abi.Rnn), vp, vp, vp, vp, vp, vp, u32, vp]
+    lib.ftl_rnn_act.restype = C.c_int
+    lib.ftl_rollout_rnn.argtypes = [vp, i32, C.c_double, C.POINTER(abi.Outputs), C.POINTER(abi.RolloutOutputs), C.POINTER(abi.Rnn), vp, C.c_int64,
+                                    u32, vp]
+    lib.ftl_rollout_rnn.restype = C.c_int
+    lib.ftl_collect_rnn.argtypes = [vp, i32, C.POINTER(abi.Outputs), C.POINTER(abi.Rnn), C.POINTER(abi.RnnCollectBuffers), u32, vp]
+    lib.ftl_collect_rnn.restype = C.c_int
     lib.ftl_sizeof_episode_record.restype = C.c_size_t
     lib.ftl_sizeof_episode_queue.restype = C.c_size_t
     lib.ftl_set_episode_queue.argtypes = [vp, C.POINTER(abi.EpisodeQueueC)]
@@ -207,6 +220,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_sizeof_guided_buffers", "ftl_baseline_act_guided", "ftl_rollout_guided", "ftl_guided_fanout", "ftl_search_guided",
            "ftl_sizeof_mlp", "ftl_mlp_param_count", "ftl_mlp_act", "ftl_rollout_mlp",
            "ftl_sizeof_collect_buffers", "ftl_mlp_sample", "ftl_collect_mlp", "ftl_gae",
+           "ftl_sizeof_rnn", "ftl_sizeof_rnn_collect_buffers", "ftl_rnn_param_count", "ftl_rnn_act", "ftl_rollout_rnn", "ftl_collect_rnn",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

@@ -274,6 +274,37 @@ class CollectBuffers(C.Structure):
                 ("reward_step_bytes", C.c_int64), ("kind_step_bytes", C.c_int64), ("noise_step_bytes", C.c_int64)]
 
 
+# the recurrent policy (include/ftl.h, ftl_rnn_act): the cell limit, the bits of ftl_rnn.flags, the flag of a call, the cells of a gate pass
+FTL_RNN_MAX_CELL = 128
+FTL_RNN_PREV_ACTION, FTL_RNN_PREV_REWARD = 1, 2
+FTL_RNN_ZERO_ON_OUT_DONE = 1
+FTL_RNN_PASS_CELLS = 64
+
+
+def rnn_widths(widths, cell, flags):
+    """(P, R, U, S) of a recurrent net: the widths of a_prev and r_prev in the cell input, the cell input's width, the floats of a state row."""
+    head = int(widths[-1])
+    P, R = (head if flags & FTL_RNN_PREV_ACTION else 0), (1 if flags & FTL_RNN_PREV_REWARD else 0)
+    return P, R, int(widths[-2]) + P + R + int(cell), 2 * int(cell) + P + 1
+
+
+def rnn_param_count(widths, cell, flags):
+    """Floats of one weight set (``ftl_rnn_param_count``): the trunk ``widths[:-1]`` as in ``mlp_param_count``, W_g ``[U][4C]``, b_g
+    ``[4C]``, W_y ``[C][A]``, b_y ``[A]``; ``widths[-1]`` is the head width."""
+    U = rnn_widths(widths, cell, flags)[2]
+    return mlp_param_count(widths[:-1]) + (U + 1) * 4 * int(cell) + (int(cell) + 1) * int(widths[-1])
+
+
+class Rnn(C.Structure):
+    """ftl_rnn: ftl_mlp's fields (``n_layers`` the trunk's layers, the head width after the trunk's widths), the cell and its state."""
+    _fields_ = Mlp._fields_ + [("cell", C.c_int32), ("flags", C.c_uint32), ("state", C.c_void_p), ("state_stride", C.c_int64)]
+
+
+class RnnCollectBuffers(C.Structure):
+    """ftl_rnn_collect_buffers: ``CollectBuffers`` plus where the state rows every decision read are recorded."""
+    _fields_ = [("b", CollectBuffers), ("state", C.c_void_p), ("state_step_bytes", C.c_int64), ("state_steps", C.c_int32), ("_pad", C.c_int32)]
+
+
 class EpisodeRecord(C.Structure):
     """ftl_episode_record: one row per entry of an episode queue, written once (``RECORD_DTYPE`` is the same row for numpy)."""
     _fields_ = [("state", C.c_int32), ("scenario", C.c_int32), ("env", C.c_int32), ("frames", C.c_int32), ("calls", C.c_int32),

@@ -1,0 +1,504 @@
+// ftl_rnn.hpp -- a recurrent policy, or a population of them, on the device: a trunk of dense ReLU layers, one LSTM cell and a linear
+// head (include/ftl.h, the ftl_rnn_act block, is the contract).  One decision of every env with its state update (ftl_rnn_act), T
+// closed-loop steps (ftl_rollout_rnn) and a recorded trajectory (ftl_collect_rnn).  Included by ftl_abi.hip after ftl_collect.hpp (same
+// translation unit: it reads the handle, uses the head maps of ftl_mlp.hpp and the record kernel of ftl_collect.hpp, and hands its
+// kernel to rollout_loop, which owns the steps; there is no second loop here).
+//
+// ftl_rnn_kernel keeps the plan of ftl_mlp_kernel: one workgroup of 256 threads per tile of up to FTL_MLP_ENV_TILE envs of ONE weight set,
+// everything in one launch, activations in LDS between the layers, a layer's weights staged in LDS in k-chunks, the products on
+// v_mfma_f32_16x16x4_f32 with the bias as the C operand (the contract's fmaf chain: tests/test_gpu_mlp.py).  The layer loop is a copy of
+// mlp_body's (ftl_mlp_kernel and ftl_mlp_sample_kernel keep their code and their resource rows) with two generalisations: input and
+// output are separate LDS arrays, and the staged columns of the gate layer go through a column map.
+//   trunk   layers 0 .. Lt-1 as in ftl_mlp_kernel; the last one writes x into the first width[Lt] columns of u.
+//   gather  u[e] = [x | a_prev | r_prev | h]: the rest of the row comes from the env's state row and out->reward (all zeros where mode
+//           BEFORE reads a finished env as fresh); the same threads store h | a_prev | live to state_rec.
+//   gates   a dense layer over u in passes of at most 64 cells: a pass computes the columns {q * C + j0 + jj}, q = 0 .. 3 (i, f, g, o), of
+//           the torch-ordered W_g -- at most 256, what a tile's accumulators hold.  The column map (gate_col) gives the four gates of a
+//           cell to the four accumulators acc[4 * gs + q] of ONE lane, so z never leaves the registers: the lane that holds z of (4 envs,
+//           2 cells) reads their c from HBM, runs the cell lines (ftl_rnn_math.hpp), writes h' to an LDS array of its own -- later
+//           passes still read the old h in u -- and c', h' to the state row (zeros in mode AFTER at an env that was done on entry).
+//           Nothing reads h or c from HBM after the gather / its own lane, so the row is updated in place.
+//   head    a dense layer h' -> y, then one thread per env: the head map of ftl_mlp_sample, a_prev' and live.
+// LDS is sized from the actual widths (rnn_lds_bytes): 61.25 KiB for 180-64-64, C = 64 (two workgroups a CU), and at the limits (widths
+// 256, C = 128, head 5) 125.25 KiB of the 160 KiB a workgroup may have.
+#include <hip/hip_runtime.h>
+#include "ftl_rnn_math.hpp"
+
+#define FTL_RNN_PASS_CELLS 64          // cells of one gate pass: 4 * 64 = FTL_MLP_MAX_WIDTH columns
+
+namespace ftlrnn {
+
+using ftlmlp::f32x4;
+using ftlmlp::TILE; using ftlmlp::KC; using ftlmlp::EPW; using ftlmlp::NB; using ftlmlp::GROUPS; using ftlmlp::PARITIES; using ftlmlp::BPW; using ftlmlp::XS;
+static_assert(4 * FTL_RNN_PASS_CELLS == FTL_MLP_MAX_WIDTH && FTL_RNN_MAX_CELL % FTL_RNN_PASS_CELLS == 0, "a gate pass fills a tile's accumulators");
+
+struct Args {
+    ftlmlp::Args m;            // the trunk as ftl_mlp_kernel's arguments: n_layers = Lt, width[0 .. Lt]; head, bounds, action, the tile map
+    int32_t cell, P, R, A;     // C; widths of a_prev and r_prev in u; the head width
+    int32_t u_stride, h_stride;                // floats per env row of u and h' in LDS (each % 32 == 2)
+    float* state; int64_t state_stride;
+    float* state_rec;          // [n_envs][S] or null
+    const double* reward; const uint8_t* out_done;
+    const uint8_t* alive;      // mode AFTER inside a loop: the rollout scratch; null: the state's done word
+    const int32_t* env_int; int32_t rec_stride;
+    int32_t before;            // 1: mode BEFORE
+};
+
+// The staged columns of a gate pass.  A wave of parity p owns the column blocks jb = p + PARITIES * m, m < BPW = 8; in a gate pass block
+// (p, m) holds gate q = m & 3 of the 16 cells of group G = 2 * (m >> 2) + p, so the lane that holds accumulator rows of cell G * 16 + li
+// holds all four gates of that cell (acc[4 * (m >> 2) + q]) and the cell lines run in registers.  cn <= 64 cells of the pass are real;
+// a column of a cell past cn is staged from the pass's last cell and never used.
+struct Gates { int cn, C, j0; };
+constexpr int NLD = 16;                  // weights of a chunk a thread has in flight from L2 at a time: a 4,096-float chunk in one go
+__device__ __forceinline__ int gate_group(int par, int m) { return 2 * (m >> 2) + par; }
+__device__ __forceinline__ int gate_col(const Gates& gm, int c) {
+    const int jb = c >> 4, m = jb >> 1, jj = gate_group(jb & 1, m) * NB + (c & 15);
+    return (m & 3) * gm.C + gm.j0 + (jj < gm.cn ? jj : gm.cn - 1);
+}
+static_assert(PARITIES == 2 && BPW == 8 && NB == 16 && FTL_RNN_PASS_CELLS == 4 * NB, "the gate map");
+
+// The accumulators of one dense layer of a tile: acc of column j = chain over k of x[e][k] * W[k][col(j)] from bias[col(j)].
+// GATES false: col(j) = j, j < w_out, W is [w_in][w_out].  GATES true: col = gate_col, w_out is the staged width (128 for up to 32 cells of
+// the pass, else 256), W is W_g with rows of ldw floats.  obs != null: x is read from HBM (the policy_obs rows, staged in xs chunk by chunk
+// and copied to obs_rec); else from xin in LDS.
+template <bool GATES>
+__device__ __forceinline__ void layer_acc(f32x4 (&acc)[BPW], const float* W, int ldw, const float* bias, const Gates gm, int w_in, int w_out,
+                                          const float* obs, float* obs_rec, int start, int tile_n,
+                                          const float* xin, int xin_stride, float* xs, float* ws) {
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, lk = lane >> 4;
+    const int g = wave % GROUPS, par = wave / GROUPS;
+    const int row_a = g * EPW + li, row_d = g * EPW + 4 * lk;
+    const bool busy = g * EPW < tile_n;
+    const int nblk = (w_out + NB - 1) / NB;
+    bool on[BPW];                                               // (wave-uniform) the block holds columns somebody reads
+#pragma unroll
+    for (int m = 0; m < BPW; m++) {
+        const int jb = par + PARITIES * m, j = jb * NB + li;
+        on[m] = GATES ? gate_group(par, m) * NB < gm.cn : jb < nblk;
+        const float b = !on[m] ? 0.0f : GATES ? bias[gate_col(gm, j)] : j < w_out ? bias[j] : 0.0f;
+        acc[m] = f32x4{b, b, b, b};
+    }
+    const int kc = ftlmlp::chunk_rows(w_out);
+    const int xstride = obs ? XS : xin_stride;
+    for (int k0 = 0; k0 < w_in; k0 += kc) {
+        const int kn = w_in - k0 < kc ? w_in - k0 : kc;
+        __syncthreads();                                        // the chunk before this one has been read (and, k0 == 0, the input written)
+        // (NLD loads are issued before the first is stored, so a thread waits for L2 once per NLD floats, not once per float)
+        const int sh = w_out == 128 ? 7 : 8;
+        for (int base = t; base < kn * w_out; base += NLD * FTL_MLP_THREADS) {
+            float v[NLD];
+#pragma unroll
+            for (int i = 0; i < NLD; i++) {
+                const int idx = base + i * FTL_MLP_THREADS, ok = idx < kn * w_out, at = ok ? idx : base;
+                v[i] = GATES ? W[(size_t)(k0 + (at >> sh)) * ldw + gate_col(gm, at & (w_out - 1))] : W[(size_t)k0 * w_out + at];
+            }
+#pragma unroll
+            for (int i = 0; i < NLD; i++) {
+                const int idx = base + i * FTL_MLP_THREADS;
+                if (idx < kn * w_out) ws[idx] = v[i];
+            }
+        }
+        if (obs) {
+            const int e = t >> 3;                               // 8 threads per env of the tile
+            if (e < tile_n) {
+                const size_t row = (size_t)(start + e) * w_in + k0;
+                if (obs_rec)
+                    for (int kk = t & 7; kk < kn; kk += 8) { const float v = obs[row + kk]; xs[e * XS + kk] = v; obs_rec[row + kk] = v; }
+                else
+                    for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = obs[row + kk];
+            }
+        }
+        __syncthreads();
+        if (!busy) continue;
+        const float* x = obs ? xs : xin + k0;
+        const float* xa = x + row_a * xstride + lk;
+        const float* xd = x + row_d * xstride;
+        int kk = 0;
+        for (; kk + 4 <= kn; kk += 4) {
+            const float av = xa[kk];
+            const float* wrow = ws + (kk + lk) * w_out + li;    // columns past w_out read on into the stage
+#pragma unroll
+            for (int m = 0; m < BPW; m++)
+                if (on[m]) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wrow[(par + PARITIES * m) * NB], acc[m], 0, 0, 0);
+        }
+        for (; kk < kn; kk++) {                                  // w_in % 4 rows at the layer's end
+#pragma unroll
+            for (int m = 0; m < BPW; m++) {
+                if (!on[m]) continue;
+                const float w = ws[kk * w_out + (par + PARITIES * m) * NB + li];
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc[m][r] = __builtin_fmaf(xd[r * xstride + kk], w, acc[m][r]);
+            }
+        }
+    }
+}
+
+// One dense layer of a tile into LDS: y[e][j], j < w_out; relu as in ftl_mlp_kernel.  yout may be xin.
+__device__ __forceinline__ void dense(const float* W, const float* bias, int w_in, int w_out, const float* obs, float* obs_rec, int start, int tile_n,
+                                      const float* xin, int xin_stride, float* yout, int y_stride, bool relu, float* xs, float* ws) {
+    f32x4 acc[BPW];
+    layer_acc<false>(acc, W, w_out, bias, Gates{0, 0, 0}, w_in, w_out, obs, obs_rec, start, tile_n, xin, xin_stride, xs, ws);
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, lk = lane >> 4;
+    const int row_d = (wave % GROUPS) * EPW + 4 * lk, par = wave / GROUPS;
+    __syncthreads();                                            // every wave has read this layer's input
+#pragma unroll
+    for (int m = 0; m < BPW; m++) {
+        const int j = (par + PARITIES * m) * NB + li;
+        if (j >= w_out) continue;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float v = acc[m][r];
+            yout[(row_d + r) * y_stride + j] = relu ? (v > 0.0f ? v : 0.0f) : v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_rnn_kernel(const Args a, const ftlmlp::Sample sm) {
+    extern __shared__ float4 rnn_lds[];
+    const ftlmlp::Args& m = a.m;
+    float* act = reinterpret_cast<float*>(rnn_lds);             // [TILE][act_stride]: the trunk between its layers, then y
+    float* u = act + TILE * m.act_stride;                       // [TILE][u_stride]
+    float* hn = u + TILE * a.u_stride;                          // [TILE][h_stride]: h'
+    float* xs = hn + TILE * a.h_stride;                         // [TILE][XS]
+    float* ws = xs + TILE * XS;                                 // the weight stage (+ 64 floats never used)
+    const int t = (int)threadIdx.x;
+    // the tile's set and envs (as in mlp_body)
+    int set = m.env_first / m.envs_per_set, start, end;
+    if ((int)blockIdx.x < m.tiles0) { start = (int)blockIdx.x * TILE; end = m.len0; }
+    else {
+        const int b = (int)blockIdx.x - m.tiles0, q = b / m.tiles_per_set;
+        const int64_t seg = (int64_t)m.len0 + (int64_t)q * m.envs_per_set, seg_end = seg + m.envs_per_set;
+        set += 1 + q;
+        start = (int)seg + (b % m.tiles_per_set) * TILE;
+        end = seg_end < (int64_t)m.n_envs ? (int)seg_end : m.n_envs;
+    }
+    const int tile_n = end - start < TILE ? end - start : TILE;
+    const float* P = m.params + (int64_t)set * m.set_stride;
+    const int Lt = m.n_layers, C = a.cell, wx = m.width[Lt], U = wx + a.P + a.R + C, S = 2 * C + a.P + 1;
+    for (int l = 0; l < Lt; l++) {
+        const int w_in = m.width[l], w_out = m.width[l + 1];
+        const bool last = l + 1 == Lt;
+        dense(P, P + (size_t)w_in * w_out, w_in, w_out, l == 0 ? m.obs : nullptr, sm.obs_rec, start, tile_n,
+              act, m.act_stride, last ? u : act, last ? a.u_stride : m.act_stride, true, xs, ws);
+        P += ((size_t)w_in + 1) * w_out;
+    }
+    // gather the rest of u; the env's "read as fresh" and "write zeros" predicates
+    const int tail = a.P + a.R + C;
+    for (int idx = t; idx < tile_n * tail; idx += FTL_MLP_THREADS) {
+        const int e = idx / tail, k = idx - e * tail;
+        const size_t env = (size_t)start + e;
+        const bool fresh = a.before && a.out_done[env] != 0;
+        const float* row = a.state + env * a.state_stride;
+        float* rec = a.state_rec ? a.state_rec + env * S : nullptr;
+        float v;
+        if (k < a.P) {
+            v = fresh ? 0.0f : row[2 * C + k];
+            if (rec) rec[2 * C + k] = v;
+        } else if (k < a.P + a.R) {
+            const float live = fresh ? 0.0f : row[2 * C + a.P];
+            v = live != 0.0f ? (float)a.reward[env] : 0.0f;
+        } else {
+            const int j = k - a.P - a.R;
+            v = fresh ? 0.0f : row[j];
+            if (rec) rec[j] = v;
+        }
+        u[e * a.u_stride + wx + k] = v;
+    }
+    if (a.state_rec && t < tile_n) {
+        const size_t env = (size_t)start + t;
+        const bool fresh = a.before && a.out_done[env] != 0;
+        a.state_rec[env * S + 2 * C + a.P] = fresh ? 0.0f : a.state[env * a.state_stride + 2 * C + a.P];
+    }
+    // (layer_acc() begins with a barrier: u is complete before any wave reads it)
+    const float* Wg = P;
+    const float* bg = Wg + (size_t)U * 4 * C;
+    const int lane = t & 63, wave = t >> 6, li = lane & 15, row_d = (wave % GROUPS) * EPW + 4 * (lane >> 4), par = wave / GROUPS;
+    for (int j0 = 0; j0 < C; j0 += FTL_RNN_PASS_CELLS) {
+        const int cn = C - j0 < FTL_RNN_PASS_CELLS ? C - j0 : FTL_RNN_PASS_CELLS;
+        f32x4 z[BPW];
+        layer_acc<true>(z, Wg, 4 * C, bg, Gates{cn, C, j0}, U, cn <= 2 * NB ? 128 : 256, nullptr, nullptr, start, tile_n, u, a.u_stride, xs, ws);
+#pragma unroll
+        for (int gs = 0; gs < 2; gs++) {                            // the lane's two cells of the pass, four envs each
+            const int jj = gate_group(par, 4 * gs) * NB + li, j = j0 + jj;
+            if (jj >= cn) continue;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int e = row_d + r;
+                if (e >= tile_n) continue;
+                const size_t env = (size_t)start + e;
+                const bool done_in = a.alive ? a.alive[env] == 0
+                                   : reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(a.env_int) + env * (size_t)a.rec_stride)[FTL_EI_DONE] != 0;
+                const bool fresh = a.before && a.out_done[env] != 0, wipe = !a.before && done_in;
+                float* row = a.state + env * a.state_stride;
+                const float c = fresh ? 0.0f : row[C + j];
+                if (a.state_rec) a.state_rec[env * S + C + j] = c;
+                const float gi = ftlrnnmath::sig32(z[4 * gs][r]);
+                const float gf = ftlrnnmath::sig32(z[4 * gs + 1][r]);
+                const float gg = ftlrnnmath::tanh32(z[4 * gs + 2][r]);
+                const float go = ftlrnnmath::sig32(z[4 * gs + 3][r]);
+                const float tt = gi * gg;
+                const float cn1 = __builtin_fmaf(gf, c, tt);
+                const float th = ftlrnnmath::tanh32(cn1);
+                const float hn1 = go * th;
+                hn[e * a.h_stride + j] = hn1;                       // (an array of its own: later passes still read the old h in u)
+                row[j] = wipe ? 0.0f : hn1;
+                row[C + j] = wipe ? 0.0f : cn1;
+            }
+        }
+    }
+    const float* Wy = bg + 4 * C;
+    dense(Wy, Wy + (size_t)C * a.A, C, a.A, nullptr, nullptr, start, tile_n, hn, a.h_stride, act, m.act_stride, false, xs, ws);
+    __syncthreads();
+    if (t >= tile_n) return;
+    const float* y = act + t * m.act_stride;
+    const size_t e = (size_t)start + t;
+    const int wl = a.A;
+    if (sm.head_rec)
+        for (int j = 0; j < wl; j++) sm.head_rec[e * wl + j] = y[j];
+    float ap[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (m.head == FTL_ACTION_DISCRETE) {
+        int k = 0;
+        if (sm.noise) {                                         // s_j = y_j + noise_j in float64; the first maximum, a NaN never beats anything
+            const float* nz = sm.noise + e * wl;
+            double best = (double)y[0] + (double)nz[0];
+            for (int j = 1; j < 5; j++) {
+                const double sj = (double)y[j] + (double)nz[j];
+                if (sj > best) { best = sj; k = j; }
+            }
+        } else {
+            for (int j = 1; j < 5; j++) if (y[j] > y[k]) k = j;
+        }
+        static_cast<int32_t*>(m.action)[e] = k;
+#pragma unroll
+        for (int j = 0; j < 5; j++) ap[j] = j == k ? 1.0f : 0.0f;
+    } else {
+        const float* nz = sm.noise ? sm.noise + e * wl : nullptr;
+        const float* sg = sm.noise ? sm.sigma + (size_t)set * wl : nullptr;
+        if (m.head == FTL_ACTION_BOX2) {
+            const double a0 = nz ? ftlmlp::box_sample(y[0], sg[0], nz[0], m.lo0, m.hi0) : ftlmlp::box_head(y[0], m.lo0, m.hi0);
+            const double a1 = nz ? ftlmlp::box_sample(y[1], sg[1], nz[1], m.lo1, m.hi1) : ftlmlp::box_head(y[1], m.lo1, m.hi1);
+            static_cast<double*>(m.action)[2 * e] = a0;
+            static_cast<double*>(m.action)[2 * e + 1] = a1;
+            ap[0] = (float)a0; ap[1] = (float)a1;
+        } else {
+            const double a1 = nz ? ftlmlp::box_sample(y[0], sg[0], nz[0], m.lo1, m.hi1) : ftlmlp::box_head(y[0], m.lo1, m.hi1);
+            static_cast<double*>(m.action)[e] = a1;
+            ap[0] = (float)a1;
+        }
+    }
+    const bool done_in = a.alive ? a.alive[e] == 0
+                       : reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(a.env_int) + e * (size_t)a.rec_stride)[FTL_EI_DONE] != 0;
+    const bool wipe = !a.before && done_in;
+    float* row = a.state + e * a.state_stride + 2 * C;
+#pragma unroll
+    for (int j = 0; j < 5; j++)
+        if (j < a.P) row[j] = wipe ? 0.0f : ap[j];
+    row[a.P] = wipe ? 0.0f : 1.0f;
+}
+
+}  // namespace ftlrnn
+
+static int32_t rnn_prev_width(int32_t head_width, uint32_t flags) { return (flags & FTL_RNN_PREV_ACTION) ? head_width : 0; }
+
+// floats of one weight set; -1 outside the limits of include/ftl.h
+static int64_t rnn_param_count(const int32_t* w, int32_t Lt, int32_t C, uint32_t flags) {
+    if (!w || Lt < 1 || Lt > FTL_MLP_MAX_LAYERS - 1 || C < 1 || C > FTL_RNN_MAX_CELL || (flags & ~3u)) return -1;
+    const int64_t trunk = mlp_param_count(w, Lt);
+    const int32_t A = w[Lt + 1];
+    if (trunk < 0 || (A != 1 && A != 2 && A != 5)) return -1;
+    const int64_t U = (int64_t)w[Lt] + rnn_prev_width(A, flags) + ((flags & FTL_RNN_PREV_REWARD) ? 1 : 0) + C;
+    return trunk + (U + 1) * 4 * C + ((int64_t)C + 1) * A;
+}
+
+static size_t rnn_lds_bytes(const ftlrnn::Args& a) {
+    return ((size_t)FTL_MLP_ENV_TILE * ((size_t)a.m.act_stride + a.u_stride + a.h_stride + ftlmlp::XS) + FTL_MLP_W_STAGE + 64) * sizeof(float);
+}
+
+// the checks of the net and its state that every entry shares (those of mlp_args, in its order, then the cell and the state); fills the
+// kernel's arguments but for action / state_rec / alive / before, its grid and its LDS bytes
+static int rnn_args(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, ftlrnn::Args& a, unsigned& grid, size_t& lds) {
+    if (!h || !out || !net || !net->params) return fail(FTL_E_INVALID, "null argument");
+    const int32_t Lt = net->n_layers;
+    if (Lt < 1) return fail(FTL_E_INVALID, "rnn: n_layers must be at least 1");
+    if (Lt > FTL_MLP_MAX_LAYERS - 1) return fail(FTL_E_UNSUPPORTED, "rnn: more than FTL_MLP_MAX_LAYERS - 1 trunk layers");
+    for (int l = 0; l <= Lt + 1; l++) {
+        if (net->width[l] < 1) return fail(FTL_E_INVALID, "rnn: every width must be at least 1");
+        if (net->width[l] > (l == 0 ? FTL_MLP_MAX_IN : FTL_MLP_MAX_WIDTH))
+            return fail(FTL_E_UNSUPPORTED, l == 0 ? "rnn: input width beyond FTL_MLP_MAX_IN" : "rnn: layer width beyond FTL_MLP_MAX_WIDTH");
+    }
+    if (net->cell < 1) return fail(FTL_E_INVALID, "rnn: cell must be at least 1");
+    if (net->cell > FTL_RNN_MAX_CELL) return fail(FTL_E_UNSUPPORTED, "rnn: cell beyond FTL_RNN_MAX_CELL");
+    if (net->flags & ~(uint32_t)(FTL_RNN_PREV_ACTION | FTL_RNN_PREV_REWARD)) return fail(FTL_E_INVALID, "rnn: unknown bit in ftl_rnn.flags");
+    const int32_t wl = net->width[Lt + 1], C = net->cell;
+    if (wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "rnn: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
+    if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "rnn: params must be 4-byte aligned");
+    if (net->set_stride < rnn_param_count(net->width, Lt, C, net->flags)) return fail(FTL_E_INVALID, "rnn: set_stride below ftl_rnn_param_count");
+    if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "rnn: n_sets and envs_per_set must be at least 1, env_first at least 0");
+    const int64_t n = h->P.n_envs, eps = net->envs_per_set, first = net->env_first;
+    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, "rnn: the handle's last env lies beyond the last weight set");
+    if (!out->policy_obs || h->P.pol_h <= 0 || h->P.pol_width <= 0) return fail(FTL_E_INVALID, "rnn: the policy reads policy_obs (ftl_outputs.policy_obs, a config with a sensor for it)");
+    if ((int64_t)net->width[0] != (int64_t)h->P.pol_h * h->P.pol_width) return fail(FTL_E_INVALID, "rnn: width[0] must be H * W of policy_obs");
+    const int32_t P = rnn_prev_width(wl, net->flags), R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0, S = 2 * C + P + 1;
+    if (!net->state) return fail(FTL_E_INVALID, "rnn: state is NULL");
+    if (((uintptr_t)net->state) & 3) return fail(FTL_E_INVALID, "rnn: state must be 4-byte aligned");
+    if (net->state_stride < S) return fail(FTL_E_INVALID, "rnn: state_stride below S = 2 * cell + P + 1");
+    if (!out->reward || !out->done) return fail(FTL_E_INVALID, "rnn: the policy reads out->reward and out->done");
+    ftlmlp::Args& m = a.m;
+    m.obs = out->policy_obs; m.params = net->params; m.set_stride = net->set_stride;
+    m.n_envs = (int32_t)n; m.n_layers = Lt; m.env_first = net->env_first; m.envs_per_set = net->envs_per_set;
+    int wmax = wl;                                              // act holds the trunk's inner layers and y
+    for (int l = 0; l <= FTL_MLP_MAX_LAYERS; l++) {
+        m.width[l] = l <= Lt ? net->width[l] : 0;
+        if (l >= 1 && l < Lt && m.width[l] > wmax) wmax = m.width[l];
+    }
+    m.act_stride = ((wmax + 31) & ~31) + 2;
+    const int64_t tile = FTL_MLP_ENV_TILE;
+    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0;
+    m.len0 = (int32_t)len0; m.tiles0 = (int32_t)((len0 + tile - 1) / tile); m.tiles_per_set = (int32_t)((eps + tile - 1) / tile);
+    grid = (unsigned)(m.tiles0 + (rem / eps) * m.tiles_per_set + (rem % eps + tile - 1) / tile);
+    m.head = wl == 2 ? FTL_ACTION_BOX2 : wl == 1 ? FTL_ACTION_TURN : FTL_ACTION_DISCRETE;
+    const ftl_robot_params& f = h->P.cfg.follower;
+    m.lo0 = f.min_speed; m.hi0 = f.max_speed; m.lo1 = -f.max_rotation_speed; m.hi1 = f.max_rotation_speed;
+    m.action = nullptr;
+    a.cell = C; a.P = P; a.R = R; a.A = wl;
+    const int U = net->width[Lt] + P + R + C;
+    a.u_stride = ((U + 31) & ~31) + 2; a.h_stride = ((C + 31) & ~31) + 2;
+    a.state = net->state; a.state_stride = net->state_stride; a.state_rec = nullptr;
+    a.reward = out->reward; a.out_done = out->done; a.alive = nullptr;
+    a.env_int = h->P.env_int; a.rec_stride = h->P.rec_stride; a.before = 0;
+    lds = rnn_lds_bytes(a);
+    return FTL_OK;
+}
+
+// dynamic LDS above 64 KiB is asked for on the current device before the launch (harmless where the runtime needs no asking; a launch that
+// is refused all the same is reported by launched())
+static int rnn_kernel_ready(size_t lds) {
+    if (lds > 160 * 1024) return fail(FTL_E_UNSUPPORTED, "rnn: the net needs more than 160 KiB of LDS per workgroup");
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)ftlrnn::ftl_rnn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return FTL_OK;
+}
+
+extern "C" {
+
+size_t ftl_sizeof_rnn(void) { return sizeof(ftl_rnn); }
+size_t ftl_sizeof_rnn_collect_buffers(void) { return sizeof(ftl_rnn_collect_buffers); }
+
+int64_t ftl_rnn_param_count(const int32_t* widths, int32_t n_layers, int32_t cell, uint32_t flags) { return rnn_param_count(widths, n_layers, cell, flags); }
+
+int ftl_rnn_act(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, const float* noise, const float* sigma, float* head_rec,
+                float* obs_rec, float* state_rec, void* action, uint32_t flags, void* stream) {
+    if (!action) return fail(FTL_E_INVALID, "null argument");
+    ftlrnn::Args a; unsigned grid; size_t lds;
+    if (int rc = rnn_args(h, out, net, a, grid, lds)) return rc;
+    if (flags & ~(uint32_t)FTL_RNN_ZERO_ON_OUT_DONE) return fail(FTL_E_INVALID, "ftl_rnn_act takes no flag but FTL_RNN_ZERO_ON_OUT_DONE");
+    if (((uintptr_t)action) & (a.m.head == FTL_ACTION_DISCRETE ? 3 : 7)) return fail(FTL_E_INVALID, "ftl_rnn_act: action not aligned to its element");
+    if (int rc = mlp_sample_check("ftl_rnn_act", a.m.head, noise, sigma, head_rec, obs_rec)) return rc;
+    if (((uintptr_t)state_rec) & 3) return fail(FTL_E_INVALID, "ftl_rnn_act: state_rec must be 4-byte aligned");
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (int rc = rnn_kernel_ready(lds)) return rc;
+    a.m.action = action; a.state_rec = state_rec; a.before = (flags & FTL_RNN_ZERO_ON_OUT_DONE) ? 1 : 0;
+    const ftlmlp::Sample sm{noise, sigma, head_rec, obs_rec};
+    hipLaunchKernelGGL(ftlrnn::ftl_rnn_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
+    return launched();
+}
+
+int ftl_rollout_rnn(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_rnn* net,
+                    void* actions, int64_t step_bytes, uint32_t flags, void* stream) {
+    if (!h || !out || !net) return fail(FTL_E_INVALID, "null argument");
+    if (flags & FTL_STEP_NO_SENSORS)
+        return fail(FTL_E_INVALID, "ftl_rollout_rnn refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
+    if (int rc = rollout_check("ftl_rollout_rnn", ro, T, 0, flags)) return rc;
+    ftlrnn::Args a; unsigned grid; size_t lds;
+    if (int rc = rnn_args(h, out, net, a, grid, lds)) return rc;
+    const int64_t block = (int64_t)h->P.n_envs * (int64_t)mlp_action_bytes(a.m.head);
+    if (actions && step_bytes < block) return fail(FTL_E_INVALID, "ftl_rollout_rnn: step_bytes below one block of encoded actions");
+    if (actions && ((((uintptr_t)actions) | (uintptr_t)step_bytes) & (a.m.head == FTL_ACTION_DISCRETE ? 3 : 7)))
+        return fail(FTL_E_INVALID, "ftl_rollout_rnn: actions and step_bytes not aligned to the action element");
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (int rc = rnn_kernel_ready(lds)) return rc;
+    if (!actions && !h->bl_action) {                            // (16 bytes per env: any encoding fits the baseline's scratch)
+        hipError_t e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
+        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(policy actions): ") + hipGetErrorString(e));
+    }
+    if (int rc = rollout_scratch(h)) return rc;
+    a.alive = h->ro_alive;                                      // (the fold's first pass sets it from the state before decision 0 reads it)
+    const ftlmlp::Sample sm{nullptr, nullptr, nullptr, nullptr};
+    return rollout_loop(h, a.m.head, T, gamma, out, ro, 0, true, stream, [&](int32_t t) {
+        a.m.action = actions ? (void*)((char*)actions + (int64_t)t * step_bytes) : (void*)h->bl_action;
+        hipLaunchKernelGGL(ftlrnn::ftl_rnn_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
+        return a.m.action;
+    });
+}
+
+int ftl_collect_rnn(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_rnn* net, const ftl_rnn_collect_buffers* rb, uint32_t flags, void* stream) {
+    if (!h || !out || !net || !rb) return fail(FTL_E_INVALID, "null argument");
+    const ftl_collect_buffers* b = &rb->b;
+    if (flags & FTL_STEP_NO_SENSORS)
+        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
+    if (flags & FTL_STEP_AUTO_RESET)
+        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_AUTO_RESET: a same-step reset puts the next episode's first observation where "
+                                   "the terminal one belongs, so obs[t+1] would not be the successor of transition t (FTL_STEP_NEXT_RESET keeps it)");
+    if (flags & FTL_STEP_QUEUE_RESET)
+        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_QUEUE_RESET: the queue restarts a finished env inside the step that ended its "
+                                   "episode, so obs[t+1] would not be the successor of transition t (FTL_STEP_NEXT_RESET keeps it)");
+    if (flags & FTL_STEP_SAMPLE_RESET)
+        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_SAMPLE_RESET: the sampler restarts a finished env inside the step that ended its "
+                                   "episode, so obs[t+1] would not be the successor of transition t (FTL_STEP_NEXT_RESET keeps it)");
+    if (flags & ~(uint32_t)FTL_STEP_NEXT_RESET) return fail(FTL_E_INVALID, "ftl_collect_rnn takes no flag but FTL_STEP_NEXT_RESET");
+    if (T <= 0) return fail(FTL_E_INVALID, "ftl_collect_rnn: T must be positive");
+    ftlrnn::Args a; unsigned grid; size_t lds;
+    if (int rc = rnn_args(h, out, net, a, grid, lds)) return rc;
+    if (!b->obs || !b->head || !b->action || !b->reward || !b->kind)
+        return fail(FTL_E_INVALID, "ftl_collect_buffers: obs / head / action / reward / kind missing");
+    if (!rb->state) return fail(FTL_E_INVALID, "ftl_rnn_collect_buffers: state missing (at least block 0: the rows decision 0 read)");
+    if (rb->state_steps != 1 && rb->state_steps != T) return fail(FTL_E_INVALID, "ftl_rnn_collect_buffers: state_steps must be 1 or T");
+    const int64_t n = h->P.n_envs, wl = a.A, arow = (int64_t)mlp_action_bytes(a.m.head), S = 2 * (int64_t)a.cell + a.P + 1;
+    if (b->obs_step_bytes < n * net->width[0] * 4 || b->head_step_bytes < n * wl * 4 || b->action_step_bytes < n * arow ||
+        b->reward_step_bytes < n * 8 || b->kind_step_bytes < n || (b->noise && b->noise_step_bytes < n * wl * 4) ||
+        (rb->state_steps > 1 && rb->state_step_bytes < n * S * 4))
+        return fail(FTL_E_INVALID, "ftl_collect_buffers: a *_step_bytes below one block of its array");
+    if (((((uintptr_t)b->obs) | (uintptr_t)b->obs_step_bytes | ((uintptr_t)b->head) | (uintptr_t)b->head_step_bytes) & 3) ||
+        ((((uintptr_t)b->action) | (uintptr_t)b->action_step_bytes) & (uintptr_t)(arow == 4 ? 3 : 7)) ||
+        ((((uintptr_t)b->reward) | (uintptr_t)b->reward_step_bytes) & 7) || (b->noise && (b->noise_step_bytes & 3)) ||
+        ((((uintptr_t)rb->state) | (uintptr_t)(rb->state_steps > 1 ? rb->state_step_bytes : 0)) & 3))
+        return fail(FTL_E_INVALID, "ftl_collect_buffers: a base pointer or a *_step_bytes not aligned to the element of its array");
+    if (int rc = mlp_sample_check("ftl_collect_rnn", a.m.head, b->noise, b->sigma, b->head, b->obs)) return rc;
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (int rc = rnn_kernel_ready(lds)) return rc;
+    if (int rc = rollout_scratch(h)) return rc;
+    ftlcol::Args r;
+    r.env_int = h->P.env_int; r.rec_stride = h->P.rec_stride; r.n_envs = h->P.n_envs;
+    r.reward = out->reward; r.done = out->done; r.status = out->status;
+    r.alive = h->ro_alive; r.rec_reward = nullptr; r.rec_kind = nullptr; r.first = 1;
+    const dim3 rgrid((unsigned)((h->P.n_envs + 255) / 256));
+    hipLaunchKernelGGL(ftlcol::ftl_collect_record_kernel, rgrid, dim3(256), 0, (hipStream_t)stream, r);
+    r.first = 0;
+    a.alive = h->ro_alive;
+    ftlmlp::Sample sm{nullptr, b->sigma, nullptr, nullptr};
+    const int rc = rollout_loop(h, a.m.head, T, 1.0, out, nullptr, flags, true, stream,
+        [&](int32_t t) {
+            sm.noise = b->noise ? (const float*)((const char*)b->noise + (int64_t)t * b->noise_step_bytes) : nullptr;
+            sm.head_rec = (float*)((char*)b->head + (int64_t)t * b->head_step_bytes);
+            sm.obs_rec = (float*)((char*)b->obs + (int64_t)t * b->obs_step_bytes);
+            a.m.action = (char*)b->action + (int64_t)t * b->action_step_bytes;
+            a.state_rec = t < rb->state_steps ? (float*)((char*)rb->state + (int64_t)t * rb->state_step_bytes) : nullptr;
+            hipLaunchKernelGGL(ftlrnn::ftl_rnn_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
+            return a.m.action;
+        },
+        [&](int32_t t) {
+            r.rec_reward = (double*)((char*)b->reward + (int64_t)t * b->reward_step_bytes);
+            r.rec_kind = b->kind + (int64_t)t * b->kind_step_bytes;
+            hipLaunchKernelGGL(ftlcol::ftl_collect_record_kernel, rgrid, dim3(256), 0, (hipStream_t)stream, r);
+            return (int)FTL_OK;
+        });
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync((char*)b->obs + (int64_t)T * b->obs_step_bytes, out->policy_obs, (size_t)n * net->width[0] * 4,
+                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMemcpyAsync(obs[T]): ") + hipGetErrorString(e));
+    return FTL_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,207 @@
+"""A recurrent policy on the device, or a population of them: ``RecurrentPolicy`` is a trunk of dense ReLU layers, one LSTM cell and a
+linear head on the batch's ``policy_obs`` (the reference's ``*_lstm`` architectures with ``lstm_use_prev_action`` /
+``lstm_use_prev_reward``).  One decision with its state update is one launch (``ftl_rnn_act``); ``batch.rollout_rnn`` closes the loop over T
+steps and ``batch.collect_rnn`` records a PPO-ready trajectory through episode boundaries, each with one call.  The arithmetic is fixed
+operation by operation, ``sigmoid`` and ``tanh`` included (the ``ftl_rnn_act`` block of ``include/ftl.h``).
+
+The state is a ``[N, S]`` float32 tensor, a row ``h | c | a_prev | live``; the device zeroes a row at the episode boundary, so that no
+memory of a finished episode leaks into the next one: after the void decision at a finished env (``auto_reset`` False or "next_step"), or
+before the first decision on the new episode's observation ("same_step", "queue", "sample")."""
+import ctypes as C
+
+import torch
+
+from . import _lib, abi
+from .mlp import MlpPolicy, Trajectory, check_widths, head_encoding
+
+_BEFORE = ("same_step", "queue", "sample")
+
+
+class RecurrentPolicy(MlpPolicy):
+    """``n_sets`` recurrent nets on ``batch`` (a ``VecGame`` or a ``PipelinedVecGame`` built with ``policy_obs=True``): ``widths`` names
+    the input width, the trunk's layers and the head width -- ``(180, 64, 64, 2)`` is 180 -> 64 -> 64 -> cell -> 2 --, ``cell`` the LSTM
+    units; ``prev_action`` / ``prev_reward`` feed the last action (one-hot on Discrete(5)) and the last reward to the cell.  Env e uses
+    set ``e // (batch.n // n_sets)``.
+
+    ``params`` is the float32 ``[n_sets, param_count]`` device tensor of all weights (zeros unless given); ``layer(l)``,
+    ``cell_weights()`` and ``head_weights()`` are views into it and ``load_lstm_cell`` copies a ``torch.nn.LSTMCell``.  ``state`` is the
+    ``[N, S]`` state (zeros: every env at the start of an episode).  ``auto_reset`` names the reset discipline of the ``step`` calls that
+    ``act()`` / ``sample()`` are used with: it decides where the state is zeroed.  ``act()``, ``sample()`` and the call operator return the
+    persistent action tensor like ``MlpPolicy``; like ``step`` they do not join a pipelined batch."""
+
+    def __init__(self, batch, widths, cell, n_sets=1, params=None, prev_action=True, prev_reward=True, auto_reset="next_step"):
+        widths = tuple(int(w) for w in widths)
+        if len(widths) < 3:
+            raise ValueError("widths must name the input width, at least one trunk layer and the head width")
+        check_widths(batch.cfg, widths)                            # (the trunk and the head obey the limits of a feed-forward net one layer deeper)
+        cell = int(cell)
+        if cell < 1:
+            raise ValueError("cell must be at least 1")
+        if cell > abi.FTL_RNN_MAX_CELL:
+            raise NotImplementedError("at most %d LSTM units" % abi.FTL_RNN_MAX_CELL)
+        if auto_reset is not False and auto_reset != "next_step" and auto_reset not in _BEFORE:
+            raise ValueError('auto_reset must be False, "next_step", "same_step", "queue" or "sample" (got %r)' % (auto_reset,))
+        self.cell, self.auto_reset = cell, auto_reset
+        self.flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+        self.P, self.R, self.U, self.S = abi.rnn_widths(widths, cell, self.flags)
+        self.widths, self.trunk = widths, widths[:-1]
+        self.encoding, _ = head_encoding(batch.cfg)
+        pol = getattr(batch, "policy_obs", None)
+        if pol is None:
+            raise ValueError("the policy reads policy_obs: build the batch with policy_obs=True on a config that has a sensor for it")
+        if widths[0] != pol.shape[1] * pol.shape[2]:
+            raise ValueError("widths[0] must be H * W = %d of policy_obs, not %d" % (pol.shape[1] * pol.shape[2], widths[0]))
+        n_sets = int(n_sets)
+        if n_sets < 1 or batch.n % n_sets:
+            raise ValueError("n_sets must divide the batch's %d envs" % batch.n)
+        self.batch, self.n, self.device, self.n_sets, self.envs_per_set = batch, batch.n, batch.device, n_sets, batch.n // n_sets
+        self.param_count = abi.rnn_param_count(widths, cell, self.flags)
+        if params is None:
+            params = torch.zeros(n_sets, self.param_count, dtype=torch.float32, device=self.device)
+        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (n_sets, self.param_count)
+                or params.device != self.device or not params.is_contiguous()):
+            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the batch's device" % self.param_count)
+        self.params = params
+        self.state = torch.zeros(self.n, self.S, dtype=torch.float32, device=self.device)
+        self.lib = _lib.load()
+        if self.lib.ftl_rnn_param_count((C.c_int32 * len(widths))(*widths), len(widths) - 2, cell, self.flags) != self.param_count:
+            raise _lib.FtlError("ftl_rnn_param_count disagrees with abi.rnn_param_count: library and package do not match")
+        shape = (self.n, 2) if self.encoding == abi.FTL_ACTION_BOX2 else (self.n,)
+        self.action = torch.zeros(*shape, dtype=torch.int32 if self.encoding == abi.FTL_ACTION_DISCRETE else torch.float64, device=self.device)
+        self.row = self.action.element_size() * (2 if self.encoding == abi.FTL_ACTION_BOX2 else 1)
+        self.head = torch.zeros(self.n, widths[-1], dtype=torch.float32, device=self.device)
+        self.obs = torch.zeros(self.n, widths[0], dtype=torch.float32, device=self.device)
+        games = getattr(batch, "games", None)
+        self._parts = [(g, lo, self._net(lo)) for g, lo in ([(batch, 0)] if games is None else [(g, sh.lo) for g, sh in zip(games, batch.shards)])]
+
+    def _net(self, env_first):
+        net = abi.Rnn()
+        net.params, net.set_stride, net.n_sets, net.n_layers = self.params.data_ptr(), self.param_count, self.n_sets, len(self.widths) - 2
+        for l, w in enumerate(self.widths):
+            net.width[l] = w
+        net.env_first, net.envs_per_set = env_first, self.envs_per_set
+        net.cell, net.flags = self.cell, self.flags
+        net.state, net.state_stride = self.state.data_ptr() + env_first * self.S * 4, self.S
+        return net
+
+    # ------------------------------------------------------------------ views of the parameters
+    def layer(self, l):
+        """Views ``(W [n_sets, in, out], b [n_sets, out])`` of trunk layer ``l`` (0-based) in ``params``."""
+        w = self.trunk
+        if not 0 <= l < len(w) - 1:
+            raise IndexError("trunk layer %d of %d" % (l, len(w) - 1))
+        off = abi.mlp_param_count(w[:l + 1])
+        nw = w[l] * w[l + 1]
+        return self.params[:, off:off + nw].view(self.n_sets, w[l], w[l + 1]), self.params[:, off + nw:off + nw + w[l + 1]]
+
+    def cell_weights(self):
+        """Views ``(W_g [n_sets, U, 4C], b_g [n_sets, 4C])``: rows in the order ``x | a_prev | r_prev | h``, columns ``i | f | g | o``."""
+        off, n = abi.mlp_param_count(self.trunk), self.U * 4 * self.cell
+        return self.params[:, off:off + n].view(self.n_sets, self.U, 4 * self.cell), self.params[:, off + n:off + n + 4 * self.cell]
+
+    def head_weights(self):
+        """Views ``(W_y [n_sets, C, A], b_y [n_sets, A])``."""
+        A = self.widths[-1]
+        off = abi.mlp_param_count(self.trunk) + (self.U + 1) * 4 * self.cell
+        n = self.cell * A
+        return self.params[:, off:off + n].view(self.n_sets, self.cell, A), self.params[:, off + n:off + n + A]
+
+    def load_lstm_cell(self, s, lstm):
+        """Copy a ``torch.nn.LSTMCell(U - C, C)`` into set ``s``: ``weight_ih.T`` over ``weight_hh.T``, ``bias_ih + bias_hh``."""
+        if lstm.input_size != self.U - self.cell or lstm.hidden_size != self.cell:
+            raise ValueError("the cell takes %d inputs and has %d units, not %d and %d" % (self.U - self.cell, self.cell, lstm.input_size, lstm.hidden_size))
+        W, b = self.cell_weights()
+        with torch.no_grad():
+            W[s, :self.U - self.cell].copy_(lstm.weight_ih.detach().t())
+            W[s, self.U - self.cell:].copy_(lstm.weight_hh.detach().t())
+            if lstm.bias:
+                b[s].copy_((lstm.bias_ih.detach().to(torch.float32) + lstm.bias_hh.detach().to(torch.float32)))
+            else:
+                b[s].zero_()
+
+    def reset_state(self, env_ids=None):
+        """Zero the state of every env, or of ``env_ids``: the rows of a fresh episode (after a ``batch.reset`` of those envs)."""
+        if env_ids is None:
+            self.state.zero_()
+        else:
+            self.state[torch.as_tensor(env_ids, device=self.device).long()] = 0
+
+    # ------------------------------------------------------------------ decisions
+    def _mode(self):
+        return abi.FTL_RNN_ZERO_ON_OUT_DONE if self.auto_reset in _BEFORE else 0
+
+    def act(self):
+        """One deterministic decision of every env with its state update (``ftl_rnn_act``, one launch per part); returns ``action``."""
+        return self.sample()
+
+    def sample(self, noise=None, sigma=None, state_rec=None):
+        """One decision of every env with its state update: ``noise`` / ``sigma`` as ``MlpPolicy.sample`` takes them (None: the
+        deterministic map); the raw head and the observation rows are kept in ``self.head`` and ``self.obs``; ``state_rec`` (float32
+        ``[N, S]``, optional) receives the state rows as the decision read them.  Returns ``action``."""
+        self.batch._need_pool()
+        self._check_noise(noise, sigma)
+        if state_rec is not None and (not torch.is_tensor(state_rec) or state_rec.dtype != torch.float32 or tuple(state_rec.shape) != (self.n, self.S)
+                                      or state_rec.device != self.device or not state_rec.is_contiguous()):
+            raise ValueError("state_rec must be a contiguous float32 [N, %d] tensor on the batch's device" % self.S)
+        A, W0, S = self.widths[-1], self.widths[0], self.S
+        ap, hp, op = self.action.data_ptr(), self.head.data_ptr(), self.obs.data_ptr()
+        for (g, lo, net), s in zip(self._parts, self._streams(noise)):
+            _lib.check(self.lib.ftl_rnn_act(g.h, g._out_ref, C.byref(net), (noise.data_ptr() + lo * A * 4) if noise is not None else None,
+                                            sigma.data_ptr() if sigma is not None else None, hp + lo * A * 4, op + lo * W0 * 4,
+                                            (state_rec.data_ptr() + lo * S * 4) if state_rec is not None else None,
+                                            ap + lo * self.row, self._mode(), s), self.lib)
+        self._keep = (noise, sigma, state_rec)
+        return self.action
+
+    def rollout(self, T, gamma=1.0, record=False):
+        """``batch.rollout_rnn(self, ...)``."""
+        b, T = self.batch, int(T)
+        b._need_pool()
+        if T < 1:
+            raise ValueError("a rollout needs T >= 1")
+        actions = torch.empty(T, *self.action.shape, dtype=self.action.dtype, device=self.device) if record else None
+        b._prepare_rollout_outputs()
+        ap = actions.data_ptr() if record else 0
+        for (g, lo, net), s in zip(self._parts, self._streams(actions)):
+            _lib.check(self.lib.ftl_rollout_rnn(g.h, T, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), C.byref(net),
+                                                (ap + lo * self.row) if record else None, self.n * self.row if record else 0, 0, s), self.lib)
+        out = (b.rollout_ret, b.rollout_steps, b.rollout_status)
+        return out + (actions,) if record else out
+
+    def collect(self, T, noise=None, sigma=None, auto_reset="next_step", out=None, record_state=False):
+        """``batch.collect_rnn(self, ...)``."""
+        b, T = self.batch, int(T)
+        b._need_pool()
+        if T < 1:
+            raise ValueError("a trajectory needs T >= 1")
+        if auto_reset is not False and auto_reset != "next_step":
+            raise ValueError('collect() takes auto_reset=False or "next_step": the other modes put the next episode\'s first observation where '
+                             'the terminal one belongs (got %r)' % (auto_reset,))
+        self._check_noise(noise, sigma, lead=(T,))
+        A, W0, N, S = self.widths[-1], self.widths[0], self.n, self.S
+        TS = T if record_state else 1
+        want = dict(obs=((T + 1, N, W0), torch.float32), head=((T, N, A), torch.float32), action=((T,) + tuple(self.action.shape), self.action.dtype),
+                    reward=((T, N), torch.float64), kind=((T, N), torch.uint8), state=((TS, N, S), torch.float32))
+        if out is None:
+            out = Trajectory(**{k: torch.empty(*shape, dtype=dtype, device=self.device) for k, (shape, dtype) in want.items() if k != "state"})
+            out.state = torch.empty(TS, N, S, dtype=torch.float32, device=self.device)
+        else:
+            for name, (shape, dtype) in want.items():
+                t = getattr(out, name, None)
+                if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
+                    raise ValueError("out.%s must be a contiguous %s %s tensor on the batch's device" % (name, dtype, list(shape)))
+        out.noise, out.sigma = noise, sigma
+        flags = abi.FTL_STEP_NEXT_RESET if auto_reset == "next_step" else 0
+        for (g, lo, net), s in zip(self._parts, self._streams(noise)):
+            rb = abi.RnnCollectBuffers()
+            cb = rb.b
+            cb.obs, cb.head, cb.action = out.obs.data_ptr() + lo * W0 * 4, out.head.data_ptr() + lo * A * 4, out.action.data_ptr() + lo * self.row
+            cb.reward, cb.kind = out.reward.data_ptr() + lo * 8, out.kind.data_ptr() + lo
+            cb.noise = (noise.data_ptr() + lo * A * 4) if noise is not None else None
+            cb.sigma = sigma.data_ptr() if sigma is not None else None
+            cb.obs_step_bytes, cb.head_step_bytes, cb.action_step_bytes = N * W0 * 4, N * A * 4, N * self.row
+            cb.reward_step_bytes, cb.kind_step_bytes, cb.noise_step_bytes = N * 8, N, N * A * 4
+            rb.state, rb.state_step_bytes, rb.state_steps = out.state.data_ptr() + lo * S * 4, N * S * 4, TS
+            _lib.check(self.lib.ftl_collect_rnn(g.h, T, g._out_ref, C.byref(net), C.byref(rb), flags, s), self.lib)
+        self._keep = out
+        return out

@@ -317,6 +317,24 @@ class _BatchBase:
             raise ValueError("collect_mlp() takes an MlpPolicy of this batch")
         return policy.collect(T, noise, sigma, auto_reset, out)
 
+    def rollout_rnn(self, policy, T, gamma=1.0, record=False):
+        """``rollout_mlp`` for a recurrent policy population (an ``rnn.RecurrentPolicy`` of this batch; ``ftl_rollout_rnn``): every step
+        is one decision with its state update on the stream and one scanning step; a finished env's state row is zeroed.  Bit-identical
+        to ``T`` times ``policy.act()`` + ``step()``, ``policy.state`` included.  Does not join a pipelined batch, like ``step``."""
+        if getattr(policy, "batch", None) is not self or not hasattr(policy, "cell"):
+            raise ValueError("rollout_rnn() takes a RecurrentPolicy of this batch")
+        return policy.rollout(T, gamma, record)
+
+    def collect_rnn(self, policy, T, noise=None, sigma=None, auto_reset="next_step", out=None, record_state=False):
+        """``collect_mlp`` for a recurrent policy population (``ftl_collect_rnn``).  The ``mlp.Trajectory`` gains ``state`` float32
+        ``[1 or T, N, S]``: the state rows decision t read (``record_state=True``: every t; else only t = 0, what back-propagation through
+        time starts from).  The state is zeroed after the decision of every ``FTL_TR_VOID`` row, so the row the first decision of an
+        episode reads is all zeros.  ``mlp.gae`` works on the result unchanged.  Bit-identical to the loop it replaces.  Does not join a
+        pipelined batch, like ``step``."""
+        if getattr(policy, "batch", None) is not self or not hasattr(policy, "cell"):
+            raise ValueError("collect_rnn() takes a RecurrentPolicy of this batch")
+        return policy.collect(T, noise, sigma, auto_reset, out, record_state)
+
     def terminated_truncated(self):
         """(terminated, truncated) bool [N] device tensors of the last step, without a host synchronisation (needs ``final_obs=True``):
         truncated = ended and mission status FINISHED_BY_TIME (the reference's max_steps limit, ENV:1126-1134: a value bootstrap

@@ -960,6 +960,99 @@ int ftl_gae(const ftl_handle* h /* device only */, int32_t T, int32_t n,
             const float* values /* [T+1][n], dense */, double gamma, double lambda,
             float* adv, float* ret /* [T][n], dense */, void* stream);
 
+/* ---- recurrent policy: a trunk of dense ReLU layers, one LSTM cell and a linear head, as a decision, a rollout and a trajectory -------
+ * The memoryless stack above (ftl_mlp_act, ftl_rollout_mlp, ftl_mlp_sample, ftl_collect_mlp) with a state per env that the caller owns
+ * and the library zeroes at episode boundaries.  ftl_rnn_act (ftl_rnn_kernel, csrc/ftl_rnn.hpp, one launch per decision, asynchronous on
+ * `stream`) is one decision of every env; ftl_rollout_rnn and ftl_collect_rnn are ftl_rollout_mlp and ftl_collect_mlp with it.  The
+ * arithmetic is fixed operation by operation, transcendentals included, so the device equals a numpy twin bit for bit
+ * (tests/rnn_numpy.py).
+ *
+ * Net         Trunk: Lt = n_layers dense ReLU layers, 1 <= Lt <= FTL_MLP_MAX_LAYERS - 1, widths width[0 .. Lt]; the limits of the widths,
+ *             the chain of a neuron and the ReLU are exactly those of ftl_mlp_act (every trunk layer is a hidden one); width[0] = H * W
+ *             of policy_obs.  Then one LSTM cell of C = cell units, 1 <= C <= FTL_RNN_MAX_CELL.  Then a linear head of width
+ *             A = width[Lt + 1], which is 2, 1 or 5 with the encodings of ftl_mlp_act (any other: FTL_E_INVALID).  Beyond the limits:
+ *             FTL_E_UNSUPPORTED before any device work.
+ * Cell input  u = [x | a_prev | r_prev | h] of width U = width[Lt] + P + R + C: x the trunk's output; a_prev of width P under
+ *             FTL_RNN_PREV_ACTION (2 for Box(2), 1 for the turn, 5 -- one-hot -- for Discrete(5)), else P = 0; r_prev of width R = 1 under
+ *             FTL_RNN_PREV_REWARD, else R = 0; h the cell's last output.
+ * Parameters  float32 in DEVICE memory, sets and set_stride as in ftl_mlp.  One set: the trunk layers as in ftl_mlp; then W_g [U][4C]
+ *             row-major, rows in the order of u, columns gate-major i | f | g | o (torch's weight_ih.T stacked over weight_hh.T); then
+ *             b_g [4C] (a loader adds bias_ih + bias_hh); then W_y [C][A] and b_y [A].  ftl_rnn_param_count returns the count, -1 outside
+ *             the limits or on NULL.
+ * State       a device block [n][S] float32 the caller owns, row e at state + e * state_stride floats (row 0 = env 0 of the handle),
+ *             S = 2C + P + 1, state_stride >= S: a row is h [C] | c [C] | a_prev [P] | live.  live is 1.0f once the row holds a decision
+ *             of the running episode; a zeroed row is a fresh episode.
+ * One decision of env e, in this order:
+ *   1. read the row; in mode BEFORE it is read as all zeros when out->done[e] != 0.  r_prev = live != 0 ? (float)out->reward[e] : 0.0f.
+ *   2. x = the trunk.
+ *   3. z_j, j < 4C: acc = b_g[j]; for k = 0 .. U - 1: acc = fmaf(u[k], W_g[k][j], acc).
+ *   4. the cell, one float32 rounding per line, for j < C:
+ *          i = sig32(z[j]); f = sig32(z[C + j]); g = tanh32(z[2C + j]); o = sig32(z[3C + j]);
+ *          t = i * g;  c' = fmaf(f, c, t);  h' = o * tanh32(c')
+ *   5. y = the chain of the head layer over h'.  The head map, noise, sigma, head_rec and obs_rec are exactly those of ftl_mlp_sample;
+ *      noise == NULL is the deterministic map of ftl_mlp_act.
+ *   6. a_prev': Box heads (float)a_j of the float64 action just written; Discrete(5) the one-hot of k.
+ *   7. write the row: in mode AFTER, when the env was done on entry, zeros; otherwise h' | c' | a_prev' | 1.0f.  The optional
+ *      state_rec [n][S] (dense) receives the row as step 1 read it.
+ * Mode AFTER  the default: for no reset and next-step reset, where the decision at a finished env is the void one (its action is ignored
+ *             by the restart step, or nothing restarts at all), and the zeroed row is what the new episode's first decision reads.  "Done
+ *             on entry" is the state's done word env_int[FTL_EI_DONE] in ftl_rnn_act, and inside the loops the byte of the rollout scratch
+ *             that ftl_rollout_fold_kernel / ftl_collect_record_kernel keep (the same predicate that marks FTL_TR_VOID).
+ * Mode BEFORE FTL_RNN_ZERO_ON_OUT_DONE (a flag of the CALL): for same-step, queue and sample reset, where `out` already holds the next
+ *             episode's first observation beside the terminal reward and done.
+ * sig32, tanh32, exp32 (csrc/ftl_rnn_math.hpp, __host__ __device__; every line one float32 operation, the unit is built with
+ * -ffp-contract=off; divisions IEEE-rounded, subnormals kept):
+ *     exp32(a), a <= 0:  a = fmaxf(a, -86.0f); n = rintf(a * 0x1.715476p+0f); r = fmaf(n, -0x1.62e400p-1f, a);
+ *                        r = fmaf(n, -0x1.7f7d1cp-20f, r); p = Horner with fmaf over the float32 roundings of 1/5040, 1/720, 1/120, 1/24,
+ *                        1/6, 1/2, 1, 1; result ldexpf(p, (int)n)
+ *     sig32(x):          e = exp32(-fabsf(x)); d = 1.0f + e; x >= 0 ? 1.0f / d : e / d
+ *     tanh32(x):         e = exp32(-2.0f * fabsf(x)); copysignf((1.0f - e) / (1.0f + e), x)
+ *   Both return x itself when x != x.  Against float64: exp32 within 0.92 ulp, sig32 within 8.91e-8 and tanh32 within 8.93e-8 absolute.
+ *   Near 0 the relative error of tanh32 is large by cancellation ((1 - e) with e close to 1); that is accepted.
+ *
+ * ftl_rollout_rnn: ftl_rollout_mlp's signature and rules with ftl_rnn_kernel in mode AFTER as the decision; every step scans.
+ * ftl_collect_rnn: ftl_collect_mlp's signature, rules and record; ftl_rnn_collect_buffers is ftl_collect_buffers plus `state`: block t
+ * (at state + t * state_step_bytes) receives the rows decision t READ, [n][S] dense; state_steps is 1 (only block 0: what
+ * back-propagation through time starts from) or T.  Both go through the one rollout loop (csrc/ftl_rollout.hpp).  Contract: `out`, every
+ * state byte of the env, the policy's state block and every recorded block equal T iterations of ftl_rnn_act + ftl_step_encoded(flags)
+ * (+ fold / record), bit for bit.
+ * FTL_E_INVALID / FTL_E_UNSUPPORTED before any device work: what ftl_mlp_sample and ftl_collect_mlp refuse, a NULL state, a state_stride
+ * below S, a state not 4-byte aligned, an unknown flag, a cell beyond the limit (UNSUPPORTED), FTL_RNN_ZERO_ON_OUT_DONE given to a loop. */
+#define FTL_RNN_MAX_CELL 128
+#define FTL_RNN_PREV_ACTION 1u        /* ftl_rnn.flags */
+#define FTL_RNN_PREV_REWARD 2u        /* ftl_rnn.flags */
+#define FTL_RNN_ZERO_ON_OUT_DONE 1u   /* flags of ftl_rnn_act: mode BEFORE */
+typedef struct ftl_rnn {
+    const float* params;       /* DEVICE, [n_sets] sets of set_stride floats */
+    int64_t  set_stride;
+    int32_t  n_sets;
+    int32_t  n_layers;         /* Lt: the trunk's layers */
+    int32_t  width[FTL_MLP_MAX_LAYERS + 1];   /* width[0 .. Lt] the trunk, width[Lt + 1] the head */
+    int32_t  env_first;
+    int32_t  envs_per_set;
+    int32_t  _pad;
+    int32_t  cell;             /* C */
+    uint32_t flags;            /* FTL_RNN_PREV_ACTION | FTL_RNN_PREV_REWARD */
+    float*   state;            /* DEVICE, [n] rows of state_stride floats */
+    int64_t  state_stride;     /* floats between two rows, >= S */
+} ftl_rnn;
+typedef struct ftl_rnn_collect_buffers {
+    ftl_collect_buffers b;
+    float*   state;            /* [state_steps] blocks [n][S] f32: the rows decision t read */
+    int64_t  state_step_bytes;
+    int32_t  state_steps;      /* 1 or T */
+    int32_t  _pad;
+} ftl_rnn_collect_buffers;
+size_t ftl_sizeof_rnn(void);
+size_t ftl_sizeof_rnn_collect_buffers(void);
+int64_t ftl_rnn_param_count(const int32_t* widths /* [n_layers + 2] */, int32_t n_layers, int32_t cell, uint32_t flags);
+int ftl_rnn_act(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, const float* noise, const float* sigma, float* head_rec,
+                float* obs_rec, float* state_rec, void* action, uint32_t flags /* 0 or FTL_RNN_ZERO_ON_OUT_DONE */, void* stream);
+int ftl_rollout_rnn(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_rnn* net,
+                    void* actions /* [T] blocks in the head's encoding, or NULL */, int64_t step_bytes, uint32_t flags /* 0 */, void* stream);
+int ftl_collect_rnn(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_rnn* net, const ftl_rnn_collect_buffers* b,
+                    uint32_t flags /* 0 or FTL_STEP_NEXT_RESET */, void* stream);
+
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
  * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
