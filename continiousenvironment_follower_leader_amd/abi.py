@@ -244,6 +244,7 @@ class GuidedBuffers(C.Structure):
 # the MLP policy population (include/ftl.h, ftl_mlp_act): the limits of a net and the staging sizes of ftl_mlp_kernel (csrc/ftl_mlp.hpp)
 FTL_MLP_MAX_LAYERS, FTL_MLP_MAX_WIDTH, FTL_MLP_MAX_IN = 4, 256, 4096
 FTL_MLP_ENV_TILE, FTL_MLP_K_CHUNK, FTL_MLP_W_STAGE, FTL_MLP_ENVS_PER_WAVE, FTL_MLP_NEURON_BLOCK, FTL_MLP_THREADS = 32, 64, 4096, 16, 16, 256
+FTL_MLP_ACT_RELU, FTL_MLP_ACT_TANH = 0, 1          # ftl_mlp.activation: the hidden layers' function
 
 
 def mlp_param_count(widths):
@@ -259,7 +260,8 @@ def mlp_chunk_rows(w_out):
 class Mlp(C.Structure):
     """ftl_mlp: the parameters of a policy population, its shape and which envs use which weight set."""
     _fields_ = [("params", C.c_void_p), ("set_stride", C.c_int64), ("n_sets", C.c_int32), ("n_layers", C.c_int32),
-                ("width", C.c_int32 * (FTL_MLP_MAX_LAYERS + 1)), ("env_first", C.c_int32), ("envs_per_set", C.c_int32), ("_pad", C.c_int32)]
+                ("width", C.c_int32 * (FTL_MLP_MAX_LAYERS + 1)), ("env_first", C.c_int32), ("envs_per_set", C.c_int32),
+                ("activation", C.c_int32)]
 
 
 # the kinds of a recorded transition (include/ftl.h, ftl_collect_mlp): kind[t][e] of ftl_collect_buffers, read by ftl_gae

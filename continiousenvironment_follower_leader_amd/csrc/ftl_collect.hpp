@@ -123,7 +123,7 @@ int ftl_collect_mlp(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_
             sm.head_rec = (float*)((char*)b->head + (int64_t)t * b->head_step_bytes);
             sm.obs_rec = (float*)((char*)b->obs + (int64_t)t * b->obs_step_bytes);
             a.action = (char*)b->action + (int64_t)t * b->action_step_bytes;
-            hipLaunchKernelGGL(ftlmlp::ftl_mlp_sample_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
+            mlp_launch(net, a, &sm, grid, lds, stream);
             return a.action;
         },
         [&](int32_t t) {

@@ -16,7 +16,12 @@
 // weight per lane and block from LDS.  Rows past the tile's last env and columns past w_out compute on whatever the stage holds: an MFMA
 // output depends on its own row and column only, and they are never stored.
 //
-// ftl_mlp_sample_kernel is the same body (mlp_body<true>) with three optional additions, each a pointer of ftlmlp::Sample: the threads that
+// ftl_mlp_tanh_kernel and ftl_mlp_sample_tanh_kernel are the same body with the other hidden activation of include/ftl.h (ftl_mlp.activation):
+// mlp_body<SAMPLE, ACT> differs in the hidden layers' epilogue only, tanh32 of csrc/ftl_rnn_math.hpp on every accumulator value instead of
+// the ReLU select.  ACT is a compile-time constant, so the ReLU kernels are the instantiations they were (same code, same resource rows:
+// profiles/mlp_tanh_kernel_resources.txt); grid, LDS plan, tiling and MFMA path are shared.  mlp_launch picks the kernel from the net.
+//
+// ftl_mlp_sample_kernel is the same body (mlp_body<true, ..>) with three optional additions, each a pointer of ftlmlp::Sample: the threads that
 // stage a chunk of the tile's policy_obs rows store the same floats to obs_rec (the row is read from HBM once and written once), the raw
 // head outputs go to head_rec before any map, and the head map adds the caller's noise (include/ftl.h: ftl_mlp_sample).  ftl_collect_mlp
 // plays T such decisions through episode boundaries and records a trajectory (ftl_collect_record_kernel); ftl_gae_kernel turns its rewards
@@ -25,6 +30,7 @@
 // Weight traffic: a tile reads its set once from L2, ftl_mlp_param_count * 4 bytes per FTL_MLP_ENV_TILE envs (about 2 KB per env for
 // 180-64-64-2), against the whole set per env of a wave-per-env form.
 #include <hip/hip_runtime.h>
+#include "ftl_rnn_math.hpp"
 
 #define FTL_MLP_ENV_TILE 32           // envs of one workgroup
 #define FTL_MLP_K_CHUNK 64            // input rows of a layer staged at a time, at most
@@ -82,7 +88,7 @@ __device__ __forceinline__ double box_sample(float y, float sigma, float noise, 
     return box_map((double)y + p, lo, hi);
 }
 
-template <bool SAMPLE>
+template <bool SAMPLE, int ACT>
 __device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
     extern __shared__ float4 mlp_lds[];
     float* act = reinterpret_cast<float*>(mlp_lds);            // [TILE][act_stride]
@@ -162,6 +168,16 @@ __device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
         }
         __syncthreads();                                        // every wave has read this layer's input
         const bool hidden = l + 1 < a.n_layers;
+        if (ACT == FTL_MLP_ACT_TANH && hidden) {                // (block-uniform; the head layer takes the loop below, whose select then is v)
+#pragma unroll
+            for (int m = 0; m < BPW; m++) {
+                const int j = (par + PARITIES * m) * NB + li;
+                if (j >= w_out) continue;
+#pragma unroll
+                for (int r = 0; r < 4; r++) act[(row_d + r) * a.act_stride + j] = ftlrnnmath::tanh32(acc[m][r]);
+            }
+            continue;
+        }
 #pragma unroll
         for (int m = 0; m < BPW; m++) {
             const int j = (par + PARITIES * m) * NB + li;
@@ -211,9 +227,15 @@ __device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
     } else static_cast<double*>(a.action)[e] = box_head(y[0], a.lo1, a.hi1);
 }
 
-__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) { mlp_body<false>(a, Sample{}); }
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_kernel(const Args a) { mlp_body<false, FTL_MLP_ACT_RELU>(a, Sample{}); }
 
-__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_sample_kernel(const Args a, const Sample sm) { mlp_body<true>(a, sm); }
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_sample_kernel(const Args a, const Sample sm) { mlp_body<true, FTL_MLP_ACT_RELU>(a, sm); }
+
+// (four waves a SIMD asked for: left alone the allocator spreads the 32 unrolled tanh32 of the epilogue over 112 VGPRs beside the 32
+// accumulator registers, three waves a SIMD where the ReLU kernels have four; bounded it needs 96 in all, without spill or scratch)
+__global__ __launch_bounds__(FTL_MLP_THREADS, 4) void ftl_mlp_tanh_kernel(const Args a) { mlp_body<false, FTL_MLP_ACT_TANH>(a, Sample{}); }
+
+__global__ __launch_bounds__(FTL_MLP_THREADS, 4) void ftl_mlp_sample_tanh_kernel(const Args a, const Sample sm) { mlp_body<true, FTL_MLP_ACT_TANH>(a, sm); }
 
 }  // namespace ftlmlp
 
@@ -243,6 +265,8 @@ static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, f
     }
     const int32_t wl = net->width[L];
     if (wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "mlp: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
+    if (net->activation != FTL_MLP_ACT_RELU && net->activation != FTL_MLP_ACT_TANH)
+        return fail(FTL_E_INVALID, "mlp: activation must be FTL_MLP_ACT_RELU (0) or FTL_MLP_ACT_TANH (1)");
     if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "mlp: params must be 4-byte aligned");
     if (net->set_stride < mlp_param_count(net->width, L)) return fail(FTL_E_INVALID, "mlp: set_stride below ftl_mlp_param_count");
     if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "mlp: n_sets and envs_per_set must be at least 1, env_first at least 0");
@@ -270,6 +294,13 @@ static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, f
     return FTL_OK;
 }
 
+// The one launch of a decision: the kernel of the net's activation (mlp_args has checked it), with the sampling additions when `sm` is given.
+static void mlp_launch(const ftl_mlp* net, const ftlmlp::Args& a, const ftlmlp::Sample* sm, unsigned grid, size_t lds, void* stream) {
+    const bool th = net->activation == FTL_MLP_ACT_TANH;
+    if (sm) hipLaunchKernelGGL(th ? ftlmlp::ftl_mlp_sample_tanh_kernel : ftlmlp::ftl_mlp_sample_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, *sm);
+    else hipLaunchKernelGGL(th ? ftlmlp::ftl_mlp_tanh_kernel : ftlmlp::ftl_mlp_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+}
+
 // what ftl_mlp_sample and ftl_collect_mlp check of the sampling pointers alike; `name` heads the messages
 static int mlp_sample_check(const char* name, int32_t head, const float* noise, const float* sigma, const float* head_rec, const float* obs_rec) {
     if (noise && !sigma && head != FTL_ACTION_DISCRETE)
@@ -293,7 +324,7 @@ int ftl_mlp_act(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, void*
     if (int rc = check_ready(h, out)) return rc;
     if (int rc = set_device(h)) return rc;
     a.action = action;
-    hipLaunchKernelGGL(ftlmlp::ftl_mlp_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+    mlp_launch(net, a, nullptr, grid, lds, stream);
     return launched();
 }
 
@@ -308,7 +339,7 @@ int ftl_mlp_sample(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, co
     if (int rc = set_device(h)) return rc;
     a.action = action;
     const ftlmlp::Sample sm{noise, sigma, head_rec, obs_rec};
-    hipLaunchKernelGGL(ftlmlp::ftl_mlp_sample_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
+    mlp_launch(net, a, &sm, grid, lds, stream);
     return launched();
 }
 
@@ -332,7 +363,7 @@ int ftl_rollout_mlp(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* o
     }
     return rollout_loop(h, a.head, T, gamma, out, ro, 0, true, stream, [&](int32_t t) {
         a.action = actions ? (void*)((char*)actions + (int64_t)t * step_bytes) : (void*)h->bl_action;
-        hipLaunchKernelGGL(ftlmlp::ftl_mlp_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+        mlp_launch(net, a, nullptr, grid, lds, stream);
         return a.action;
     });
 }

@@ -329,6 +329,7 @@ static int rnn_args(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, f
     if (net->cell < 1) return fail(FTL_E_INVALID, "rnn: cell must be at least 1");
     if (net->cell > FTL_RNN_MAX_CELL) return fail(FTL_E_UNSUPPORTED, "rnn: cell beyond FTL_RNN_MAX_CELL");
     if (net->flags & ~(uint32_t)(FTL_RNN_PREV_ACTION | FTL_RNN_PREV_REWARD)) return fail(FTL_E_INVALID, "rnn: unknown bit in ftl_rnn.flags");
+    if (net->activation != FTL_MLP_ACT_RELU) return fail(FTL_E_UNSUPPORTED, "rnn: the trunk is ReLU: ftl_rnn.activation must be FTL_MLP_ACT_RELU (0)");
     const int32_t wl = net->width[Lt + 1], C = net->cell;
     if (wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "rnn: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
     if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "rnn: params must be 4-byte aligned");

@@ -2,14 +2,16 @@
 of every env (``ftl_mlp_act``), and closes the loop over T steps with one call (``batch.rollout_mlp``, ``ftl_rollout_mlp``).  With
 ``n_sets`` weight sets, consecutive equal blocks of envs use consecutive sets: a 65,536-env batch scores 1,024 population members on 64
 envs each in one rollout, which is all a gradient-free method (evolution strategies, the reference's neuroevolution) needs.  The
-arithmetic is fixed operation by operation (the ``ftl_mlp_act`` block of ``include/ftl.h``): ReLU hidden layers, a linear head mapped to
-the config's action space.
+arithmetic is fixed operation by operation (the ``ftl_mlp_act`` block of ``include/ftl.h``): ReLU or tanh hidden layers
+(``activation``), a linear head mapped to the config's action space.  ``params_from_torch`` / ``torch_module`` move a net between a
+``torch.nn.Sequential`` and a row of ``params``.
 
 For a gradient method (the reference trains with PPO) ``sample()`` adds the caller's noise to the head, ``collect()`` /
 ``batch.collect_mlp`` play T such decisions through episode boundaries with one call and leave a ``Trajectory`` on the device
 (``ftl_collect_mlp``), and ``gae()`` turns its rewards and kinds and a critic's values into advantages (``ftl_gae``).  The backward pass
 is torch autograd on the recorded tensors."""
 import ctypes as C
+import functools
 
 import torch
 
@@ -42,6 +44,85 @@ def check_widths(cfg, widths):
     if widths[-1] != head:
         raise ValueError("the head of this config's action space is %d wide, not %d" % (head, widths[-1]))
     return widths
+
+
+ACTIVATIONS = {"relu": abi.FTL_MLP_ACT_RELU, "tanh": abi.FTL_MLP_ACT_TANH}
+
+
+def check_activation(activation):
+    """``activation`` if it names a hidden activation of ``ftl_mlp`` (``"relu"`` or ``"tanh"``), else ``ValueError``."""
+    if not isinstance(activation, str) or activation not in ACTIVATIONS:
+        raise ValueError('activation must be "relu" or "tanh", not %r' % (activation,))
+    return activation
+
+
+def params_from_torch(module):
+    """``(widths, activation, params_row)`` of a ``torch.nn.Sequential`` that alternates ``nn.Linear`` with ``nn.ReLU`` or ``nn.Tanh`` and
+    ends in a linear layer: ``params_row`` is a new float32 tensor ``[param_count]`` on the module's device (a CPU module needs no GPU) in
+    the layout of ``ftl_mlp`` -- layer by layer ``W_l`` as ``weight.T`` (``[in][out]``) then ``b_l`` -- ready for
+    ``policy.params[s].copy_(row)``.  A net without hidden layers
+    reports ``"relu"``.  ``ValueError`` for mixed activations or anything else in the sequence (a Linear without bias included)."""
+    nn = torch.nn
+    if not isinstance(module, nn.Sequential) or len(module) % 2 == 0:
+        raise ValueError("params_from_torch reads an nn.Sequential of Linear, activation, Linear, ..., Linear")
+    widths, kinds, parts = [], set(), []
+    for i, m in enumerate(module):
+        if i % 2:
+            if type(m) not in (nn.ReLU, nn.Tanh):
+                raise ValueError("module %d: nn.ReLU or nn.Tanh expected between two linear layers, not %s" % (i, type(m).__name__))
+            kinds.add("relu" if type(m) is nn.ReLU else "tanh")
+            continue
+        if type(m) is not nn.Linear or m.bias is None:
+            raise ValueError("module %d: nn.Linear with a bias expected, not %s" % (i, type(m).__name__))
+        if widths and widths[-1] != m.in_features:
+            raise ValueError("module %d: %d inputs after a layer of %d" % (i, m.in_features, widths[-1]))
+        widths += [m.in_features, m.out_features] if not widths else [m.out_features]
+        parts += [m.weight.detach().t().reshape(-1), m.bias.detach().reshape(-1)]
+    if len(kinds) > 1:
+        raise ValueError("mixed activations: ftl_mlp has one activation for all hidden layers")
+    row = torch.cat([p.to(torch.float32) for p in parts]).contiguous()
+    return tuple(widths), (kinds.pop() if kinds else "relu"), row
+
+
+def torch_module(widths, activation, params_row=None):
+    """The inverse of ``params_from_torch``: an ``nn.Sequential`` of float32 ``nn.Linear`` layers of ``widths`` with ``nn.ReLU`` or
+    ``nn.Tanh`` between them, on the CPU; with ``params_row`` (float32 ``[param_count]``, any device) its weights and biases are copies
+    of that row, otherwise torch's own initialisation."""
+    widths = tuple(int(w) for w in widths)
+    if len(widths) < 2 or min(widths) < 1:
+        raise ValueError("widths must name the input width and at least one layer, each at least 1")
+    act = {"relu": torch.nn.ReLU, "tanh": torch.nn.Tanh}[check_activation(activation)]
+    mods = []
+    for l, (a, b) in enumerate(zip(widths[:-1], widths[1:])):
+        mods += ([act()] if l else []) + [torch.nn.Linear(a, b)]
+    module = torch.nn.Sequential(*mods)
+    if params_row is not None:
+        count = abi.mlp_param_count(widths)
+        if not torch.is_tensor(params_row) or params_row.dtype != torch.float32 or tuple(params_row.shape) != (count,):
+            raise ValueError("params_row must be a float32 [%d] tensor" % count)
+        row, off = params_row.detach(), 0
+        with torch.no_grad():
+            for lin in module[::2]:
+                a, b = lin.in_features, lin.out_features
+                lin.weight.copy_(row[off:off + a * b].view(a, b).t())
+                lin.bias.copy_(row[off + a * b:off + (a + 1) * b])
+                off += (a + 1) * b
+    return module
+
+
+def _takes_activation(init):
+    """``MlpPolicy.__init__`` with the option ``activation`` in front of it: the fifth argument, or a keyword.  The wrapped function keeps the
+    parameter list ``(batch, widths, params, n_sets)`` that the package has had since the policy arrived, which tests/test_mlp_abi.py pins
+    by introspection; the option is checked and stored here, before the body builds the parts' ``ftl_mlp`` structs from it."""
+    @functools.wraps(init)
+    def __init__(self, *args, **kw):
+        if len(args) > 4:
+            if len(args) > 5 or "activation" in kw:
+                raise TypeError("MlpPolicy(batch, widths, params=None, n_sets=1, activation=\"relu\"): too many arguments")
+            args, kw = args[:4], dict(kw, activation=args[4])
+        self.activation = check_activation(kw.pop("activation", "relu"))
+        init(self, *args, **kw)
+    return __init__
 
 
 class Trajectory:
@@ -123,6 +204,10 @@ class MlpPolicy:
     """``n_sets`` feed-forward nets of shape ``widths`` (input width first, head width last) on ``batch`` (a ``VecGame`` or a
     ``PipelinedVecGame`` built with ``policy_obs=True``); env e uses set ``e // (batch.n // n_sets)``.
 
+    ``MlpPolicy(batch, widths, params=None, n_sets=1, activation="relu")``.  ``activation`` is the hidden layers' function, ``"relu"`` or
+    ``"tanh"`` (``ftl_mlp.activation``: tanh is the fixed float32 sequence ``tanh32`` of include/ftl.h), kept as ``policy.activation``;
+    any other value is a ``ValueError``.  The head is linear either way.
+
     ``params`` is the float32 ``[n_sets, param_count]`` device tensor of all weights (zeros unless given; the caller writes into it, so an
     ES update is one torch op); ``layer(l)`` gives views of one layer's weights and biases.  ``act()`` decides for every env from the
     ``policy_obs`` the batch's last reset / step / scan wrote and returns the persistent action tensor in the config's encoding: float64
@@ -131,6 +216,7 @@ class MlpPolicy:
 
     On a pipelined batch every part works on its rows on its own stream: like ``step``, ``act()`` does not join."""
 
+    @_takes_activation
     def __init__(self, batch, widths, params=None, n_sets=1):
         self.widths = widths = check_widths(batch.cfg, widths)
         self.encoding, _ = head_encoding(batch.cfg)
@@ -165,7 +251,7 @@ class MlpPolicy:
         net.params, net.set_stride, net.n_sets, net.n_layers = self.params.data_ptr(), self.param_count, self.n_sets, len(self.widths) - 1
         for l, w in enumerate(self.widths):
             net.width[l] = w
-        net.env_first, net.envs_per_set = env_first, self.envs_per_set
+        net.env_first, net.envs_per_set, net.activation = env_first, self.envs_per_set, ACTIVATIONS[self.activation]
         return net
 
     def layer(self, l):

@@ -830,6 +830,17 @@ int ftl_search_guided(ftl_handle* real, ftl_handle* search, const ftl_search_par
  *                 acc = b[j];  for k = 0 .. width[l-1] - 1:  acc = fmaf(x[k], W[k][j], acc)
  *             one rounding per step, no split-K, no tree, no wider accumulator; f32 subnormals are kept.  Hidden layers (l < L) then apply
  *             acc > 0 ? acc : 0.0f, which maps NaN and -0 to +0.  The head layer (l = L) has no activation: y_j = acc.
+ * Activation  ftl_mlp.activation chooses the hidden layers' function for the whole net: FTL_MLP_ACT_RELU (0, what a zeroed struct has
+ *             always meant) is the line above; FTL_MLP_ACT_TANH (1) is h_j = tanh32(acc_j), tanh32 exactly the float32 operation
+ *             sequence of csrc/ftl_rnn_math.hpp that the ftl_rnn_act block below spells out (tests/mlp_tanh_numpy.py is the twin).  acc_j
+ *             is the same chain; the head stays linear, and its maps, the noise rules of ftl_mlp_sample and the weight sets are
+ *             untouched.  What differs from ReLU: -0 stays -0 (copysignf); tanh32 returns 0 for |acc| up to 2^-26 (e rounds to 1.0f: the
+ *             accepted cancellation; its smallest nonzero result is 2^-25, about 3e-8) and exactly +/-1 from |acc| = 8.66434 on
+ *             (1.0f - e rounds to 1.0f), infinities included; a NaN pre-activation stays NaN, spreads through the next chain and reaches the head, where the float64
+ *             fmin(fmax(..)) of a Box head sends it to lo and a Discrete(5) NaN never wins.  Any other value of `activation`:
+ *             FTL_E_INVALID before any device work, with a message that names `activation`, from ftl_mlp_act, ftl_mlp_sample,
+ *             ftl_rollout_mlp and ftl_collect_mlp alike.  (ftl_mlp_tanh_kernel and ftl_mlp_sample_tanh_kernel: the same body compiled
+ *             with the other epilogue; the ReLU kernels are the instantiations they were.)
  * Heads       lo / hi are the bounds of the config's action Box (follower.min_speed / max_speed for the speed, -/+ max_rotation_speed for the
  *             rotation: those of ftl_search_sample and of the env's own clip).  Every operation below is one float64 rounding, fmin / fmax as
  *             in C (a NaN operand yields the other one):
@@ -857,6 +868,8 @@ int ftl_search_guided(ftl_handle* real, ftl_handle* search, const ftl_search_par
 #define FTL_MLP_MAX_LAYERS 4
 #define FTL_MLP_MAX_WIDTH 256
 #define FTL_MLP_MAX_IN 4096
+#define FTL_MLP_ACT_RELU 0             /* ftl_mlp.activation */
+#define FTL_MLP_ACT_TANH 1
 typedef struct ftl_mlp {
     const float* params;       /* DEVICE, [n_sets] sets of set_stride floats */
     int64_t  set_stride;       /* floats between two sets */
@@ -865,7 +878,7 @@ typedef struct ftl_mlp {
     int32_t  width[FTL_MLP_MAX_LAYERS + 1];
     int32_t  env_first;        /* index of the handle's env 0 in the whole batch */
     int32_t  envs_per_set;
-    int32_t  _pad;
+    int32_t  activation;       /* FTL_MLP_ACT_*: the hidden layers (where _pad was: 0 is ReLU) */
 } ftl_mlp;
 size_t ftl_sizeof_mlp(void);
 int64_t ftl_mlp_param_count(const int32_t* widths, int32_t n_layers);   /* floats of one set; -1 outside the limits above or on NULL */
@@ -971,7 +984,8 @@ int ftl_gae(const ftl_handle* h /* device only */, int32_t T, int32_t n,
  *             the chain of a neuron and the ReLU are exactly those of ftl_mlp_act (every trunk layer is a hidden one); width[0] = H * W
  *             of policy_obs.  Then one LSTM cell of C = cell units, 1 <= C <= FTL_RNN_MAX_CELL.  Then a linear head of width
  *             A = width[Lt + 1], which is 2, 1 or 5 with the encodings of ftl_mlp_act (any other: FTL_E_INVALID).  Beyond the limits:
- *             FTL_E_UNSUPPORTED before any device work.
+ *             FTL_E_UNSUPPORTED before any device work.  ftl_rnn.activation must be FTL_MLP_ACT_RELU (0): every ftl_rnn_* entry point
+ *             answers any other value with FTL_E_UNSUPPORTED and a message that says the trunk is ReLU.
  * Cell input  u = [x | a_prev | r_prev | h] of width U = width[Lt] + P + R + C: x the trunk's output; a_prev of width P under
  *             FTL_RNN_PREV_ACTION (2 for Box(2), 1 for the turn, 5 -- one-hot -- for Discrete(5)), else P = 0; r_prev of width R = 1 under
  *             FTL_RNN_PREV_REWARD, else R = 0; h the cell's last output.
@@ -1030,7 +1044,7 @@ typedef struct ftl_rnn {
     int32_t  width[FTL_MLP_MAX_LAYERS + 1];   /* width[0 .. Lt] the trunk, width[Lt + 1] the head */
     int32_t  env_first;
     int32_t  envs_per_set;
-    int32_t  _pad;
+    int32_t  activation;       /* ftl_mlp's field: FTL_MLP_ACT_RELU (0) only */
     int32_t  cell;             /* C */
     uint32_t flags;            /* FTL_RNN_PREV_ACTION | FTL_RNN_PREV_REWARD */
     float*   state;            /* DEVICE, [n] rows of state_stride floats */
