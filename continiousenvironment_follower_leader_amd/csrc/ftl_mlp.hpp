@@ -27,6 +27,14 @@
 // plays T such decisions through episode boundaries and records a trajectory (ftl_collect_record_kernel); ftl_gae_kernel turns its rewards
 // and kinds and the caller's values into advantages.
 //
+// ftl_mlp_forward_kernel and ftl_mlp_forward_tanh_kernel evaluate the net on rows the caller supplies (include/ftl.h: ftl_mlp_forward):
+// mlp_body<false, ACT, true>, the same tile plan, LDS plan, weight staging and MFMA path, with three differences, each behind the
+// compile-time FORWARD: blockIdx.y names a block of n rows and the first layer stages its input from obs + blockIdx.y * x_block_bytes
+// (64-bit byte offsets), the tile map runs over the n rows of a block (Args.n_envs = n, set on the host), and the epilogue stores the raw
+// head -- the tile's rows are one contiguous run of tile_n * width[L] floats of y, written by all 256 threads in order -- and has no
+// action map.  The additions travel in ftlmlp::Forward, as the sampling ones do in Sample; Args is what it was, and so are the four
+// kernels above (profiles/mlp_forward_kernel_resources.txt).
+//
 // Weight traffic: a tile reads its set once from L2, ftl_mlp_param_count * 4 bytes per FTL_MLP_ENV_TILE envs (about 2 KB per env for
 // 180-64-64-2), against the whole set per env of a wave-per-env form.
 #include <hip/hip_runtime.h>
@@ -72,6 +80,12 @@ struct Sample {               // what ftl_mlp_sample_kernel adds to ftl_mlp_kern
     float* obs_rec;           // [n_envs][width[0]]: the policy_obs rows as the first layer staged them
 };
 
+struct Forward {              // what the ftl_mlp_forward kernels add: Args.obs is x, Args.n_envs the rows of a block, blockIdx.y the block
+    int64_t x_block_bytes;    // block b of the input rows at (char*)obs + b * x_block_bytes
+    float* y;                 // block b of the raw heads, [n][width[L]], at (char*)y + b * y_block_bytes
+    int64_t y_block_bytes;
+};
+
 __device__ __forceinline__ double box_map(double z, double lo, double hi) {
     const double u = fmin(fmax(z, -1.0), 1.0);
     const double s = (u + 1.0) * 0.5;
@@ -88,8 +102,8 @@ __device__ __forceinline__ double box_sample(float y, float sigma, float noise, 
     return box_map((double)y + p, lo, hi);
 }
 
-template <bool SAMPLE, int ACT>
-__device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
+template <bool SAMPLE, int ACT, bool FORWARD = false>
+__device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm, const Forward& fw = Forward{}) {
     extern __shared__ float4 mlp_lds[];
     float* act = reinterpret_cast<float*>(mlp_lds);            // [TILE][act_stride]
     float* xs = act + TILE * a.act_stride;                      // [TILE][XS]: a chunk of the input rows (first layer)
@@ -112,6 +126,8 @@ __device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
     const bool busy = g * EPW < tile_n;                         // this wave has envs
     const float* P = a.params + (int64_t)set * a.set_stride;
     const int w0 = a.width[0];
+    const float* obs = a.obs;
+    if (FORWARD) obs = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.obs) + (int64_t)blockIdx.y * fw.x_block_bytes);
     for (int l = 0; l < a.n_layers; l++) {
         const int w_in = a.width[l], w_out = a.width[l + 1], nblk = (w_out + NB - 1) / NB;
         const float* W = P;
@@ -135,9 +151,9 @@ __device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
                 if (e < tile_n) {
                     const size_t row = (size_t)(start + e) * w0 + k0;
                     if (SAMPLE && sm.obs_rec)
-                        for (int kk = t & 7; kk < kn; kk += 8) { const float v = a.obs[row + kk]; xs[e * XS + kk] = v; sm.obs_rec[row + kk] = v; }
+                        for (int kk = t & 7; kk < kn; kk += 8) { const float v = obs[row + kk]; xs[e * XS + kk] = v; sm.obs_rec[row + kk] = v; }
                     else
-                        for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = a.obs[row + kk];
+                        for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = obs[row + kk];
                 }
             }
             __syncthreads();
@@ -190,6 +206,15 @@ __device__ __forceinline__ void mlp_body(const Args& a, const Sample& sm) {
         }
     }
     __syncthreads();
+    if (FORWARD) {                                              // the raw head rows of the tile: tile_n * width[L] consecutive floats of the block
+        const int wl = a.width[a.n_layers];
+        float* y = reinterpret_cast<float*>(reinterpret_cast<char*>(fw.y) + (int64_t)blockIdx.y * fw.y_block_bytes) + (size_t)start * wl;
+        for (int idx = t; idx < tile_n * wl; idx += FTL_MLP_THREADS) {
+            const int r = idx / wl;
+            y[idx] = act[r * a.act_stride + (idx - r * wl)];
+        }
+        return;
+    }
     if (t >= tile_n) return;
     const float* y = act + t * a.act_stride;
     const size_t e = (size_t)start + t;
@@ -237,6 +262,10 @@ __global__ __launch_bounds__(FTL_MLP_THREADS, 4) void ftl_mlp_tanh_kernel(const 
 
 __global__ __launch_bounds__(FTL_MLP_THREADS, 4) void ftl_mlp_sample_tanh_kernel(const Args a, const Sample sm) { mlp_body<true, FTL_MLP_ACT_TANH>(a, sm); }
 
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_forward_kernel(const Args a, const Forward fw) { mlp_body<false, FTL_MLP_ACT_RELU, true>(a, Sample{}, fw); }
+
+__global__ __launch_bounds__(FTL_MLP_THREADS, 4) void ftl_mlp_forward_tanh_kernel(const Args a, const Forward fw) { mlp_body<false, FTL_MLP_ACT_TANH, true>(a, Sample{}, fw); }
+
 }  // namespace ftlmlp
 
 // floats of one weight set; -1 outside the limits of include/ftl.h
@@ -251,10 +280,9 @@ static int64_t mlp_param_count(const int32_t* w, int32_t L) {
 
 static size_t mlp_action_bytes(int32_t head) { return head == FTL_ACTION_BOX2 ? 16 : head == FTL_ACTION_TURN ? 8 : 4; }
 
-// the checks of the net that ftl_mlp_act and ftl_rollout_mlp share (check_ready comes after the caller's own, so that a missing state is the
-// last thing reported); fills the kernel's arguments but for `action`, its grid and its LDS bytes
-static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, ftlmlp::Args& a, unsigned& grid, size_t& lds) {
-    if (!h || !out || !net || !net->params) return fail(FTL_E_INVALID, "null argument");
+// the checks of the net itself, for `n` rows (the handle's envs, or the rows of a block of ftl_mlp_forward: `rows` names them in the last
+// message); `any_head` admits every head width of 1 .. FTL_MLP_MAX_WIDTH instead of those of the three action encodings
+static int mlp_net_check(const ftl_mlp* net, int64_t n, bool any_head, const char* rows) {
     const int32_t L = net->n_layers;
     if (L < 1) return fail(FTL_E_INVALID, "mlp: n_layers must be at least 1");
     if (L > FTL_MLP_MAX_LAYERS) return fail(FTL_E_UNSUPPORTED, "mlp: more than FTL_MLP_MAX_LAYERS layers");
@@ -264,17 +292,23 @@ static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, f
             return fail(FTL_E_UNSUPPORTED, l == 0 ? "mlp: input width beyond FTL_MLP_MAX_IN" : "mlp: layer width beyond FTL_MLP_MAX_WIDTH");
     }
     const int32_t wl = net->width[L];
-    if (wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "mlp: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
+    if (!any_head && wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "mlp: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
     if (net->activation != FTL_MLP_ACT_RELU && net->activation != FTL_MLP_ACT_TANH)
         return fail(FTL_E_INVALID, "mlp: activation must be FTL_MLP_ACT_RELU (0) or FTL_MLP_ACT_TANH (1)");
     if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "mlp: params must be 4-byte aligned");
     if (net->set_stride < mlp_param_count(net->width, L)) return fail(FTL_E_INVALID, "mlp: set_stride below ftl_mlp_param_count");
     if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "mlp: n_sets and envs_per_set must be at least 1, env_first at least 0");
-    const int64_t n = h->P.n_envs, eps = net->envs_per_set, first = net->env_first;
-    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, "mlp: the handle's last env lies beyond the last weight set");
-    if (!out->policy_obs || h->P.pol_h <= 0 || h->P.pol_width <= 0) return fail(FTL_E_INVALID, "mlp: the policy reads policy_obs (ftl_outputs.policy_obs, a config with a sensor for it)");
-    if ((int64_t)net->width[0] != (int64_t)h->P.pol_h * h->P.pol_width) return fail(FTL_E_INVALID, "mlp: width[0] must be H * W of policy_obs");
-    a.obs = out->policy_obs; a.params = net->params; a.set_stride = net->set_stride;
+    const int64_t eps = net->envs_per_set, first = net->env_first;
+    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, std::string("mlp: ") + rows + " lies beyond the last weight set");
+    return FTL_OK;
+}
+
+// the kernel's arguments that follow from a checked net and its `n` rows: everything but obs, head, the bounds and `action`; the grid's
+// tiles and the LDS bytes
+static void mlp_fill(const ftl_mlp* net, int64_t n, ftlmlp::Args& a, unsigned& grid, size_t& lds) {
+    const int32_t L = net->n_layers;
+    const int64_t eps = net->envs_per_set, first = net->env_first;
+    a.params = net->params; a.set_stride = net->set_stride;
     a.n_envs = (int32_t)n; a.n_layers = L; a.env_first = net->env_first; a.envs_per_set = net->envs_per_set;
     int wmax = 0;
     for (int l = 0; l <= FTL_MLP_MAX_LAYERS; l++) {
@@ -287,6 +321,18 @@ static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, f
     a.len0 = (int32_t)len0; a.tiles0 = (int32_t)((len0 + tile - 1) / tile); a.tiles_per_set = (int32_t)((eps + tile - 1) / tile);
     grid = (unsigned)(a.tiles0 + (rem / eps) * a.tiles_per_set + (rem % eps + tile - 1) / tile);
     lds = ((size_t)FTL_MLP_ENV_TILE * a.act_stride + (size_t)FTL_MLP_ENV_TILE * ftlmlp::XS + FTL_MLP_W_STAGE + 64) * sizeof(float);
+}
+
+// the checks of the net that ftl_mlp_act and ftl_rollout_mlp share (check_ready comes after the caller's own, so that a missing state is the
+// last thing reported); fills the kernel's arguments but for `action`, its grid and its LDS bytes
+static int mlp_args(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, ftlmlp::Args& a, unsigned& grid, size_t& lds) {
+    if (!h || !out || !net || !net->params) return fail(FTL_E_INVALID, "null argument");
+    if (int rc = mlp_net_check(net, h->P.n_envs, false, "the handle's last env")) return rc;
+    const int32_t L = net->n_layers, wl = net->width[L];
+    if (!out->policy_obs || h->P.pol_h <= 0 || h->P.pol_width <= 0) return fail(FTL_E_INVALID, "mlp: the policy reads policy_obs (ftl_outputs.policy_obs, a config with a sensor for it)");
+    if ((int64_t)net->width[0] != (int64_t)h->P.pol_h * h->P.pol_width) return fail(FTL_E_INVALID, "mlp: width[0] must be H * W of policy_obs");
+    a.obs = out->policy_obs;
+    mlp_fill(net, h->P.n_envs, a, grid, lds);
     a.head = wl == 2 ? FTL_ACTION_BOX2 : wl == 1 ? FTL_ACTION_TURN : FTL_ACTION_DISCRETE;
     const ftl_robot_params& f = h->P.cfg.follower;
     a.lo0 = f.min_speed; a.hi0 = f.max_speed; a.lo1 = -f.max_rotation_speed; a.hi1 = f.max_rotation_speed;
@@ -366,6 +412,35 @@ int ftl_rollout_mlp(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* o
         mlp_launch(net, a, nullptr, grid, lds, stream);
         return a.action;
     });
+}
+
+int ftl_mlp_forward(const ftl_handle* h, const ftl_mlp* net, int32_t n_blocks, int32_t n, const float* x, int64_t x_block_bytes,
+                    float* y, int64_t y_block_bytes, void* stream) {
+    if (!h) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: h");
+    if (!net) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: net");
+    if (!net->params) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: net->params");
+    if (!x) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: x");
+    if (!y) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: y");
+    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_mlp_forward: n_blocks and n must be at least 1");
+    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_forward: n_blocks beyond 65,535 (the blocks are the grid's second dimension)");
+    if (int rc = mlp_net_check(net, n, true, "the last row")) return rc;
+    const int64_t w0 = net->width[0], wl = net->width[net->n_layers];
+    if (x_block_bytes < (int64_t)n * w0 * 4 || (x_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_mlp_forward: x_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
+    if (y_block_bytes < (int64_t)n * wl * 4 || (y_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_mlp_forward: y_block_bytes must be a multiple of 4 of at least one block, n * width[L] * 4");
+    ftlmlp::Args a; unsigned grid; size_t lds;
+    mlp_fill(net, n, a, grid, lds);
+    if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull)       // (a grid dimension counts threads in 32 bits: 2^24 tiles, over 5e8 rows a block)
+        return fail(FTL_E_UNSUPPORTED, "ftl_mlp_forward: n beyond the 2^24 - 1 tiles of one launch; split the rows into blocks");
+    if (((uintptr_t)x) & 3) return fail(FTL_E_INVALID, "ftl_mlp_forward: x must be 4-byte aligned");
+    if (((uintptr_t)y) & 3) return fail(FTL_E_INVALID, "ftl_mlp_forward: y must be 4-byte aligned");
+    if (int rc = set_device(h)) return rc;
+    a.obs = x; a.head = 0; a.lo0 = a.hi0 = a.lo1 = a.hi1 = 0.0; a.action = nullptr;
+    const ftlmlp::Forward fw{x_block_bytes, y, y_block_bytes};
+    hipLaunchKernelGGL(net->activation == FTL_MLP_ACT_TANH ? ftlmlp::ftl_mlp_forward_tanh_kernel : ftlmlp::ftl_mlp_forward_kernel,
+                       dim3(grid, (unsigned)n_blocks), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, fw);
+    return launched();
 }
 
 }  // extern "C"

@@ -973,6 +973,39 @@ int ftl_gae(const ftl_handle* h /* device only */, int32_t T, int32_t n,
             const float* values /* [T+1][n], dense */, double gamma, double lambda,
             float* adv, float* ret /* [T][n], dense */, void* stream);
 
+/* ---- the net on recorded rows: an ftl_mlp evaluated on the caller's rows, raw heads out (a critic's values, an actor's replay) -------
+ * ftl_mlp_forward (ftl_mlp_forward_kernel / ftl_mlp_forward_tanh_kernel, csrc/ftl_mlp.hpp: the body of ftl_mlp_kernel, ONE launch for
+ * all blocks, asynchronous on `stream`; the handle only names the device, as for ftl_gae) evaluates `net` on n_blocks blocks of n rows:
+ * block b reads float32 [n][width[0]] at (char*)x + b * x_block_bytes and writes float32 [n][width[L]] at (char*)y + b * y_block_bytes.
+ * It is the library's pinned forward pass on anything that is not the live policy_obs of a handle: a trajectory's obs blocks, a replay
+ * buffer, a critic -- an ftl_mlp of head width 1 whose y is `values` of ftl_gae.
+ *   Arithmetic  row r of every block is evaluated as ftl_mlp_act evaluates an env: per neuron the k-ordered fmaf chain from the bias,
+ *               then acc > 0 ? acc : 0.0f (FTL_MLP_ACT_RELU) or tanh32(acc) (FTL_MLP_ACT_TANH) by net->activation on the hidden layers,
+ *               and a linear head.  y receives y_j = acc of the head layer, before any map: there is no action encoding here.  On the
+ *               rows ftl_mlp_sample / ftl_collect_mlp recorded as obs, with the net that played, y equals the recorded head bit for bit.
+ *               Nothing else of y is written: not the bytes between a row's end and the next row (there are none: rows are dense), not
+ *               the padding between a block's last row and the next block.
+ *   Weight set  row r of every block uses set (env_first + r) / envs_per_set: the rule of the policy stack with n in place of the
+ *               handle's env count, the same for every block.  So a part of a pipelined batch passes its rows [lo, lo + n) of a [B][N]
+ *               tensor as x + lo * width[0], env_first = lo and x_block_bytes = N * width[0] * 4 (y alike).  (env_first + n - 1) /
+ *               envs_per_set < n_sets, else FTL_E_INVALID.
+ *   Limits      those of ftl_mlp_act for the layers and widths, except that width[L] may be anything in 1 .. FTL_MLP_MAX_WIDTH.
+ *               policy_obs and the handle's H * W play no part.  n_blocks is 1 .. 65,535 (the grid's second dimension) and a block has at
+ *               most 2^24 - 1 tiles (tiles of FTL_MLP_ENV_TILE rows that end at set boundaries; over 5e8 rows): beyond either,
+ *               FTL_E_UNSUPPORTED before any device work.
+ *   Aliasing    x and y must not overlap: a workgroup writes its rows of y while others still read x.  This is the caller's duty; it is
+ *               not checked.
+ *   State       the call needs no env state and no pool: there is no FTL_E_STATE.
+ *   FTL_E_INVALID before any device work, each with a message that names the argument: NULL h, net, net->params, x or y; n_blocks < 1 or
+ *   n < 1; what ftl_mlp_act refuses of the net itself, with its messages (n_layers, a width, `activation`, params not 4-byte aligned,
+ *   set_stride below the param count, n_sets < 1, envs_per_set < 1, env_first < 0, the last row's set beyond n_sets); x_block_bytes below
+ *   n * width[0] * 4 or y_block_bytes below n * width[L] * 4, or either not a multiple of 4; x or y not 4-byte aligned. */
+int ftl_mlp_forward(const ftl_handle* h /* device only, as ftl_gae */, const ftl_mlp* net,
+                    int32_t n_blocks, int32_t n,
+                    const float* x, int64_t x_block_bytes,   /* block b: [n][width[0]] f32 at x + b * x_block_bytes */
+                    float* y, int64_t y_block_bytes,         /* block b: [n][width[L]] f32 at y + b * y_block_bytes */
+                    void* stream);
+
 /* ---- recurrent policy: a trunk of dense ReLU layers, one LSTM cell and a linear head, as a decision, a rollout and a trajectory -------
  * The memoryless stack above (ftl_mlp_act, ftl_rollout_mlp, ftl_mlp_sample, ftl_collect_mlp) with a state per env that the caller owns
  * and the library zeroes at episode boundaries.  ftl_rnn_act (ftl_rnn_kernel, csrc/ftl_rnn.hpp, one launch per decision, asynchronous on
