@@ -302,6 +302,15 @@ class Rnn(C.Structure):
     _fields_ = Mlp._fields_ + [("cell", C.c_int32), ("flags", C.c_uint32), ("state", C.c_void_p), ("state_stride", C.c_int64)]
 
 
+class RnnSequence(C.Structure):
+    """ftl_rnn_sequence: the recorded blocks ``ftl_rnn_forward`` reads (obs, action, reward, kind, reward0) and what it writes (head, h,
+    state_out at block ``state_at``); block b of an array lies ``b * *_block_bytes`` past its base."""
+    _fields_ = [("obs", C.c_void_p), ("obs_block_bytes", C.c_int64), ("action", C.c_void_p), ("action_block_bytes", C.c_int64),
+                ("reward", C.c_void_p), ("reward_block_bytes", C.c_int64), ("kind", C.c_void_p), ("kind_block_bytes", C.c_int64),
+                ("reward0", C.c_void_p), ("head", C.c_void_p), ("head_block_bytes", C.c_int64), ("h", C.c_void_p), ("h_block_bytes", C.c_int64),
+                ("state_out", C.c_void_p), ("state_at", C.c_int32)]
+
+
 class RnnCollectBuffers(C.Structure):
     """ftl_rnn_collect_buffers: ``CollectBuffers`` plus where the state rows every decision read are recorded."""
     _fields_ = [("b", CollectBuffers), ("state", C.c_void_p), ("state_step_bytes", C.c_int64), ("state_steps", C.c_int32), ("_pad", C.c_int32)]

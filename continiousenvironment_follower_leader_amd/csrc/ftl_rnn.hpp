@@ -1,6 +1,7 @@
 // ftl_rnn.hpp -- a recurrent policy, or a population of them, on the device: a trunk of dense ReLU layers, one LSTM cell and a linear
 // head (include/ftl.h, the ftl_rnn_act block, is the contract).  One decision of every env with its state update (ftl_rnn_act), T
-// closed-loop steps (ftl_rollout_rnn) and a recorded trajectory (ftl_collect_rnn).  Included by ftl_abi.hip after ftl_collect.hpp (same
+// closed-loop steps (ftl_rollout_rnn), a recorded trajectory (ftl_collect_rnn), and the net put back over a recorded sequence in one
+// launch (ftl_rnn_forward, ftl_rnn_forward_kernel: further down, with its own comment).  Included by ftl_abi.hip after ftl_collect.hpp (same
 // translation unit: it reads the handle, uses the head maps of ftl_mlp.hpp and the record kernel of ftl_collect.hpp, and hands its
 // kernel to rollout_loop, which owns the steps; there is no second loop here).
 //
@@ -296,6 +297,185 @@ __global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_rnn_kernel(const Args a, 
     row[a.P] = wipe ? 0.0f : 1.0f;
 }
 
+// ---- ftl_rnn_forward: the net on a recorded sequence (include/ftl.h: ftl_rnn_forward) ----
+// ONE launch for all B blocks: the tile map, the LDS plan and the layers (dense, layer_acc, gate_col) of ftl_rnn_kernel, with the block
+// loop inside the kernel and the state in the workgroup.  c lives in the registers of the lane that owns the cell -- the gate map gives a
+// lane the same (4 rows, 2 cells) in every pass of every block, so C = 128 is two passes x two cells x four rows = 16 floats a lane -- and
+// h' goes from its LDS array into the h columns of u after the head layer has read it (behind a barrier; later gate passes of the same
+// block still read the old h, as in ftl_rnn_kernel).  The zero rule is applied there from kind[b].  HBM state traffic is the state before
+// block 0 (read once) and state_out (written once); head[b] and h[b] leave as contiguous runs from LDS.  The trunk does not depend on the
+// state; it runs inside the block loop, so act holds one block's activations as in ftl_rnn_kernel and the LDS plan is unchanged.
+struct Seq {
+    ftlmlp::Args m;            // the trunk and the tile map over the n rows of a block (n_envs = n); m.obs is block 0 of obs
+    int32_t cell, P, R, A;
+    int32_t u_stride, h_stride;
+    int32_t n_blocks, state_at;
+    const float* state; int64_t state_stride;                   // the rows before block 0: read only
+    int64_t obs_bb, action_bb, reward_bb, kind_bb, head_bb, h_bb;               // bytes between two blocks
+    const void* action; const double* reward; const uint8_t* kind; const double* reward0;
+    float* head; float* h; float* state_out;
+};
+
+__global__ __launch_bounds__(FTL_MLP_THREADS, 2) void ftl_rnn_forward_kernel(const Seq a) {
+    extern __shared__ float4 rnn_fwd_lds[];
+    const ftlmlp::Args& m = a.m;
+    float* act = reinterpret_cast<float*>(rnn_fwd_lds);         // [TILE][act_stride]: the trunk between its layers, then y
+    float* u = act + TILE * m.act_stride;                       // [TILE][u_stride]
+    float* hn = u + TILE * a.u_stride;                          // [TILE][h_stride]: h'
+    float* xs = hn + TILE * a.h_stride;                         // [TILE][XS]
+    float* ws = xs + TILE * XS;                                 // the weight stage (+ 64 floats never used)
+    const int t = (int)threadIdx.x;
+    // the tile's set and rows (as in ftl_rnn_kernel)
+    int set = m.env_first / m.envs_per_set, start, end;
+    if ((int)blockIdx.x < m.tiles0) { start = (int)blockIdx.x * TILE; end = m.len0; }
+    else {
+        const int b = (int)blockIdx.x - m.tiles0, q = b / m.tiles_per_set;
+        const int64_t seg = (int64_t)m.len0 + (int64_t)q * m.envs_per_set, seg_end = seg + m.envs_per_set;
+        set += 1 + q;
+        start = (int)seg + (b % m.tiles_per_set) * TILE;
+        end = seg_end < (int64_t)m.n_envs ? (int)seg_end : m.n_envs;
+    }
+    const int tile_n = end - start < TILE ? end - start : TILE;
+    const float* P0 = m.params + (int64_t)set * m.set_stride;
+    const int Lt = m.n_layers, C = a.cell, wx = m.width[Lt], U = wx + a.P + a.R + C, S = 2 * C + a.P + 1;
+    const float* Wg = P0;
+    for (int l = 0; l < Lt; l++) Wg += ((size_t)m.width[l] + 1) * m.width[l + 1];
+    const float* bg = Wg + (size_t)U * 4 * C;
+    const float* Wy = bg + 4 * C;
+    const int tail = a.P + a.R + C;
+    const int lane = t & 63, wave = t >> 6, li = lane & 15, row_d = (wave % GROUPS) * EPW + 4 * (lane >> 4), par = wave / GROUPS;
+    constexpr int PASSES = FTL_RNN_MAX_CELL / FTL_RNN_PASS_CELLS;
+    static_assert(PASSES == 2, "c of a pass is selected between two register sets");
+    // the state before block 0: the rest of u, and c into the registers of the lane that owns the cell
+    for (int idx = t; idx < tile_n * tail; idx += FTL_MLP_THREADS) {
+        const int e = idx / tail, k = idx - e * tail;
+        const size_t row_i = (size_t)start + e;
+        const float* row = a.state + row_i * a.state_stride;
+        float* so = a.state_out && a.state_at == 0 ? a.state_out + row_i * S : nullptr;
+        float v;
+        if (k < a.P) {
+            v = row[2 * C + k];
+            if (so) so[2 * C + k] = v;
+        } else if (k < a.P + a.R) {
+            const float live = row[2 * C + a.P];
+            v = live != 0.0f ? (float)(a.reward0 ? a.reward0[row_i] : 0.0) : 0.0f;
+        } else {
+            const int j = k - a.P - a.R;
+            v = row[j];
+            if (so) so[j] = v;
+        }
+        u[e * a.u_stride + wx + k] = v;
+    }
+    if (a.state_out && a.state_at == 0 && t < tile_n) {
+        const size_t row_i = (size_t)start + t;
+        a.state_out[row_i * S + 2 * C + a.P] = a.state[row_i * a.state_stride + 2 * C + a.P];
+    }
+    float c[PASSES][2][4];
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ps++)
+#pragma unroll
+        for (int gs = 0; gs < 2; gs++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int j = ps * FTL_RNN_PASS_CELLS + gate_group(par, 4 * gs) * NB + li, e = row_d + r;
+                float v = 0.0f;
+                if (j < C && e < tile_n) {
+                    const size_t row_i = (size_t)start + e;
+                    v = a.state[row_i * a.state_stride + C + j];
+                    if (a.state_out && a.state_at == 0) a.state_out[row_i * S + C + j] = v;
+                }
+                c[ps][gs][r] = v;
+            }
+    for (int b = 0; b < a.n_blocks; b++) {
+        const bool more = b + 1 < a.n_blocks;                   // block b + 1 reads the row this one leaves: kind[b], action[b], reward[b]
+        const bool keep = more && a.state_out && a.state_at == b + 1;
+        const float* obs = reinterpret_cast<const float*>(reinterpret_cast<const char*>(m.obs) + (int64_t)b * a.obs_bb);
+        const uint8_t* kind = more ? a.kind + (int64_t)b * a.kind_bb : nullptr;
+        const float* P = P0;
+        for (int l = 0; l < Lt; l++) {
+            const int w_in = m.width[l], w_out = m.width[l + 1];
+            const bool last = l + 1 == Lt;
+            dense(P, P + (size_t)w_in * w_out, w_in, w_out, l == 0 ? obs : nullptr, nullptr, start, tile_n,
+                  act, m.act_stride, last ? u : act, last ? a.u_stride : m.act_stride, true, xs, ws);
+            P += ((size_t)w_in + 1) * w_out;
+        }
+        bool wipe[4];                                           // the zero rule of the lane's four rows
+#pragma unroll
+        for (int r = 0; r < 4; r++) wipe[r] = more && row_d + r < tile_n && kind[(size_t)start + row_d + r] == FTL_TR_VOID;
+        // (layer_acc() begins with a barrier: u is complete before any wave reads it)
+#pragma unroll 1
+        for (int ps = 0; ps < PASSES; ps++) {                   // (one copy of the pass's code: c of the pass is selected, not indexed)
+            const int j0 = ps * FTL_RNN_PASS_CELLS;
+            if (j0 >= C) break;
+            const int cn = C - j0 < FTL_RNN_PASS_CELLS ? C - j0 : FTL_RNN_PASS_CELLS;
+            f32x4 z[BPW];
+            layer_acc<true>(z, Wg, 4 * C, bg, Gates{cn, C, j0}, U, cn <= 2 * NB ? 128 : 256, nullptr, nullptr, start, tile_n, u, a.u_stride, xs, ws);
+#pragma unroll
+            for (int gs = 0; gs < 2; gs++) {                        // the lane's two cells of the pass, four rows each
+                const int jj = gate_group(par, 4 * gs) * NB + li, j = j0 + jj;
+                if (jj >= cn) continue;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int e = row_d + r;
+                    if (e >= tile_n) continue;
+                    const float gi = ftlrnnmath::sig32(z[4 * gs][r]);
+                    const float gf = ftlrnnmath::sig32(z[4 * gs + 1][r]);
+                    const float gg = ftlrnnmath::tanh32(z[4 * gs + 2][r]);
+                    const float go = ftlrnnmath::sig32(z[4 * gs + 3][r]);
+                    const float tt = gi * gg;
+                    const float cn1 = __builtin_fmaf(gf, ps == 0 ? c[0][gs][r] : c[1][gs][r], tt);
+                    const float th = ftlrnnmath::tanh32(cn1);
+                    hn[e * a.h_stride + j] = go * th;               // (an array of its own: later passes still read the old h in u)
+                    const float cw = wipe[r] ? 0.0f : cn1;
+                    if (ps == 0) c[0][gs][r] = cw; else c[1][gs][r] = cw;
+                    if (keep) a.state_out[((size_t)start + e) * S + C + j] = cw;
+                }
+            }
+        }
+        dense(Wy, Wy + (size_t)C * a.A, C, a.A, nullptr, nullptr, start, tile_n, hn, a.h_stride, act, m.act_stride, false, xs, ws);
+        __syncthreads();
+        // the block's outputs, contiguous runs of the tile's rows; then the rest of u for block b + 1 (every gate pass has read the old one)
+        {
+            float* y = reinterpret_cast<float*>(reinterpret_cast<char*>(a.head) + (int64_t)b * a.head_bb) + (size_t)start * a.A;
+            for (int idx = t; idx < tile_n * a.A; idx += FTL_MLP_THREADS) {
+                const int r = idx / a.A;
+                y[idx] = act[r * m.act_stride + (idx - r * a.A)];
+            }
+        }
+        if (a.h) {
+            float* ho = reinterpret_cast<float*>(reinterpret_cast<char*>(a.h) + (int64_t)b * a.h_bb) + (size_t)start * C;
+            for (int idx = t; idx < tile_n * C; idx += FTL_MLP_THREADS) {
+                const int r = idx / C;
+                ho[idx] = hn[r * a.h_stride + (idx - r * C)];
+            }
+        }
+        if (!more) break;
+        for (int idx = t; idx < tile_n * tail; idx += FTL_MLP_THREADS) {
+            const int e = idx / tail, k = idx - e * tail;
+            const size_t row_i = (size_t)start + e;
+            const bool live = kind[row_i] != FTL_TR_VOID;
+            float* so = keep ? a.state_out + row_i * S : nullptr;
+            float v = 0.0f;
+            if (k < a.P) {
+                if (live) {
+                    const char* ab = static_cast<const char*>(a.action) + (int64_t)b * a.action_bb;
+                    if (m.head == FTL_ACTION_DISCRETE) v = reinterpret_cast<const int32_t*>(ab)[row_i] == k ? 1.0f : 0.0f;
+                    else v = (float)reinterpret_cast<const double*>(ab)[row_i * a.P + k];
+                }
+                if (so) so[2 * C + k] = v;
+            } else if (k < a.P + a.R) {
+                if (live) v = (float)reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.reward) + (int64_t)b * a.reward_bb)[row_i];
+            } else {
+                const int j = k - a.P - a.R;
+                if (live) v = hn[e * a.h_stride + j];
+                if (so) so[j] = v;
+            }
+            u[e * a.u_stride + wx + k] = v;
+        }
+        if (keep && t < tile_n) a.state_out[((size_t)start + t) * S + 2 * C + a.P] = kind[(size_t)start + t] != FTL_TR_VOID ? 1.0f : 0.0f;
+    }
+}
+
 }  // namespace ftlrnn
 
 static int32_t rnn_prev_width(int32_t head_width, uint32_t flags) { return (flags & FTL_RNN_PREV_ACTION) ? head_width : 0; }
@@ -310,14 +490,13 @@ static int64_t rnn_param_count(const int32_t* w, int32_t Lt, int32_t C, uint32_t
     return trunk + (U + 1) * 4 * C + ((int64_t)C + 1) * A;
 }
 
-static size_t rnn_lds_bytes(const ftlrnn::Args& a) {
-    return ((size_t)FTL_MLP_ENV_TILE * ((size_t)a.m.act_stride + a.u_stride + a.h_stride + ftlmlp::XS) + FTL_MLP_W_STAGE + 64) * sizeof(float);
+static size_t rnn_lds_bytes(int32_t act_stride, int32_t u_stride, int32_t h_stride) {
+    return ((size_t)FTL_MLP_ENV_TILE * ((size_t)act_stride + u_stride + h_stride + ftlmlp::XS) + FTL_MLP_W_STAGE + 64) * sizeof(float);
 }
 
-// the checks of the net and its state that every entry shares (those of mlp_args, in its order, then the cell and the state); fills the
-// kernel's arguments but for action / state_rec / alive / before, its grid and its LDS bytes
-static int rnn_args(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, ftlrnn::Args& a, unsigned& grid, size_t& lds) {
-    if (!h || !out || !net || !net->params) return fail(FTL_E_INVALID, "null argument");
+// the checks of the net itself, for `n` rows (the handle's envs, or the rows of a block of ftl_rnn_forward: `rows` names them in the last
+// message): those of mlp_net_check, in its order, then the cell
+static int rnn_net_check(const ftl_rnn* net, int64_t n, const char* rows) {
     const int32_t Lt = net->n_layers;
     if (Lt < 1) return fail(FTL_E_INVALID, "rnn: n_layers must be at least 1");
     if (Lt > FTL_MLP_MAX_LAYERS - 1) return fail(FTL_E_UNSUPPORTED, "rnn: more than FTL_MLP_MAX_LAYERS - 1 trunk layers");
@@ -335,17 +514,26 @@ static int rnn_args(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, f
     if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "rnn: params must be 4-byte aligned");
     if (net->set_stride < rnn_param_count(net->width, Lt, C, net->flags)) return fail(FTL_E_INVALID, "rnn: set_stride below ftl_rnn_param_count");
     if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "rnn: n_sets and envs_per_set must be at least 1, env_first at least 0");
-    const int64_t n = h->P.n_envs, eps = net->envs_per_set, first = net->env_first;
-    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, "rnn: the handle's last env lies beyond the last weight set");
-    if (!out->policy_obs || h->P.pol_h <= 0 || h->P.pol_width <= 0) return fail(FTL_E_INVALID, "rnn: the policy reads policy_obs (ftl_outputs.policy_obs, a config with a sensor for it)");
-    if ((int64_t)net->width[0] != (int64_t)h->P.pol_h * h->P.pol_width) return fail(FTL_E_INVALID, "rnn: width[0] must be H * W of policy_obs");
-    const int32_t P = rnn_prev_width(wl, net->flags), R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0, S = 2 * C + P + 1;
+    const int64_t eps = net->envs_per_set, first = net->env_first;
+    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, std::string("rnn: ") + rows + " lies beyond the last weight set");
+    return FTL_OK;
+}
+
+// ... and of its state block
+static int rnn_state_check(const ftl_rnn* net) {
+    const int32_t S = 2 * net->cell + rnn_prev_width(net->width[net->n_layers + 1], net->flags) + 1;
     if (!net->state) return fail(FTL_E_INVALID, "rnn: state is NULL");
     if (((uintptr_t)net->state) & 3) return fail(FTL_E_INVALID, "rnn: state must be 4-byte aligned");
     if (net->state_stride < S) return fail(FTL_E_INVALID, "rnn: state_stride below S = 2 * cell + P + 1");
-    if (!out->reward || !out->done) return fail(FTL_E_INVALID, "rnn: the policy reads out->reward and out->done");
-    ftlmlp::Args& m = a.m;
-    m.obs = out->policy_obs; m.params = net->params; m.set_stride = net->set_stride;
+    return FTL_OK;
+}
+
+// what follows from a checked net and its `n` rows: the trunk's arguments but for obs, the bounds and `action`, the tile map and the grid's
+// tiles, the LDS strides of u and h'
+static void rnn_fill(const ftl_rnn* net, int64_t n, ftlmlp::Args& m, int32_t& u_stride, int32_t& h_stride, unsigned& grid) {
+    const int32_t Lt = net->n_layers, wl = net->width[Lt + 1], C = net->cell;
+    const int64_t eps = net->envs_per_set, first = net->env_first;
+    m.params = net->params; m.set_stride = net->set_stride;
     m.n_envs = (int32_t)n; m.n_layers = Lt; m.env_first = net->env_first; m.envs_per_set = net->envs_per_set;
     int wmax = wl;                                              // act holds the trunk's inner layers and y
     for (int l = 0; l <= FTL_MLP_MAX_LAYERS; l++) {
@@ -358,24 +546,39 @@ static int rnn_args(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, f
     m.len0 = (int32_t)len0; m.tiles0 = (int32_t)((len0 + tile - 1) / tile); m.tiles_per_set = (int32_t)((eps + tile - 1) / tile);
     grid = (unsigned)(m.tiles0 + (rem / eps) * m.tiles_per_set + (rem % eps + tile - 1) / tile);
     m.head = wl == 2 ? FTL_ACTION_BOX2 : wl == 1 ? FTL_ACTION_TURN : FTL_ACTION_DISCRETE;
+    m.action = nullptr;
+    const int U = net->width[Lt] + rnn_prev_width(wl, net->flags) + ((net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0) + C;
+    u_stride = ((U + 31) & ~31) + 2; h_stride = ((C + 31) & ~31) + 2;
+}
+
+// the checks of the net and its state that every entry on a handle's policy_obs shares (those of mlp_args, in its order, then the cell and
+// the state); fills the kernel's arguments but for action / state_rec / alive / before, its grid and its LDS bytes
+static int rnn_args(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, ftlrnn::Args& a, unsigned& grid, size_t& lds) {
+    if (!h || !out || !net || !net->params) return fail(FTL_E_INVALID, "null argument");
+    if (int rc = rnn_net_check(net, h->P.n_envs, "the handle's last env")) return rc;
+    if (!out->policy_obs || h->P.pol_h <= 0 || h->P.pol_width <= 0) return fail(FTL_E_INVALID, "rnn: the policy reads policy_obs (ftl_outputs.policy_obs, a config with a sensor for it)");
+    if ((int64_t)net->width[0] != (int64_t)h->P.pol_h * h->P.pol_width) return fail(FTL_E_INVALID, "rnn: width[0] must be H * W of policy_obs");
+    if (int rc = rnn_state_check(net)) return rc;
+    if (!out->reward || !out->done) return fail(FTL_E_INVALID, "rnn: the policy reads out->reward and out->done");
+    const int32_t Lt = net->n_layers, wl = net->width[Lt + 1], C = net->cell;
+    ftlmlp::Args& m = a.m;
+    rnn_fill(net, h->P.n_envs, m, a.u_stride, a.h_stride, grid);
+    m.obs = out->policy_obs;
     const ftl_robot_params& f = h->P.cfg.follower;
     m.lo0 = f.min_speed; m.hi0 = f.max_speed; m.lo1 = -f.max_rotation_speed; m.hi1 = f.max_rotation_speed;
-    m.action = nullptr;
-    a.cell = C; a.P = P; a.R = R; a.A = wl;
-    const int U = net->width[Lt] + P + R + C;
-    a.u_stride = ((U + 31) & ~31) + 2; a.h_stride = ((C + 31) & ~31) + 2;
+    a.cell = C; a.P = rnn_prev_width(wl, net->flags); a.R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0; a.A = wl;
     a.state = net->state; a.state_stride = net->state_stride; a.state_rec = nullptr;
     a.reward = out->reward; a.out_done = out->done; a.alive = nullptr;
     a.env_int = h->P.env_int; a.rec_stride = h->P.rec_stride; a.before = 0;
-    lds = rnn_lds_bytes(a);
+    lds = rnn_lds_bytes(m.act_stride, a.u_stride, a.h_stride);
     return FTL_OK;
 }
 
 // dynamic LDS above 64 KiB is asked for on the current device before the launch (harmless where the runtime needs no asking; a launch that
 // is refused all the same is reported by launched())
-static int rnn_kernel_ready(size_t lds) {
+static int rnn_kernel_ready(size_t lds, const void* kernel = (const void*)ftlrnn::ftl_rnn_kernel) {
     if (lds > 160 * 1024) return fail(FTL_E_UNSUPPORTED, "rnn: the net needs more than 160 KiB of LDS per workgroup");
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)ftlrnn::ftl_rnn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     return FTL_OK;
 }
 
@@ -383,6 +586,7 @@ extern "C" {
 
 size_t ftl_sizeof_rnn(void) { return sizeof(ftl_rnn); }
 size_t ftl_sizeof_rnn_collect_buffers(void) { return sizeof(ftl_rnn_collect_buffers); }
+size_t ftl_sizeof_rnn_sequence(void) { return sizeof(ftl_rnn_sequence); }
 
 int64_t ftl_rnn_param_count(const int32_t* widths, int32_t n_layers, int32_t cell, uint32_t flags) { return rnn_param_count(widths, n_layers, cell, flags); }
 
@@ -500,6 +704,64 @@ int ftl_collect_rnn(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_
                                   hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMemcpyAsync(obs[T]): ") + hipGetErrorString(e));
     return FTL_OK;
+}
+
+int ftl_rnn_forward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, int32_t n, const ftl_rnn_sequence* seq, void* stream) {
+    if (!h) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: h");
+    if (!net) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: net");
+    if (!net->params) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: net->params");
+    if (!seq) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq");
+    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_rnn_forward: n_blocks and n must be at least 1");
+    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_rnn_forward: n_blocks beyond 65,535");
+    if (int rc = rnn_net_check(net, n, "the last row")) return rc;
+    if (int rc = rnn_state_check(net)) return rc;
+    const int32_t Lt = net->n_layers, A = net->width[Lt + 1], C = net->cell;
+    const int32_t P = rnn_prev_width(A, net->flags), R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0;
+    const bool more = n_blocks > 1;
+    if (!seq->obs) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->obs");
+    if (!seq->head) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->head");
+    if (more && !seq->kind) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->kind (read for every block but the last)");
+    if (more && P && !seq->action) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->action (the net has FTL_RNN_PREV_ACTION)");
+    if (more && R && !seq->reward) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->reward (the net has FTL_RNN_PREV_REWARD)");
+    const int64_t arow = A == 2 ? 16 : A == 1 ? 8 : 4, ael = A == 5 ? 4 : 8;
+    if (seq->obs_block_bytes < (int64_t)n * net->width[0] * 4 || (seq->obs_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: obs_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
+    if (more && P && seq->action && (seq->action_block_bytes < (int64_t)n * arow || (seq->action_block_bytes & (ael - 1))))
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: action_block_bytes must be a multiple of the action element of at least one block of encoded actions");
+    if (more && R && (seq->reward_block_bytes < (int64_t)n * 8 || (seq->reward_block_bytes & 7)))
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: reward_block_bytes must be a multiple of 8 of at least one block, n * 8");
+    if (more && seq->kind_block_bytes < (int64_t)n)
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: kind_block_bytes below one block, n");
+    if (seq->head_block_bytes < (int64_t)n * A * 4 || (seq->head_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: head_block_bytes must be a multiple of 4 of at least one block, n * A * 4");
+    if (seq->h && (seq->h_block_bytes < (int64_t)n * C * 4 || (seq->h_block_bytes & 3)))
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: h_block_bytes must be a multiple of 4 of at least one block, n * cell * 4");
+    if (seq->state_out && (seq->state_at < 0 || seq->state_at >= n_blocks))
+        return fail(FTL_E_INVALID, "ftl_rnn_forward: state_at must name a block, 0 <= state_at < n_blocks");
+    ftlrnn::Seq a; unsigned grid;
+    rnn_fill(net, n, a.m, a.u_stride, a.h_stride, grid);
+    if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull)       // (a grid dimension counts threads in 32 bits: 2^24 tiles, over 5e8 rows a block)
+        return fail(FTL_E_UNSUPPORTED, "ftl_rnn_forward: n beyond the 2^24 - 1 tiles of one launch; split the rows");
+    if (((uintptr_t)seq->obs) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: obs must be 4-byte aligned");
+    if (more && P && (((uintptr_t)seq->action) & (uintptr_t)(ael - 1))) return fail(FTL_E_INVALID, "ftl_rnn_forward: action not aligned to its element");
+    if (more && R && (((uintptr_t)seq->reward) & 7)) return fail(FTL_E_INVALID, "ftl_rnn_forward: reward must be 8-byte aligned");
+    if (((uintptr_t)seq->reward0) & 7) return fail(FTL_E_INVALID, "ftl_rnn_forward: reward0 must be 8-byte aligned");
+    if (((uintptr_t)seq->h) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: h must be 4-byte aligned");
+    if (((uintptr_t)seq->state_out) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: state_out must be 4-byte aligned");
+    if (((uintptr_t)seq->head) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: head must be 4-byte aligned");
+    const size_t lds = rnn_lds_bytes(a.m.act_stride, a.u_stride, a.h_stride);
+    if (int rc = set_device(h)) return rc;
+    if (int rc = rnn_kernel_ready(lds, (const void*)ftlrnn::ftl_rnn_forward_kernel)) return rc;
+    a.m.obs = seq->obs; a.m.lo0 = a.m.hi0 = a.m.lo1 = a.m.hi1 = 0.0;
+    a.cell = C; a.P = P; a.R = R; a.A = A;
+    a.n_blocks = n_blocks; a.state_at = seq->state_out ? seq->state_at : -1;
+    a.state = net->state; a.state_stride = net->state_stride;
+    a.obs_bb = seq->obs_block_bytes; a.action_bb = seq->action_block_bytes; a.reward_bb = seq->reward_block_bytes;
+    a.kind_bb = seq->kind_block_bytes; a.head_bb = seq->head_block_bytes; a.h_bb = seq->h_block_bytes;
+    a.action = P ? seq->action : nullptr; a.reward = R ? seq->reward : nullptr; a.kind = seq->kind; a.reward0 = R ? seq->reward0 : nullptr;
+    a.head = seq->head; a.h = seq->h; a.state_out = seq->state_out;
+    hipLaunchKernelGGL(ftlrnn::ftl_rnn_forward_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+    return launched();
 }
 
 }  // extern "C"

@@ -6,18 +6,60 @@ operation by operation, ``sigmoid`` and ``tanh`` included (the ``ftl_rnn_act`` b
 
 The state is a ``[N, S]`` float32 tensor, a row ``h | c | a_prev | live``; the device zeroes a row at the episode boundary, so that no
 memory of a finished episode leaks into the next one: after the void decision at a finished env (``auto_reset`` False or "next_step"), or
-before the first decision on the new episode's observation ("same_step", "queue", "sample")."""
+before the first decision on the new episode's observation ("same_step", "queue", "sample").
+
+A recorded sequence goes back through a recurrent net in one launch (``ftl_rnn_forward``): ``forward`` evaluates any net on recorded blocks
+with the state carried from block to block and zeroed after VOID rows as ``collect_rnn`` did, ``RecurrentPolicy.forward(traj)`` is the
+actor's replay -- ``traj.head`` bit for bit --, and ``RecurrentCritic`` is a head-1 net with memory whose ``values(traj)`` feed ``gae()``."""
 import ctypes as C
 
 import torch
 
 from . import _lib, abi
-from .mlp import MlpPolicy, Trajectory, check_widths, head_encoding
+from .mlp import FORWARD_MAX_BLOCKS, MlpPolicy, Trajectory, _device_handle, check_net_widths, check_widths, head_encoding
 
 _BEFORE = ("same_step", "queue", "sample")
 
 
-class RecurrentPolicy(MlpPolicy):
+class _RnnParams:
+    """Views into ``params`` of a recurrent net (``widths``, ``trunk``, ``cell``, ``U``, ``n_sets``), shared by the policy and the critic."""
+
+    def layer(self, l):
+        """Views ``(W [n_sets, in, out], b [n_sets, out])`` of trunk layer ``l`` (0-based) in ``params``."""
+        w = self.trunk
+        if not 0 <= l < len(w) - 1:
+            raise IndexError("trunk layer %d of %d" % (l, len(w) - 1))
+        off = abi.mlp_param_count(w[:l + 1])
+        nw = w[l] * w[l + 1]
+        return self.params[:, off:off + nw].view(self.n_sets, w[l], w[l + 1]), self.params[:, off + nw:off + nw + w[l + 1]]
+
+    def cell_weights(self):
+        """Views ``(W_g [n_sets, U, 4C], b_g [n_sets, 4C])``: rows in the order ``x | a_prev | r_prev | h``, columns ``i | f | g | o``."""
+        off, n = abi.mlp_param_count(self.trunk), self.U * 4 * self.cell
+        return self.params[:, off:off + n].view(self.n_sets, self.U, 4 * self.cell), self.params[:, off + n:off + n + 4 * self.cell]
+
+    def head_weights(self):
+        """Views ``(W_y [n_sets, C, A], b_y [n_sets, A])``."""
+        A = self.widths[-1]
+        off = abi.mlp_param_count(self.trunk) + (self.U + 1) * 4 * self.cell
+        n = self.cell * A
+        return self.params[:, off:off + n].view(self.n_sets, self.cell, A), self.params[:, off + n:off + n + A]
+
+    def load_lstm_cell(self, s, lstm):
+        """Copy a ``torch.nn.LSTMCell(U - C, C)`` into set ``s``: ``weight_ih.T`` over ``weight_hh.T``, ``bias_ih + bias_hh``."""
+        if lstm.input_size != self.U - self.cell or lstm.hidden_size != self.cell:
+            raise ValueError("the cell takes %d inputs and has %d units, not %d and %d" % (self.U - self.cell, self.cell, lstm.input_size, lstm.hidden_size))
+        W, b = self.cell_weights()
+        with torch.no_grad():
+            W[s, :self.U - self.cell].copy_(lstm.weight_ih.detach().t())
+            W[s, self.U - self.cell:].copy_(lstm.weight_hh.detach().t())
+            if lstm.bias:
+                b[s].copy_((lstm.bias_ih.detach().to(torch.float32) + lstm.bias_hh.detach().to(torch.float32)))
+            else:
+                b[s].zero_()
+
+
+class RecurrentPolicy(_RnnParams, MlpPolicy):
     """``n_sets`` recurrent nets on ``batch`` (a ``VecGame`` or a ``PipelinedVecGame`` built with ``policy_obs=True``): ``widths`` names
     the input width, the trunk's layers and the head width -- ``(180, 64, 64, 2)`` is 180 -> 64 -> 64 -> cell -> 2 --, ``cell`` the LSTM
     units; ``prev_action`` / ``prev_reward`` feed the last action (one-hot on Discrete(5)) and the last reward to the cell.  Env e uses
@@ -83,41 +125,6 @@ class RecurrentPolicy(MlpPolicy):
         net.cell, net.flags = self.cell, self.flags
         net.state, net.state_stride = self.state.data_ptr() + env_first * self.S * 4, self.S
         return net
-
-    # ------------------------------------------------------------------ views of the parameters
-    def layer(self, l):
-        """Views ``(W [n_sets, in, out], b [n_sets, out])`` of trunk layer ``l`` (0-based) in ``params``."""
-        w = self.trunk
-        if not 0 <= l < len(w) - 1:
-            raise IndexError("trunk layer %d of %d" % (l, len(w) - 1))
-        off = abi.mlp_param_count(w[:l + 1])
-        nw = w[l] * w[l + 1]
-        return self.params[:, off:off + nw].view(self.n_sets, w[l], w[l + 1]), self.params[:, off + nw:off + nw + w[l + 1]]
-
-    def cell_weights(self):
-        """Views ``(W_g [n_sets, U, 4C], b_g [n_sets, 4C])``: rows in the order ``x | a_prev | r_prev | h``, columns ``i | f | g | o``."""
-        off, n = abi.mlp_param_count(self.trunk), self.U * 4 * self.cell
-        return self.params[:, off:off + n].view(self.n_sets, self.U, 4 * self.cell), self.params[:, off + n:off + n + 4 * self.cell]
-
-    def head_weights(self):
-        """Views ``(W_y [n_sets, C, A], b_y [n_sets, A])``."""
-        A = self.widths[-1]
-        off = abi.mlp_param_count(self.trunk) + (self.U + 1) * 4 * self.cell
-        n = self.cell * A
-        return self.params[:, off:off + n].view(self.n_sets, self.cell, A), self.params[:, off + n:off + n + A]
-
-    def load_lstm_cell(self, s, lstm):
-        """Copy a ``torch.nn.LSTMCell(U - C, C)`` into set ``s``: ``weight_ih.T`` over ``weight_hh.T``, ``bias_ih + bias_hh``."""
-        if lstm.input_size != self.U - self.cell or lstm.hidden_size != self.cell:
-            raise ValueError("the cell takes %d inputs and has %d units, not %d and %d" % (self.U - self.cell, self.cell, lstm.input_size, lstm.hidden_size))
-        W, b = self.cell_weights()
-        with torch.no_grad():
-            W[s, :self.U - self.cell].copy_(lstm.weight_ih.detach().t())
-            W[s, self.U - self.cell:].copy_(lstm.weight_hh.detach().t())
-            if lstm.bias:
-                b[s].copy_((lstm.bias_ih.detach().to(torch.float32) + lstm.bias_hh.detach().to(torch.float32)))
-            else:
-                b[s].zero_()
 
     def reset_state(self, env_ids=None):
         """Zero the state of every env, or of ``env_ids``: the rows of a fresh episode (after a ``batch.reset`` of those envs)."""
@@ -205,3 +212,189 @@ class RecurrentPolicy(MlpPolicy):
             _lib.check(self.lib.ftl_collect_rnn(g.h, T, g._out_ref, C.byref(net), C.byref(rb), flags, s), self.lib)
         self._keep = out
         return out
+
+    def forward(self, traj, reward0=None, **outs):
+        """The policy's own net -- its sets and its flags -- replayed on a trajectory its ``collect`` recorded, in one launch (the
+        module's ``forward`` on ``traj.obs[:-1]`` from ``traj.state[0]``, with ``traj.action`` / ``reward`` / ``kind``): float32
+        ``[T, N, A]``, which is ``traj.head`` bit for bit when ``reward0`` is ``batch.reward`` as it stood before the ``collect`` call (float64
+        ``[N]``; None reads as zeros, right for envs that had not stepped yet).  ``outs`` are ``out``, ``h_out``, ``state_out`` and
+        ``state_at`` of ``forward``: ``state_out`` at ``state_at=t`` is ``traj.state[t]`` of a ``record_state=True`` trajectory.  The launch
+        goes to the current stream, not to the parts' streams: on a pipelined batch ``join()`` first."""
+        if not isinstance(traj, Trajectory) or not torch.is_tensor(getattr(traj, "state", None)):
+            raise ValueError("traj must be a Trajectory of collect_rnn (with its state blocks)")
+        if not torch.is_tensor(traj.obs) or traj.obs.dim() != 3 or traj.obs.shape[0] < 2 or traj.obs.shape[1] != self.n:
+            raise ValueError("traj.obs must be a [T + 1, N, H * W] tensor with the batch's N = %d rows a block" % self.n)
+        return forward(self.widths, self.cell, self.params, traj.obs[:-1], traj.action, traj.reward, traj.kind, traj.state[0], reward0,
+                       bool(self.flags & abi.FTL_RNN_PREV_ACTION), bool(self.flags & abi.FTL_RNN_PREV_REWARD), **outs)
+
+
+def check_rnn_widths(widths, cell):
+    """``(widths, cell)`` as ints inside the limits of ``ftl_rnn`` alone (no config): ``ValueError`` for a malformed net,
+    ``NotImplementedError`` beyond the limits."""
+    widths = tuple(int(w) for w in widths)
+    if len(widths) < 3:
+        raise ValueError("widths must name the input width, at least one trunk layer and the head width")
+    widths = check_net_widths(widths)
+    if widths[-1] not in (1, 2, 5):
+        raise ValueError("the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5)), not %d" % widths[-1])
+    cell = int(cell)
+    if cell < 1:
+        raise ValueError("cell must be at least 1")
+    if cell > abi.FTL_RNN_MAX_CELL:
+        raise NotImplementedError("at most %d LSTM units" % abi.FTL_RNN_MAX_CELL)
+    return widths, cell
+
+
+def _is(t, dtype, shape, device):
+    return torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device == device and t.is_contiguous()
+
+
+def forward(widths, cell, params, obs, action=None, reward=None, kind=None, state=None, reward0=None, prev_action=True, prev_reward=True,
+            out=None, h_out=None, state_out=None, state_at=0):
+    """The raw heads of ``n_sets`` recurrent nets (``widths`` = input width, trunk layers, head width; ``cell`` LSTM units) on a recorded
+    sequence, in ONE launch (``ftl_rnn_forward``): block b is evaluated operation for operation as ``ftl_rnn_act`` evaluates a decision,
+    the state is carried from block to block inside the kernel, and the row block b + 1 reads is all zeros where ``kind[b]`` is
+    ``FTL_TR_VOID`` -- what ``collect_rnn`` did when it recorded the sequence.
+
+    ``params`` float32 ``[n_sets, param_count]`` (``RecurrentPolicy.params``); ``obs`` float32 ``[B, N, widths[0]]``; ``n_sets`` must
+    divide N and row r uses set ``r // (N // n_sets)``.  ``action`` (float64 ``[>= B-1, N, 2]`` for head 2, float64 ``[>= B-1, N]`` for head
+    1, int32 ``[>= B-1, N]`` for head 5), ``reward`` float64 ``[>= B-1, N]`` and ``kind`` uint8 ``[>= B-1, N]`` are the records between
+    the blocks: a ``Trajectory``'s T-block tensors are accepted as they are for B = T (``obs[:-1]``) or B = T + 1 (``obs``).  ``action``
+    is needed only with ``prev_action``, ``reward`` only with ``prev_reward``, and none of the three for B = 1.  ``state`` float32
+    ``[N, S]`` is the state before block 0 (None: zeros, every row at the start of an episode; it is never written), ``reward0`` float64
+    ``[N]`` the reward the first decision saw (None: zeros).
+
+    Returns float32 ``[B, N, A]`` (``out=`` reuses such a buffer).  ``h_out`` float32 ``[B, N, cell]`` receives the cell's output of every
+    block, ``state_out`` float32 ``[N, S]`` the rows block ``state_at`` read (``0 <= state_at < B``): the ``state`` of a call that continues
+    there.  Outputs must not overlap inputs.  The launch goes to the current stream of ``obs``'s device.  ``ValueError`` for every shape,
+    dtype, device or contiguity mismatch, ``NotImplementedError`` beyond the limits of ``ftl_rnn`` or beyond 65,535 blocks, both before any
+    library call.  There is no backward pass."""
+    widths, cell = check_rnn_widths(widths, cell)
+    A, W0 = widths[-1], widths[0]
+    flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+    P, R, U, S = abi.rnn_widths(widths, cell, flags)
+    count = abi.rnn_param_count(widths, cell, flags)
+    if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == count
+            and params.shape[0] >= 1 and params.is_contiguous()):
+        raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor" % count)
+    n_sets = int(params.shape[0])
+    if not (torch.is_tensor(obs) and obs.dtype == torch.float32 and obs.dim() == 3 and obs.shape[2] == W0 and obs.is_contiguous()):
+        raise ValueError("obs must be a contiguous float32 [B, N, %d] tensor" % W0)
+    if obs.requires_grad or params.requires_grad:
+        raise ValueError("forward() has no backward pass: pass detached tensors")
+    B, N, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+    if B < 1 or N < 1:
+        raise ValueError("obs must hold at least one block of at least one row, not %s" % (list(obs.shape),))
+    if N % n_sets:
+        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
+    if B > FORWARD_MAX_BLOCKS:
+        raise NotImplementedError("at most %d blocks in one call, not %d" % (FORWARD_MAX_BLOCKS, B))
+    adt, atail = (torch.int32, (N,)) if A == 5 else (torch.float64, (N, 2) if A == 2 else (N,))
+    need = (("action", action, adt, atail, bool(P)), ("reward", reward, torch.float64, (N,), bool(R)), ("kind", kind, torch.uint8, (N,), True))
+    for name, t, dtype, tail, used in need:
+        if t is None and (B == 1 or not used):
+            continue
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 1 + len(tail) and tuple(t.shape[1:]) == tail and t.shape[0] >= B - 1
+                and t.device == dev and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous %s tensor of at least B - 1 = %d blocks %s on obs's device" % (name, dtype, B - 1, list(tail)))
+    if state is not None and not _is(state, torch.float32, (N, S), dev):
+        raise ValueError("state must be a contiguous float32 [N, S] = [%d, %d] tensor on obs's device" % (N, S))
+    if reward0 is not None and not _is(reward0, torch.float64, (N,), dev):
+        raise ValueError("reward0 must be a contiguous float64 [N] = [%d] tensor on obs's device" % N)
+    if out is not None and not _is(out, torch.float32, (B, N, A), dev):
+        raise ValueError("out must be a contiguous float32 %s tensor on obs's device" % ([B, N, A],))
+    if h_out is not None and not _is(h_out, torch.float32, (B, N, cell), dev):
+        raise ValueError("h_out must be a contiguous float32 %s tensor on obs's device" % ([B, N, cell],))
+    if state_out is not None:
+        if not _is(state_out, torch.float32, (N, S), dev):
+            raise ValueError("state_out must be a contiguous float32 [N, S] = [%d, %d] tensor on obs's device" % (N, S))
+        if not 0 <= int(state_at) < B:
+            raise ValueError("state_at must name a block, 0 <= state_at < %d, not %r" % (B, state_at))
+    if not obs.is_cuda or params.device != dev:
+        raise ValueError("obs and params must lie on the same GPU device")
+    if out is None:
+        out = torch.empty(B, N, A, dtype=torch.float32, device=dev)
+    if state is None:
+        state = torch.zeros(N, S, dtype=torch.float32, device=dev)
+    net = abi.Rnn()
+    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), count, n_sets, len(widths) - 2
+    for l, w in enumerate(widths):
+        net.width[l] = w
+    net.env_first, net.envs_per_set, net.cell, net.flags = 0, N // n_sets, cell, flags
+    net.state, net.state_stride = state.data_ptr(), S
+    seq = abi.RnnSequence()
+    seq.obs, seq.obs_block_bytes = obs.data_ptr(), N * W0 * 4
+    if B > 1:
+        if P:
+            seq.action, seq.action_block_bytes = action.data_ptr(), N * (16 if A == 2 else 8 if A == 1 else 4)
+        if R:
+            seq.reward, seq.reward_block_bytes = reward.data_ptr(), N * 8
+        seq.kind, seq.kind_block_bytes = kind.data_ptr(), N
+    seq.reward0 = reward0.data_ptr() if reward0 is not None else None
+    seq.head, seq.head_block_bytes = out.data_ptr(), N * A * 4
+    if h_out is not None:
+        seq.h, seq.h_block_bytes = h_out.data_ptr(), N * cell * 4
+    if state_out is not None:
+        seq.state_out, seq.state_at = state_out.data_ptr(), int(state_at)
+    lib = _lib.load()
+    h = _device_handle(dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(lib.ftl_rnn_forward(h, C.byref(net), B, N, C.byref(seq), stream), lib)
+    return out
+
+
+class RecurrentCritic(_RnnParams):
+    """A value net with memory for ``gae()``, or a population of ``n_sets`` of them: an ``ftl_rnn`` of head width 1 -- trunk, LSTM cell,
+    linear value head, the value branch on the cell's output as in the reference's ``*_lstm`` models -- evaluated on a trajectory by
+    ``forward`` in one launch.  ``RecurrentCritic(widths, cell, n_sets=1, prev_reward=True, params=None, device=None)``: ``widths[-1]``
+    must be 1; ``params`` is the float32 ``[n_sets, param_count]`` tensor of all weights (zeros on ``device``, the current GPU by
+    default, unless given), with the views ``layer(l)``, ``cell_weights()``, ``head_weights()`` and ``load_lstm_cell`` of the policy.
+
+    The parameter layout of ``ftl_rnn`` ties the width of ``a_prev`` to the head width, here 1.  The critic can therefore be fed the last
+    action (``prev_action=True``) only where an action is one float64 -- the turn of a ``constant_follower_speed`` config --; ``values``
+    refuses any other action record with ``ValueError``.  The default feeds the last reward only."""
+
+    def __init__(self, widths, cell, n_sets=1, prev_reward=True, params=None, device=None, prev_action=False):
+        self.widths, self.cell = check_rnn_widths(widths, cell)
+        if self.widths[-1] != 1:
+            raise ValueError("a critic's head is 1 wide, not %d" % self.widths[-1])
+        self.trunk = self.widths[:-1]
+        self.prev_action, self.prev_reward = bool(prev_action), bool(prev_reward)
+        self.flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+        self.P, self.R, self.U, self.S = abi.rnn_widths(self.widths, self.cell, self.flags)
+        self.n_sets, self.param_count = int(n_sets), abi.rnn_param_count(self.widths, self.cell, self.flags)
+        if self.n_sets < 1:
+            raise ValueError("n_sets must be at least 1")
+        if params is None:
+            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
+        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
+                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
+            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the critic's device" % self.param_count)
+        self.params, self.device = params, params.device
+
+    def values(self, traj, state=None, reward0=None, out=None):
+        """``(values, carry)``: float32 ``[T + 1, N]``, the value of every ``traj.obs[t]`` with the memory of the blocks before it -- what
+        ``gae(traj, values, ...)`` takes --, and float32 ``[N, S]``, the rows block T read: the ``state`` for the next trajectory's
+        ``values`` (with ``reward0 = traj.reward[-1]``), so that the critic's memory runs on through consecutive ``collect`` calls.
+        ``state`` None: zeros, every env at the start of an episode; ``reward0`` float64 ``[N]``: the reward the first decision saw
+        (``batch.reward`` before the ``collect`` call).  ``out=(values, carry)`` reuses a pair.  With ``prev_action`` the trajectory's
+        actions must be the float64 ``[T, N]`` of a ``constant_follower_speed`` config (``ValueError`` otherwise)."""
+        if not isinstance(traj, Trajectory) or not torch.is_tensor(traj.obs) or traj.obs.dim() != 3:
+            raise ValueError("traj must be a Trajectory with obs [T + 1, N, %d]" % self.widths[0])
+        T1, N = int(traj.obs.shape[0]), int(traj.obs.shape[1])
+        if self.prev_action and not (torch.is_tensor(traj.action) and traj.action.dtype == torch.float64 and traj.action.dim() == 2):
+            raise ValueError("prev_action needs actions of one float64 each (a constant_follower_speed config): the critic's a_prev is as "
+                             "wide as its head, 1")
+        values = carry = None
+        if out is not None:
+            values, carry = out
+            if not (torch.is_tensor(values) and values.dtype == torch.float32 and tuple(values.shape) == (T1, N) and values.is_contiguous()):
+                raise ValueError("out's values must be a contiguous float32 [T + 1, N] tensor")
+            values = values.unsqueeze(-1)
+        if carry is None:
+            if not traj.obs.is_cuda:
+                raise ValueError("traj must lie on a GPU device")
+            carry = torch.empty(N, self.S, dtype=torch.float32, device=traj.obs.device)
+        v = forward(self.widths, self.cell, self.params, traj.obs, traj.action if self.prev_action else None, traj.reward, traj.kind, state,
+                    reward0, self.prev_action, self.prev_reward, out=values, state_out=carry, state_at=T1 - 1)
+        return v[..., 0], carry

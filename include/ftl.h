@@ -1100,6 +1100,55 @@ int ftl_rollout_rnn(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* o
 int ftl_collect_rnn(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_rnn* net, const ftl_rnn_collect_buffers* b,
                     uint32_t flags /* 0 or FTL_STEP_NEXT_RESET */, void* stream);
 
+/* ---- the recurrent net on a recorded sequence: an ftl_rnn evaluated on the caller's blocks, raw heads out (the actor's replay, a critic
+ * with memory) ------------------------------------------------------------------------------------------------------------------------
+ * ftl_rnn_forward (ftl_rnn_forward_kernel, csrc/ftl_rnn.hpp: ONE launch for the whole sequence, the block loop inside the kernel,
+ * asynchronous on `stream`; the handle only names the device, as for ftl_gae and ftl_mlp_forward) is ftl_mlp_forward's counterpart for
+ * ftl_rnn: it puts n_blocks = B recorded blocks of n rows back through `net`, carrying the state from block to block as ftl_collect_rnn
+ * did when it recorded them.  Block b of an array lies at (char*)base + b * its *_block_bytes.
+ *   Net, sets   the limits, the parameter layout and the set rule are those of ftl_rnn_act: row r of every block uses set
+ *               (env_first + r) / envs_per_set with n in place of the handle's env count; (env_first + n - 1) / envs_per_set < n_sets.
+ *               policy_obs and the handle's H * W play no part.  A part of a wider [B][N] record passes its rows [lo, lo + n) as base +
+ *               lo * row bytes, env_first = lo and the *_block_bytes of N rows.
+ *   State       net->state (rows of state_stride floats, row 0 = row 0 of this call) is the row h | c | a_prev | live every row of the
+ *               sequence has BEFORE block 0.  It is read and never written.
+ *   Block b     is evaluated operation for operation as ftl_rnn_act in mode AFTER evaluates a decision (tests/rnn_numpy.py: decide):
+ *               u = [trunk(obs[b]) | a_prev | r_prev | h], the gate chain, the cell lines, the linear head.
+ *                 b = 0: a_prev, live and h, c come from the state row; r_prev = live != 0 ? (float)reward0[r] : 0.0f (reward0 == NULL
+ *                        reads as 0.0: it is out->reward as it stood before block 0 was decided).
+ *                 b > 0: the row block b reads is the one block b - 1 left: h', c', a_prev = (float) of action[b - 1] (Discrete(5): the
+ *                        one-hot of the index, zeros for an index outside 0 .. 4), live = 1 and r_prev = live != 0 ?
+ *                        (float)reward[b - 1] : 0.0f -- except under the zero rule.
+ *               Zero rule: the row block b + 1 reads is all zeros (h, c, a_prev and live, so r_prev too) where kind[b] == FTL_TR_VOID,
+ *               and nowhere else: exactly what ftl_collect_rnn does at a decision whose env was done on entry.
+ *   Outputs     head[b] = the head layer's acc, float32 [n][A] dense: no map, no noise.  On the record of ftl_collect_rnn, with the net
+ *               that played, the state block 0 of the record and reward0 = out->reward before the call, head equals the recorded head bit
+ *               for bit, VOID rows included.  h[b] (optional) = h' of block b, float32 [n][C] dense, before any wipe, as the head reads
+ *               it.  state_out (optional) = the rows block state_at READ, [n][S] dense, 0 <= state_at < n_blocks: with state_at = t it
+ *               equals block t of ftl_rnn_collect_buffers.state, and it is the net->state of a call that continues at block state_at
+ *               (with reward0 = reward[state_at - 1]).  Nothing else is written.
+ *   Pointers    action may be NULL without FTL_RNN_PREV_ACTION, reward without FTL_RNN_PREV_REWARD; with n_blocks == 1 action, reward
+ *               and kind may all be NULL (they are read for b < n_blocks - 1 only).  Inputs and outputs must not overlap: that is the
+ *               caller's duty; it is not checked.
+ *   No FTL_E_STATE: the call needs no env state and no pool.
+ *   FTL_E_INVALID before any device work, each with a message that names the argument: NULL h, net, net->params, seq, obs, head, or a
+ *   record array the net reads; n_blocks < 1 or n < 1; what ftl_rnn_act refuses of the net and its state, with its messages; a
+ *   *_block_bytes below one block of n rows or no multiple of the element size; a pointer not aligned to its element; state_at outside
+ *   [0, n_blocks) when state_out is given.  FTL_E_UNSUPPORTED: an activation other than ReLU, a cell or a width beyond the limits, more
+ *   than 65,535 blocks, more than 2^24 - 1 tiles. */
+typedef struct ftl_rnn_sequence {
+    const float*   obs;      int64_t obs_block_bytes;     /* [B][n][width[0]] */
+    const void*    action;   int64_t action_block_bytes;  /* [B-1][n] in the head's encoding: f64 x2 (head 2), f64 (head 1), int32 (head 5) */
+    const double*  reward;   int64_t reward_block_bytes;  /* [B-1][n] */
+    const uint8_t* kind;     int64_t kind_block_bytes;    /* [B-1][n] of FTL_TR_* */
+    const double*  reward0;                               /* [n]: out->reward before block 0, NULL = 0 */
+    float*         head;     int64_t head_block_bytes;    /* out [B][n][A] */
+    float*         h;        int64_t h_block_bytes;       /* out [B][n][C], optional */
+    float*         state_out; int32_t state_at;           /* out [n][S], optional: the rows block state_at read, 0 <= state_at < B */
+} ftl_rnn_sequence;
+size_t ftl_sizeof_rnn_sequence(void);
+int ftl_rnn_forward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, int32_t n, const ftl_rnn_sequence* seq, void* stream);
+
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
  * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
