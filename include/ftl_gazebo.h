@@ -50,7 +50,24 @@ int ftl_gz_reset(ftl_gz_handle* h, const uint8_t* mask, void* stream);
 /* One tracker.scan (GZ:17-172) followed by every laser's scan (GZ:203-297), as arctic_env.py:190-211 calls them.
  *   leader_pos [n][2] f64  leader position in the follower's frame;  yaw [n] f64  follower_orientation[2], radians;
  *   delta [n][2] f64  (delta_x, delta_y);  pts1, pts2 [n][max_pts][2] f64 + n_pts [n]  cur_object_points_1 / _2;
- *   lasers [n][ftl_gz_lasers_len] f32 out: per sensor a [history][width] block, oldest row first. */
+ *   lasers [n][ftl_gz_lasers_len] f32 out: per sensor a [history][width] block, oldest row first.
+ * n_pts[e] is clamped to [0, max_pts]: a negative count reads no point, a count above the capacity reads the first max_pts (the
+ * reference takes len() of the lists it is handed, so it has no such case).  With max_pts == 0, pts1 / pts2 may be NULL.
+ * Fewer than two points make no obstacle segment (GZ:193 loops over len - 1): a sensor that reacts to obstacles only then stores
+ * an empty snapshot, whose rays read laser_length (GZ:226 is False for an empty array under the numpy 1.x the reference ran on).
+ *
+ * The error word ("gz_int"[3]; sticky until ftl_gz_reset of that env) uses the FTL_ERR_* bits of ftl.h.  For this kernel:
+ *   FTL_ERR_CORR_OVERFLOW   a history point or a corridor pair beyond FTL_GZ_HIST_CAP was due and is NOT stored; everything stored
+ *                           stays as it is and the sensors go on reading it.  The reference's deques are unbounded: a leader that
+ *                           stays beyond 25 m is never appended to the history (GZ:130), nothing is trimmed, and every saving call
+ *                           still appends one more pair (GZ:160-166) -- from 10 pairs after the seeding call, the 65th is due at
+ *                           call 165 (counting from 0) and the results part from the reference's there.
+ *   FTL_ERR_EMPTY_CORRIDOR  a sensor was scanned with len(corridor) <= 1 (GZ:216/297: `all_obs_arr` unbound, UnboundLocalError in
+ *                           the reference), e.g. a leader so far away at the seeding call that the ten seed points are trimmed
+ *                           to one.  Every reading of that sensor is laser_length and its snapshot ring does not advance.
+ *   FTL_ERR_TRACKER_SEED    an empty history with a non-zero counter (reference: IndexError on hist[-1]).  Unreachable through
+ *                           this interface: the trim loop stops at one point (path length 0), and only a reset, which zeroes the
+ *                           counter as well, empties the history. */
 int ftl_gz_step(ftl_gz_handle* h, const double* leader_pos, const double* yaw, const double* delta, const double* pts1,
                 const double* pts2, const int32_t* n_pts, float* lasers, void* stream);
 /* parity introspection: byte offset of the per-env records inside the state buffer.
