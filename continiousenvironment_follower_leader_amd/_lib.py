@@ -17,6 +17,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_scenario_dev.hpp"),
            os.path.join(_PKG, "csrc", "ftl_scenario_core.hpp"),
            os.path.join(_PKG, "csrc", "ftl_crmath.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_trktrim.hpp"),
            os.path.join(_PKG, "csrc", "ftl_render.hpp"),
            os.path.join(_PKG, "csrc", "ftl_snapshot.hpp"),
            os.path.join(_PKG, "csrc", "ftl_restart.hpp"),

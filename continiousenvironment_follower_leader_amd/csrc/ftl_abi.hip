@@ -46,15 +46,18 @@ struct Switches {
     int regroup_every, corr_lds_cap, lds_pad, lds_pad_rays;            // FTL_REGROUP_EVERY, FTL_DEBUG_CORR_LDS_CAP, FTL_DEBUG_LDS_PAD[_RAYS] (0: not given)
     int pair_window;                                                  // FTL_DEBUG_PAIR_WINDOW (0: not given)
     bool print_lds;                                                   // FTL_DEBUG_PRINT_LDS
+    int trk_running; double trk_band;                                 // FTL_TRK_RUNNING, FTL_DEBUG_TRK_BAND (pixels; 0: not given)
 };
 
 Switches read_switches() {
     auto tri = [](const char* name, int other) { const char* v = getenv(name); return !v ? -1 : v[0] == '1' ? 1 : v[0] == '0' ? 0 : other; };
     auto num = [](const char* name, int hi) { const char* v = getenv(name); const int p = v ? atoi(v) : 0; return p < 0 ? 0 : (p > hi ? hi : p); };
+    auto px = [](const char* name) { const char* v = getenv(name); const double p = v ? atof(v) : 0.0; return p > 0.0 && p < 1024.0 ? p : 0.0; };
     return Switches{tri("FTL_SPLIT", 0), tri("FTL_NO_REGROUP", 0), tri("FTL_DEBUG_G8", 0), tri("FTL_RAYS_ONE_PASS", 1), tri("FTL_DEFER", 1),
                     tri("FTL_RAYS_CLASS_CULL", 1),
                     num("FTL_REGROUP_EVERY", INT32_MAX), num("FTL_DEBUG_CORR_LDS_CAP", INT32_MAX), num("FTL_DEBUG_LDS_PAD", 48 * 1024),
-                    num("FTL_DEBUG_LDS_PAD_RAYS", 48 * 1024), num("FTL_DEBUG_PAIR_WINDOW", FTL_PAIR_CAP), getenv("FTL_DEBUG_PRINT_LDS") != nullptr};
+                    num("FTL_DEBUG_LDS_PAD_RAYS", 48 * 1024), num("FTL_DEBUG_PAIR_WINDOW", FTL_PAIR_CAP), getenv("FTL_DEBUG_PRINT_LDS") != nullptr,
+                    tri("FTL_TRK_RUNNING", 1), px("FTL_DEBUG_TRK_BAND")};
 }
 
 // What ftl_create and ftl_tune decide about the frame kernel and the cost sort: plan_schedule()
@@ -470,6 +473,12 @@ int ftl_create(const ftl_config* cfg, int32_t n_envs, int32_t device, ftl_handle
                            + rects * 8 + 32                   /* facing-edge list (u16 x 4 per rect) + edge counters */
                            + (size_t)FTL_PAIR_CAP * 2 + 16);  /* candidate list of phase 3 */
     }
+    // The v2 tracker trims its window from a running length while that length stays exact in float64: the kernel drops it for a window
+    // that reaches 2^10 px (no config bounds the longest segment: a seeded step is as long as the field allows), which a window trimmed to
+    // a corridor_length of 2^10 or more always does.  FTL_TRK_RUNNING=0: the two full sums of every saving scan, no length kept.
+    P.trk_running = (h->sw.trk_running != 0 && cfg->has_tracker == 2 && cfg->corridor_length > 0.0 && cfg->corridor_length < 1024.0) ? 1 : 0;
+    P._pad_trk = 0;
+    P.trk_band = h->sw.trk_band;
     P.lds_rays += h->sw.lds_pad_rays;      // diagnostic: occupancy of the ray kernel without touching the code
     if (cfg->traj_cap > 65535 || frames_max(*cfg) > 4095) { delete h; return fail(FTL_E_INVALID, "traj_cap above 65535 or more than 4095 frames per step"); }
     if (apply_plan(h, n_envs)) { delete h; return FTL_E_INVALID; }

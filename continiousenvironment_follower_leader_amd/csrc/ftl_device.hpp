@@ -90,6 +90,10 @@ struct FtlDevParams {
     uint32_t inv_nrect_dyn;           // ceil(65536 / (R - 1)): source index / objects per snapshot without an integer division
     int32_t miss_const;               // 1: a ray without a hit reads float32(laser_length) exactly for every sensor (checked on the host: the
                                       // value float64 |end - origin| lies within 4e-13 of laser_length, far from a float32 rounding boundary)
+    // v2 tracker: the trim of the history window is decided from a running length (ftl_trktrim.hpp; FTL_TRK_RUNNING=0 and a
+    // corridor_length outside (0, 2^10) leave it to the two full sums); pixels added to the band of undecided trims (FTL_DEBUG_TRK_BAND)
+    int32_t trk_running, _pad_trk;
+    double trk_band;
     // env regrouping (library-owned; null = envs stay bound to their wavefronts): slot -> env, cost class of the next step,
     // rank inside the block histogram, per-block key histograms
     int32_t* perm; uint8_t* keys; uint16_t* rank; int32_t* bh;

@@ -12,6 +12,7 @@
 // Semantics are those of oracle/ftl_oracle.c operation by operation; reference citations as there.
 #pragma once
 #include "ftl_device.hpp"
+#include "ftl_trktrim.hpp"
 
 namespace ftl {
 
@@ -163,6 +164,10 @@ struct GCtx {
     float hx, hy;        // coordinates of trajectory point `hint`
     float clr_g, clr_a;  // lower bounds: distance follower -> any green point / any trajectory point (see g_frame)
     double green_w;      // running length of the green-zone window (approximate; decisions near the threshold are re-derived exactly)
+    // running length of the tracker's history window (g_sensors): trk_w is the exact float64 sum of the float32 segment lengths of
+    // hist[trk_tlo .. trk_thi) while trk_thi > trk_tlo and both equal corr_lo / corr_hi; trk_thi < 0: no length is kept, and none is
+    // taken up before corr_lo reaches trk_tlo.  FTL_RI_SPARE0/1 of robot 0 (the words of trk_w) and of robot 1 (trk_tlo, trk_thi)
+    double trk_w; int trk_tlo, trk_thi;
     Robot rb;
 };
 
@@ -179,6 +184,9 @@ __device__ __forceinline__ void g_load_late(const FtlDevParams& P, GCtx& E) {
     E.corr_hi = ei[FTL_EI_CORR_HI]; E.seed_end = ei[FTL_EI_SEED_END]; E.snap_count = ei[FTL_EI_SNAP_COUNT];
     E.episodes = ei[FTL_EI_EPISODES]; E.snap_head = ei[FTL_EI_SNAP_HEAD];
     E.acc_penalty = ed[FTL_ED_ACC_PENALTY]; E.overall_reward = ed[FTL_ED_OVERALL_REWARD];
+    const int2* rs = reinterpret_cast<const int2*>(rec_field(P.rb_int, P, E.env) + FTL_RI_SPARE0);
+    const int2 w01 = rs[0], t01 = rs[FTL_RI_COUNT / 2];
+    E.trk_w = __hiloint2double(w01.x, w01.y); E.trk_tlo = t01.x; E.trk_thi = t01.y;
     if (!REG) {
         E.acc_consumed = ei[FTL_EI_ACC_CONSUMED];
         E.cur_mult = ed[FTL_ED_CUR_MULT]; E.cur_acc = ed[FTL_ED_CUR_ACC]; E.cum_speed = ed[FTL_ED_CUM_SPEED];
@@ -249,7 +257,8 @@ __device__ __forceinline__ void g_store(const FtlDevParams& P, GCtx& E) {
         rd[FTL_RD_DIRECTION] = E.rb.direction; rd[FTL_RD_SPEED] = E.rb.speed; rd[FTL_RD_ROT_SPEED] = E.rb.rot_speed;
         rd[FTL_RD_DES_SPEED] = E.rb.des_speed; rd[FTL_RD_DES_ROT_SPEED] = E.rb.des_rot_speed;
         int4* ri = reinterpret_cast<int4*>(rec_field(P.rb_int, P, E.env) + E.r * FTL_RI_COUNT);
-        ri[0] = make_int4(E.rb.rx, E.rb.ry, E.rb.rw, E.rb.rh); ri[1] = make_int4(E.rb.rot_dir, E.rb.des_rot_dir, 0, 0);
+        ri[0] = make_int4(E.rb.rx, E.rb.ry, E.rb.rw, E.rb.rh); ri[1] = make_int4(E.rb.rot_dir, E.rb.des_rot_dir, E.r == 0 ? __double2hiint(E.trk_w) : E.r == 1 ? E.trk_tlo : 0,
+                                                                                E.r == 0 ? __double2loint(E.trk_w) : E.r == 1 ? E.trk_thi : 0);
         if (E.r >= 2) {
             int b = E.r - 2;
             ed[FTL_ED_BEAR_POINTS + 2 * b] = E.rb.tgt_x; ed[FTL_ED_BEAR_POINTS + 2 * b + 1] = E.rb.tgt_y;
@@ -286,6 +295,7 @@ __device__ __forceinline__ void g_reset(const FtlDevParams& P, GCtx& E, int scen
         E.cur_target_id = 1; E.leader_finished = 0; E.finish_timer = -1;
         E.green_count = 0; E.green_len = -1; E.green_w = 0.0; E.green_tiny = 0; E.error = 0; E.scan_ok = 0;
         E.trk_counter = 0; E.corr_lo = 0; E.corr_hi = 0; E.seed_end = 0; E.snap_count = 0; E.snap_head = 0;
+        E.trk_w = 0.0; E.trk_tlo = 0; E.trk_thi = -1;
         E.hint = 0; E.hx = 3.0e38f; E.hy = 3.0e38f; E.clr_g = 0.0f; E.clr_a = 0.0f;     // no cached point, no bound
         if (c.has_tracker == 1 && E.r == 0) rec_field(P.env_int, P, E.env)[FTL_EI_HIST1_LEN] = 0;   // v1 tracker reset(), SEN:223-226
         if (c.rand_fps_hi > 0 && E.fps == 0) E.fps = d_rand_frames(c, d_stream_id(P, E.env), 0, 0);      // the constructor's draw (ENV:405)
@@ -421,6 +431,11 @@ __device__ __forceinline__ int g_green_seq(const float2* tr, int n, double maxd)
 // every partial sum stays below 2^9, so float64 addition of them is EXACT: any summation order reproduces the
 // reference's sequential sums bit for bit.  Only a window that holds a shorter segment needs the tolerance band.
 static constexpr double kTinySeg = 9.5367431640625e-07;   // 2^-20
+// The tracker's running length while float64 seed points are in its window (g_sensors) is a rounded float64 sum, and so is the pairwise sum
+// it stands in for.  Both stay below 2^10, so every addition rounds by at most 2^-44: at most 520 of them take the length up, at most
+// 3 * corr_cap appends and pops follow before the last seed point leaves (no more pops than seed points, no more appends than pops plus
+// the ring's capacity; FTL_MAX_CORR_CAP = 512), and the pairwise sum has fewer than 520 -- under 2^-32 px in all.  The band added for such windows:
+static constexpr double kTrkSeedBand = 1e-8;
 template <int G>
 __device__ __forceinline__ int g_green_walk(const FtlDevParams& P, const GCtx& E, double& wlen, int& tiny) {
     const float2* tr = reinterpret_cast<const float2*>(P.traj + (size_t)E.env * P.cfg.traj_cap * 2);
@@ -1106,11 +1121,13 @@ __device__ __forceinline__ void g_tail(const TailK& K, GCtx& E, const int rec, i
 
 // ---- LeaderPositionsTracker_v2.scan (sensors.py:243-327), one env per group; the sequential parts (numpy pairwise
 // sum, border pairs) are evaluated redundantly by every lane of the group, memory is written by lane r == 0 ------------
-__device__ __forceinline__ double g_hist_dist(const FtlDevParams& P, int env, int i, bool f64) {     // |hist[i] - hist[i+1]| in the array's dtype
-    const double* p = hist_slot(P, env, i); const double* q = hist_slot(P, env, i + 1);
+__device__ __forceinline__ double g_seg(const double* p, const double* q, bool f64) {     // |p - q| of two history points in the array's dtype
     if (f64) { double dx = p[0] - q[0], dy = p[1] - q[1]; return sqrt(dx * dx + dy * dy); }
     float dx = (float)p[0] - (float)q[0], dy = (float)p[1] - (float)q[1];
     return (double)sqrtf(dx * dx + dy * dy);
+}
+__device__ __forceinline__ double g_hist_dist(const FtlDevParams& P, int env, int i, bool f64) {     // |hist[i] - hist[i+1]| in the array's dtype
+    return g_seg(hist_slot(P, env, i), hist_slot(P, env, i + 1), f64);
 }
 // numpy pairwise sum of the m-1 consecutive distances of hist[lo..hi) without staging them (a[i] = dist(lo+i, lo+i+1));
 // T is the array dtype (float when no seeded float64 point is left).  n <= 128 * 4 (validated on the host).
@@ -1171,8 +1188,9 @@ __device__ __forceinline__ double g_path_length(const FtlDevParams& P, const GCt
     if (lo < E.seed_end) return g_pw<double, G>(P, E.env, E.r, lo, m - 1, true);
     return (double)g_pw<float, G>(P, E.env, E.r, lo, m - 1, false);
 }
-__device__ __forceinline__ void g_border_pair(const FtlDevParams& P, const GCtx& E, int i1, int i0, int ia, int at, bool write) {
-    const double* p1 = hist_slot(P, E.env, i1); const double* p0 = hist_slot(P, E.env, i0); const double* a = hist_slot(P, E.env, ia);
+// the border pair of corridor slot `at` from the history points p1 = hist[i1], p0 = hist[i0] and a = hist[ia], given as values
+__device__ __forceinline__ void g_border_pair_v(const FtlDevParams& P, const GCtx& E, const double* p1, const double* p0, const double* a,
+                                                int i1, int i0, int at, bool write) {
     double vx, vy;
     if (i1 < E.seed_end || i0 < E.seed_end) {
         vx = p1[0] - p0[0]; vy = p1[1] - p0[1];
@@ -1192,6 +1210,39 @@ __device__ __forceinline__ void g_border_pair(const FtlDevParams& P, const GCtx&
         double* q = corr_slot(P, E.env, at); q[0] = r0; q[1] = r1; q[2] = l0; q[3] = l1;
         *corr32_slot(P, E.env, at) = make_float4((float)r0, (float)r1, (float)l0, (float)l1);
     }
+}
+__device__ __forceinline__ void g_border_pair(const FtlDevParams& P, const GCtx& E, int i1, int i0, int ia, int at, bool write) {
+    g_border_pair_v(P, E, hist_slot(P, E.env, i1), hist_slot(P, E.env, i0), hist_slot(P, E.env, ia), i1, i0, at, write);
+}
+// Take up the running length of hist[corr_lo .. corr_hi) (GCtx::trk_w): the in-order float64 sum of its segment lengths.  Lane r of the
+// group computes segments r, r + G, ..; the sum takes them in order from the lanes, so every lane ends with the same bits as the sequential
+// form.  Float32 segments (no seed point left): the sum is exact, hence the value every other route to this window arrives at; not taken
+// up -- the full sums trim the window until corr_lo has passed the obstacle -- while a non-zero segment below kTinySeg or a length of
+// 2^10 is in the way.  With float64 seed points in the window the segments are float64 and the sum is a rounded one.
+// Must be called by all G lanes of the group.
+template <int G, int K = 0>
+__device__ __forceinline__ void g_trk_take(double d, int i0, int n, bool f64, double& s, int& tiny_at) {
+    const double dk = gb_d<G, K>(d);
+    if (i0 + K < n) { s += dk; if (!f64 && dk != 0.0 && dk < kTinySeg) tiny_at = i0 + K; }
+    if constexpr (K + 1 < G) g_trk_take<G, K + 1>(d, i0, n, f64, s, tiny_at);
+}
+template <int G>
+__device__ __forceinline__ void g_trk_establish(const FtlDevParams& P, GCtx& E) {
+    const int n = E.corr_hi - E.corr_lo - 1;
+    if (n < 1 || (E.trk_thi < 0 && E.corr_lo < E.trk_tlo)) {
+        if (E.trk_thi >= 0) { E.trk_tlo = 0; E.trk_thi = -1; }
+        return;
+    }
+    const bool f64 = E.corr_lo < E.seed_end;
+    double s = 0.0; int tiny_at = -1;
+#pragma nounroll
+    for (int i = 0; i < n; i += G) {
+        const double d = g_hist_dist(P, E.env, E.corr_lo + min(i + E.r, n - 1), f64);
+        g_trk_take<G>(d, i, n, f64, s, tiny_at);
+    }
+    if (tiny_at >= 0) { E.trk_tlo = E.corr_lo + tiny_at + 1; E.trk_thi = -1; }
+    else if (!(s < 1024.0)) { E.trk_tlo = E.corr_lo + 1; E.trk_thi = -1; }
+    else { E.trk_w = s; E.trk_tlo = E.corr_lo; E.trk_thi = E.corr_hi; }
 }
 
 // Both scans of a step for every env of the wave.  Memory written by one lane is read by the other lanes of its group
@@ -1216,12 +1267,32 @@ __device__ __forceinline__ void g_sensors(const FtlDevParams& P, GCtx& E) {
         bool save = E.valid && (E.trk_counter % c.tracker_saving_period == 0);
         bool counted = E.valid;                      // sensors.py:247-251 returns WITHOUT incrementing the counter
         bool first = false;
+        // The running length (GCtx::trk_w) decides the trim of a scan that appends one point to the window it belongs to.  Everything such a
+        // scan reads is requested here, in one memory round trip: the last point (which the reference compares with the leader's position,
+        // and the final border pair is built from), the snapshot windows, and the three oldest points -- the two segments a steady-state
+        // trim can drop.  (A point of those three that is the one appended below is taken from the registers instead.)
+        bool run = false;
+        double lastp[2] = {0.0, 0.0};
+        double h0[2] = {0.0, 0.0}, h1[2] = {0.0, 0.0}, h2[2] = {0.0, 0.0};
         if (save) {
             int len = E.corr_hi - E.corr_lo;
+            run = P.trk_running != 0 && len > 0 && E.trk_thi == E.corr_hi && E.trk_tlo == E.corr_lo;
             if (len > 0) {
                 const double* last = hist_slot(P, E.env, E.corr_hi - 1);
-                if (last[0] == (double)lpx && last[1] == (double)lpy) { save = false; counted = false; }
+                lastp[0] = last[0]; lastp[1] = last[1];
+                if (run) {
+                    const double* q0 = hist_slot(P, E.env, E.corr_lo); const double* q1 = hist_slot(P, E.env, E.corr_lo + 1);
+                    const double* q2 = hist_slot(P, E.env, E.corr_lo + 2);
+                    h0[0] = q0[0]; h0[1] = q0[1]; h1[0] = q1[0]; h1[1] = q1[1]; h2[0] = q2[0]; h2[1] = q2[1];
+                }
             }
+            int oldest = E.corr_lo;               // the ring must still hold every point a stored snapshot refers to
+            {
+                const int* sw = rec_field(P.snap_win, P, E.env);
+                int nsnap = E.snap_count < P.hmax ? E.snap_count : P.hmax;
+                for (int j = 0; j < nsnap; j++) { int l0 = sw[4 * j], l1 = sw[4 * j + 2]; oldest = min(oldest, min(l0, l1)); }
+            }
+            if (len > 0 && lastp[0] == (double)lpx && lastp[1] == (double)lpy) { save = false; counted = false; }
             if (save) {
                 first = (len == 0 && E.trk_counter == 0);
                 if (first) {
@@ -1260,13 +1331,21 @@ __device__ __forceinline__ void g_sensors(const FtlDevParams& P, GCtx& E) {
                         }
                     }
                 } else {                                              // sensors.py:286
-                    int oldest = E.corr_lo;               // the ring must still hold every point a stored snapshot refers to
-                    const int* sw = rec_field(P.snap_win, P, E.env);
-                    int nsnap = E.snap_count < P.hmax ? E.snap_count : P.hmax;
-                    for (int j = 0; j < nsnap; j++) { int l0 = sw[4 * j], l1 = sw[4 * j + 2]; oldest = min(oldest, min(l0, l1)); }
                     if (E.corr_hi + 1 - oldest > c.corr_cap) { E.error |= FTL_ERR_CORR_OVERFLOW; save = false; }
                     else {
                         if (w) { double* h = hist_slot(P, E.env, E.corr_hi); h[0] = (double)lpx; h[1] = (double)lpy; }
+                        if (run) {                    // the new segment, as g_hist_dist(corr_hi - 1) will read it from the ring
+                            const double np[2] = {(double)lpx, (double)lpy};
+                            const bool f64 = E.corr_lo < E.seed_end;
+                            if (E.corr_lo + 1 == E.corr_hi) { h1[0] = np[0]; h1[1] = np[1]; }
+                            if (E.corr_lo + 2 == E.corr_hi) { h2[0] = np[0]; h2[1] = np[1]; }
+                            const double d_new = g_seg(lastp, np, f64);
+                            const double wn = E.trk_w + d_new;
+                            // a tiny segment or a length of 2^10 ends the exact arithmetic: full sums until it has left the window
+                            if (!f64 && d_new != 0.0 && d_new < kTinySeg) { run = false; E.trk_tlo = E.corr_hi; E.trk_thi = -1; }
+                            else if (!(wn < 1024.0)) { run = false; E.trk_tlo = E.corr_lo + 1; E.trk_thi = -1; }
+                            else E.trk_w = wn;
+                        }
                         E.corr_hi += 1;
                     }
                 }
@@ -1275,18 +1354,43 @@ __device__ __forceinline__ void g_sensors(const FtlDevParams& P, GCtx& E) {
         __syncthreads();
         // ---- phase B: trim to corridor_length, append the border pair(s) ------------------------------------------------
         if (save) {
-            double path = g_path_length<G>(P, E, E.corr_lo, E.corr_hi);          // sensors.py:288-297
-            while (path > c.corridor_length) {
+            // sensors.py:288-297.  path_length feeds nothing but this test.  With a running length: away from the threshold the length decides
+            // it (ftl_trktrim.hpp); inside the band the pairwise sum is evaluated, once, for that one decision.  While float64 seed points are in
+            // the window the length is a rounded sum (kTrkSeedBand); the pop that drops the last of them changes the dtype of every
+            // segment, and the exact length is taken up afresh below.  Without one: the pairwise sum after every pop, as before.
+            for (;;) {
+                const bool f64 = E.corr_lo < E.seed_end;
+                if (E.corr_hi - E.corr_lo < 2) run = false;      // no segment left: the sum is 0, whatever an injected state holds as length
+                int dec = FTL_TRIM_UNDECIDED;
+                if (run) dec = ftl_trk_trim(E.trk_w, c.corridor_length, P.trk_band + (f64 ? kTrkSeedBand : 0.0));
+                if (dec == FTL_TRIM_UNDECIDED) dec = g_path_length<G>(P, E, E.corr_lo, E.corr_hi) > c.corridor_length ? FTL_TRIM_POP : FTL_TRIM_KEEP;
+                if (dec != FTL_TRIM_POP) break;
                 if (first) E.error |= FTL_ERR_TRACKER_SEED;                   // reference: popleft on the still-empty corridor deque
                 E.corr_lo += 1;
-                path = g_path_length<G>(P, E, E.corr_lo, E.corr_hi);
+                if (run) {
+                    // the dropped segment comes from phase A's registers; the point a third pop of this scan would need (the first saves after
+                    // seeding) is requested now and waited for only then
+                    E.trk_w -= g_seg(h0, h1, f64);
+                    const double* q2 = hist_slot(P, E.env, E.corr_lo + 2);
+                    h0[0] = h1[0]; h0[1] = h1[1]; h1[0] = h2[0]; h1[1] = h2[1]; h2[0] = q2[0]; h2[1] = q2[1];
+                    if (f64 && E.corr_lo >= E.seed_end) run = false;
+                }
             }
+            if (run) { E.trk_tlo = E.corr_lo; E.trk_thi = E.corr_hi; }
+            else if (P.trk_running != 0) g_trk_establish<G>(P, E);
+            else { E.trk_tlo = 0; E.trk_thi = -1; }
             int m = E.corr_hi - E.corr_lo;
             if (m > 1) {                                                      // sensors.py:299-317
                 if (first)
                     for (int i = m - 1 - E.r; i > 0; i -= G)                  // the m-1 initial pairs are independent: strided over the group
                         g_border_pair(P, E, E.corr_lo + i, E.corr_lo + i - 1, E.corr_lo + m - i - 1, E.corr_lo + m - 1 - i, true);
-                g_border_pair(P, E, E.corr_hi - 1, E.corr_hi - 2, E.corr_hi - 2, E.corr_hi - 1, w);
+                // the last pair: p1 = the point phase A appended, p0 = a = the one it loaded -- the values the ring holds, without the trip to it
+                double p1[2] = {(double)lpx, (double)lpy};
+                if (first) {
+                    const double* q1 = hist_slot(P, E.env, E.corr_hi - 1); const double* q0 = hist_slot(P, E.env, E.corr_hi - 2);
+                    p1[0] = q1[0]; p1[1] = q1[1]; lastp[0] = q0[0]; lastp[1] = q0[1];
+                }
+                g_border_pair_v(P, E, p1, lastp, lastp, E.corr_hi - 1, E.corr_hi - 2, E.corr_hi - 1, w);
             }
         }
         if (counted) E.trk_counter += 1;
@@ -1668,7 +1772,12 @@ __global__ void __launch_bounds__(FTL_WAVE, FTL_FRAMESG_WPE) ftl_frames_group_ke
         // tracker: envs whose counters are at most one scan apart save in the same steps and stay together from step to
         // step (all counters advance by two per step); class 0 = saves in the next step
         int tc = 0;
-        if (P.cfg.has_tracker == 2) {
+#ifndef FTL_KEY_NOTRK           // diagnostic build: the key without the tracker class (A/B of what it is worth, profiles/README.md)
+        if (P.cfg.has_tracker == 2)
+#else
+        if (false)
+#endif
+        {
             const int per = P.cfg.tracker_saving_period;
             tc = (((E.trk_counter + 1) % per) * 4) / per;
         }

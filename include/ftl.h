@@ -1307,7 +1307,9 @@ enum { FTL_ED_ACC_PENALTY = 0, FTL_ED_OVERALL_REWARD, FTL_ED_SPARE0, FTL_ED_SPAR
        FTL_ED_CUR_MULT,  /* cur_speed_multiplier (ENV:412, 449, 1150-1156) */
        FTL_ED_CUR_ACC, FTL_ED_CUM_SPEED, /* cur_leader_acceleration, cur_leader_cumulative_speed (ENV:591-592, 1167-1172) */
        FTL_ED_COUNT };
-/* per robot: rb_dbl[5] and rb_int[8] */
+/* per robot: rb_dbl[5] and rb_int[8].  FTL_RI_SPARE0/1 of robots 0 and 1 carry the v2 tracker's running corridor length (search
+   acceleration, like FTL_ED_GREEN_W): robot 0 the high / low word of the float64 length of the history window, robot 1 the window
+   (corr_lo, corr_hi) it belongs to -- (x, -1): none is kept.  Zeroed or foreign words are re-derived by the next saving scan. */
 enum { FTL_RD_DIRECTION = 0, FTL_RD_SPEED, FTL_RD_ROT_SPEED, FTL_RD_DES_SPEED, FTL_RD_DES_ROT_SPEED, FTL_RD_COUNT };
 enum { FTL_RI_X = 0, FTL_RI_Y, FTL_RI_W, FTL_RI_H, FTL_RI_ROT_DIR, FTL_RI_DES_ROT_DIR, FTL_RI_SPARE0, FTL_RI_SPARE1, FTL_RI_COUNT };
 
