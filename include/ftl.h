@@ -570,6 +570,15 @@ int ftl_kernel_times(ftl_handle* h, double* ms, int32_t* n_steps);
  *   outline of an integer rect (x, y, w, h): the points inside [x, x + w) x [y, y + h) that lie within one output pixel of its border
  *              (at scale 1 and origin 0 exactly pygame.draw.rect(width=1)'s pixels).
  * The last primitive in painter's order that covers a pixel sets its colour; there is no anti-aliasing; uncovered pixels are white.
+ * A pixel centre exactly on a boundary follows the <= / < of the rule; these rules are met wherever the centre is farther than 1e-3
+ * output pixels from every boundary, and inside that band the float32 arithmetic may decide either way.  Range of that guarantee: a
+ * primitive is stored as float32 output-pixel coordinates and tested in float32 (no fused multiply-add), so with u = 2^-24 every rounding
+ * moves a distance by at most u M, M being the largest magnitude among the primitive's output-pixel coordinates (centre, end points,
+ * corners, relative to the image's origin) and sizes (radius, half sizes).  The longest chain, the segment's closest point, has 8 such
+ * roundings (2 stored end points, the edge vector, the product and the sum of the closest point, its square, the sum of squares, the
+ * squared half width): 8 u M <= 1e-3 holds up to M = 2048 output pixels, and that is the guaranteed range.  Zooming in (scale < 1) grows
+ * M as world size / scale: a primitive beyond the range that meets the image may be off by more than the band along its boundary
+ * (a float32 emulation of the tests finds the first such pixels at M = 32768; tests/test_render_numpy_host.py, profiles/render_edges_checks.txt).
  *
  * Painter's order (layer bits below; FTL_RENDER_TARGET stands for the ring the reference always draws):
  *   PATH     the route (pool route[0..route_len)) as a 1-px red polyline when route_len > 2; the bridge point (mean of the centres of
@@ -591,7 +600,12 @@ int ftl_kernel_times(ftl_handle* h, double* ms, int32_t* n_steps);
  *            sensors draw their lines only.  The v2 tracker draws its history points (discs of r 3) and, with more than one corridor
  *            point, the two corridor borders and the two end caps as 3-px segments (sensors.py:329-339).  The v1 tracker and the aux
  *            sensors draw nothing.
- *   TARGET   a red ring of r 10, width 2 at the current way-point route[cur_target_id] (the leader's start with an empty route). */
+ *   TARGET   a red ring of r 10, width 2 at the current way-point route[cur_target_id] (the leader's start with an empty route).
+ * State words outside their range are clamped, never followed out of an array: route_len to [0, route_cap], cur_target_id to
+ * [0, route_len - 1], the corridor window to max(0, min(FTL_EI_CORR_HI - FTL_EI_CORR_LO, corr_cap)) points from slot FTL_EI_CORR_LO modulo
+ * corr_cap; the green zone is drawn only when green_count > 5, green_len <= traj_cap and green_len - 1 - green_count >= 0.  An env
+ * whose scenario index FTL_EI_SCEN lies outside the loaded pool has no pool entry to read: no route and no finish point, no static rects
+ * and no bridge point, and the TARGET ring around the leader's current position; everything else is drawn as usual. */
 enum { FTL_RENDER_PATH = 1, FTL_RENDER_BOX = 2, FTL_RENDER_OBJECTS = 4, FTL_RENDER_RECTS = 8,
        FTL_RENDER_SENSORS = 16, FTL_RENDER_TARGET = 32 };
 #define FTL_RENDER_ALL 63u

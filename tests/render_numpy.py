@@ -31,6 +31,7 @@ class Raster:
         self.img = np.empty((self.h, self.w, 3), np.uint8)
         self.img[:] = rgb_of(WHITE)
         self.band = np.zeros((self.h, self.w), bool)
+        self.tie = np.zeros((self.h, self.w), bool)       # pixel centres exactly on a primitive boundary (decided by the <= / < rules)
 
     # world -> output pixels
     def X(self, x):
@@ -51,10 +52,12 @@ class Raster:
         py = np.arange(j0, j1, dtype=np.float64)[:, None] + 0.5
         return (slice(j0, j1), slice(i0, i1)), px, py
 
-    def _paint(self, win, cover, near, rgb):
+    def _paint(self, win, cover, near, rgb, tie=None):
         sl = win[0]
         self.img[sl][cover] = rgb_of(rgb)
         self.band[sl] |= near
+        if tie is not None:
+            self.tie[sl] |= tie
 
     # primitives in output pixels
     def disc_px(self, cx, cy, r, r_in, rgb):
@@ -66,10 +69,12 @@ class Raster:
         d = np.sqrt(d2)
         cover = d2 <= r * r
         near = (np.abs(d - r) < TOL) & (d2 != r * r)
+        tie = d2 == r * r
         if r_in >= 0:
             cover &= d2 > r_in * r_in
             near |= (np.abs(d - r_in) < TOL) & (d2 != r_in * r_in)
-        self._paint(win, cover, near, rgb)
+            tie |= d2 == r_in * r_in
+        self._paint(win, cover, near, rgb, tie)
 
     def seg_px(self, ax, ay, bx, by, hw, rgb):
         win = self._window(min(ax, bx) - hw, min(ay, by) - hw, max(ax, bx) + hw, max(ay, by) + hw)
@@ -82,7 +87,7 @@ class Raster:
         u = np.clip(u, 0.0, 1.0)
         qx, qy = (ax + u * ex) - px, (ay + u * ey) - py
         d2 = qx * qx + qy * qy
-        self._paint(win, d2 <= hw * hw, (np.abs(np.sqrt(d2) - hw) < TOL) & (d2 != hw * hw), rgb)
+        self._paint(win, d2 <= hw * hw, (np.abs(np.sqrt(d2) - hw) < TOL) & (d2 != hw * hw), rgb, d2 == hw * hw)
 
     def rrect_px(self, cx, cy, ux, uy, hw, hh, rgb):
         ex, ey = abs(ux) * hw + abs(uy) * hh, abs(uy) * hw + abs(ux) * hh
@@ -94,7 +99,7 @@ class Raster:
         a, b = np.abs(dx * ux + dy * uy), np.abs(dy * ux - dx * uy)
         cover = (a <= hw) & (b <= hh)
         near = ((np.abs(a - hw) < TOL) & (a != hw) & (b <= hh + TOL)) | ((np.abs(b - hh) < TOL) & (b != hh) & (a <= hw + TOL))
-        self._paint(win, cover, near, rgb)
+        self._paint(win, cover, near, rgb, ((a == hw) & (b <= hh)) | ((b == hh) & (a <= hw)))
 
     def outline_px(self, x0, y0, x1, y1, rgb):
         win = self._window(x0, y0, x1, y1)
@@ -107,7 +112,9 @@ class Raster:
             return (np.abs(p - e) < TOL) & (p != e)
         nx = near(px, x0) | near(px, x1) | near(px, x0 + 1) | near(px, x1 - 1)
         ny = near(py, y0) | near(py, y1) | near(py, y0 + 1) | near(py, y1 - 1)
-        self._paint(win, inside & border, (nx & (py >= y0 - TOL) & (py <= y1 + TOL)) | (ny & (px >= x0 - TOL) & (px <= x1 + TOL)), rgb)
+        self._paint(win, inside & border, (nx & (py >= y0 - TOL) & (py <= y1 + TOL)) | (ny & (px >= x0 - TOL) & (px <= x1 + TOL)), rgb,
+                    (((px == x0) | (px == x1) | (px == x0 + 1) | (px == x1 - 1)) & (py >= y0) & (py <= y1))
+                    | (((py == y0) | (py == y1) | (py == y0 + 1) | (py == y1 - 1)) & (px >= x0) & (px <= x1)))
 
     # primitives in world pixels
     def disc(self, x, y, r, rgb):
@@ -134,13 +141,14 @@ class Raster:
 
 
 def env_scene(env, e):
-    """Everything the spec reads for env ``e`` of a VecGame / PipelinedVecGame, as host arrays."""
+    """Everything the spec reads for env ``e`` of a VecGame / PipelinedVecGame, as host arrays.  ``pool`` is None when the env's scenario
+    index (EI_SCEN) lies outside the pool (include/ftl.h: no route, no static rects, target ring at the leader)."""
     import torch  # noqa: F401
     cfg = env.cfg
     R = cfg.n_robots
     ei = env.state_field("env_int")[e].cpu().numpy()
     s = int(ei[abi.EI_SCEN])
-    pool = {k: v[s].cpu().numpy() for k, v in env.pool.t.items()}
+    pool = {k: v[s].cpu().numpy() for k, v in env.pool.t.items()} if 0 <= s < env.pool.n else None
     cap = cfg.c.corr_cap
     return dict(env_int=ei, rb_pos=env.state_field("rb_pos")[e].cpu().numpy().reshape(R, 2),
                 rb_dbl=env.state_field("rb_dbl")[e].cpu().numpy().reshape(R, abi.RD_COUNT),
@@ -151,47 +159,60 @@ def env_scene(env, e):
                 lasers=env.lasers[e].cpu().numpy(), pool=pool)
 
 
-def render_scene(cfg, sc, width, height, scale=1.0, origin=(0.0, 0.0), layers=abi.RENDER_ALL, lasers=True):
-    """(image uint8 [H, W, 3], band bool [H, W]) of one env's scene (``env_scene``) under the spec of include/ftl.h."""
+def _prim(kind, rgb, g, layer, section):
+    return dict(kind=kind, rgb=rgb, g=tuple(float(v) for v in g), layer=layer, section=section)
+
+
+def scene_prims(cfg, sc, layers=abi.RENDER_ALL, lasers=True):
+    """The ordered primitive list include/ftl.h prescribes for one env's scene (``env_scene``): dicts of ``kind``, ``rgb``, float64
+    geometry ``g`` in world units, the ``layer`` bit and a ``section`` name.  Geometry by kind:
+        disc (x, y, r); ring (x, y, r, stroke w); seg (ax, ay, bx, by, stroke w); robot (x, y, direction deg, w, h);
+        box (x, y, w, h) filled; outline (x, y, w, h).
+    ``render_scene`` paints exactly this list, so ``len(scene_prims(...))`` is the length the device list must have."""
     c = cfg.c
     R = cfg.n_robots
-    ras = Raster(width, height, scale, origin)
+    out = []
     ei, pos, rd, ri, pool = sc["env_int"], sc["rb_pos"].astype(np.float64), sc["rb_dbl"], sc["rb_int"], sc["pool"]
-    rlen = int(np.clip(pool["route_len"], 0, c.route_cap))
-    route = pool["route"].astype(np.float64)
-    srects = pool["static_rects"].reshape(-1, 4) if c.n_static > 0 else np.zeros((0, 4), np.int32)
+    if pool is None:            # scenario index outside the pool
+        rlen, route, srects = 0, np.zeros((0, 2)), np.zeros((0, 4), np.int32)
+    else:
+        rlen = int(np.clip(pool["route_len"], 0, c.route_cap))
+        route = pool["route"].astype(np.float64)
+        srects = pool["static_rects"].reshape(-1, 4) if c.n_static > 0 else np.zeros((0, 4), np.int32)
     if layers & abi.RENDER_PATH:
         if rlen > 2:
             for i in range(rlen - 1):
-                ras.seg(route[i, 0], route[i, 1], route[i + 1, 0], route[i + 1, 1], 1.0, RED)
+                out.append(_prim("seg", RED, (route[i, 0], route[i, 1], route[i + 1, 0], route[i + 1, 1], 1.0), abi.RENDER_PATH, "route"))
         if len(srects) >= 2:
             a, b = srects[0].astype(np.float64), srects[1].astype(np.float64)
-            ras.disc(((a[0] + 0.5 * a[2]) + (b[0] + 0.5 * b[2])) * 0.5, ((a[1] + 0.5 * a[3]) + (b[1] + 0.5 * b[3])) * 0.5, 5.0, BLACK)
+            out.append(_prim("disc", BLACK, (((a[0] + 0.5 * a[2]) + (b[0] + 0.5 * b[2])) * 0.5,
+                                             ((a[1] + 0.5 * a[3]) + (b[1] + 0.5 * b[3])) * 0.5, 5.0), abi.RENDER_PATH, "bridge"))
         if rlen >= 1:
-            ras.disc(route[rlen - 1, 0], route[rlen - 1, 1], 5.0, RED)
+            out.append(_prim("disc", RED, (route[rlen - 1, 0], route[rlen - 1, 1], 5.0), abi.RENDER_PATH, "finish"))
     if layers & abi.RENDER_BOX:
         # green_zone_trajectory_points (ENV:1835-1841) were built on the trajectory of EI_GREEN_LEN points, before that frame's append
         gl, gc = int(ei[abi.EI_GREEN_LEN]), int(ei[abi.EI_GREEN_COUNT])
         if gc > 5 and gl <= c.traj_cap and gl - 1 - gc >= 0:
             tr = sc["traj"].astype(np.float64)
             for q in range(gl - 2, gl - 2 - gc, -1):
-                ras.disc(tr[q, 0], tr[q, 1], c.max_dev, GREEN)
-        ras.ring(pos[0, 0], pos[0, 1], c.min_distance, 2.0 if ei[abi.EI_TOO_CLOSE] else 1.0, RED)
+                out.append(_prim("disc", GREEN, (tr[q, 0], tr[q, 1], c.max_dev), abi.RENDER_BOX, "green"))
+        out.append(_prim("ring", RED, (pos[0, 0], pos[0, 1], c.min_distance, 2.0 if ei[abi.EI_TOO_CLOSE] else 1.0), abi.RENDER_BOX, "min_ring"))
     if layers & abi.RENDER_OBJECTS:
         rects = bool(layers & abi.RENDER_RECTS)
         sizes = [c.leader, c.follower] + [c.bear] * (R - 2)
         colours = [LEADER, FOLLOWER] + [BEAR] * (R - 2)
 
         def robot(r):
-            ras.robot(pos[r, 0], pos[r, 1], rd[r, abi.RD_DIRECTION], sizes[r].img_w, sizes[r].img_h, colours[r])
+            out.append(_prim("robot", colours[r], (pos[r, 0], pos[r, 1], rd[r, abi.RD_DIRECTION], sizes[r].img_w, sizes[r].img_h),
+                             abi.RENDER_OBJECTS, "robot%d" % r))
             if rects:
-                ras.outline(ri[r, :4])
+                out.append(_prim("outline", RED, ri[r, :4], abi.RENDER_RECTS, "robot%d" % r))
         robot(0)
         robot(1)
         for i, r in enumerate(srects):
-            ras.box(r, WALL if i < 2 else ROCK)
+            out.append(_prim("box", WALL if i < 2 else ROCK, r, abi.RENDER_OBJECTS, "static%d" % i))
             if rects:
-                ras.outline(r)
+                out.append(_prim("outline", RED, r, abi.RENDER_RECTS, "static%d" % i))
         for r in range(2, R):
             robot(r)
     if layers & abi.RENDER_SENSORS:
@@ -212,7 +233,7 @@ def render_scene(cfg, sc, width, height, scale=1.0, origin=(0.0, 0.0), layers=ab
                     t = th * (math.pi / 180.0)
                     cs, sn = math.cos(t), math.sin(t)
                     ends.append((cs, sn))
-                    ras.seg(fx, fy, fx + cs * lc.length, fy + sn * lc.length, 1.0, line)
+                    out.append(_prim("seg", line, (fx, fy, fx + cs * lc.length, fy + sn * lc.length, 1.0), abi.RENDER_SENSORS, "rays%d" % k))
                 if lc.compas or not lasers:
                     continue
                 for j in range(H - 1 if v1 else 0, H):            # collide points (hit or end point) per row, oldest first
@@ -225,7 +246,7 @@ def render_scene(cfg, sc, width, height, scale=1.0, origin=(0.0, 0.0), layers=ab
                             lis = N / 4
                             col = (0 if i < lis else 1 if i < 2 * lis else 2 if i < 3 * lis else 3) * N + i
                         v = float(row[col])
-                        ras.disc(fx + cs * v, fy + sn * v, 5.0 if newest else 3.0, colour)
+                        out.append(_prim("disc", colour, (fx + cs * v, fy + sn * v, 5.0 if newest else 3.0), abi.RENDER_SENSORS, "hits%d" % k))
         rays(False)
         if c.has_tracker == 2:
             lo, hi = int(ei[abi.EI_CORR_LO]), int(ei[abi.EI_CORR_HI])
@@ -233,22 +254,71 @@ def render_scene(cfg, sc, width, height, scale=1.0, origin=(0.0, 0.0), layers=ab
             idx = (lo + np.arange(cnt)) & (c.corr_cap - 1)
             hs, cr = sc["hist"][idx], sc["corr"][idx]
             for p in hs:
-                ras.disc(p[0], p[1], 3.0, TRACK_HIST)
+                out.append(_prim("disc", TRACK_HIST, (p[0], p[1], 3.0), abi.RENDER_SENSORS, "track_hist"))
             if cnt > 1:
                 for side in (0, 1):
                     for t in range(cnt - 1):
-                        ras.seg(cr[t, side, 0], cr[t, side, 1], cr[t + 1, side, 0], cr[t + 1, side, 1], 3.0, CORRIDOR)
+                        out.append(_prim("seg", CORRIDOR, (cr[t, side, 0], cr[t, side, 1], cr[t + 1, side, 0], cr[t + 1, side, 1], 3.0),
+                                         abi.RENDER_SENSORS, "corridor"))
                 for q in (0, cnt - 1):
-                    ras.seg(cr[q, 0, 0], cr[q, 0, 1], cr[q, 1, 0], cr[q, 1, 1], 3.0, CORRIDOR)
+                    out.append(_prim("seg", CORRIDOR, (cr[q, 0, 0], cr[q, 0, 1], cr[q, 1, 0], cr[q, 1, 1], 3.0), abi.RENDER_SENSORS, "corridor_cap"))
         rays(True)
     if layers & abi.RENDER_TARGET:
-        if rlen == 0:
+        if pool is None:
+            tx, ty = pos[0, 0], pos[0, 1]
+        elif rlen == 0:
             tx, ty = float(pool["robot_pos"][0, 0]), float(pool["robot_pos"][0, 1])
         else:
             t = min(max(int(ei[abi.EI_TARGET_ID]), 0), rlen - 1)
             tx, ty = route[t, 0], route[t, 1]
-        ras.ring(tx, ty, 10.0, 2.0, RED)
-    return ras.img, ras.band
+        out.append(_prim("ring", RED, (tx, ty, 10.0, 2.0), abi.RENDER_TARGET, "target"))
+    return out
+
+
+def paint_prim(ras, p):
+    """Paint one ``scene_prims`` entry into a ``Raster``."""
+    g, rgb = p["g"], p["rgb"]
+    k = p["kind"]
+    if k == "disc": ras.disc(g[0], g[1], g[2], rgb)
+    elif k == "ring": ras.ring(g[0], g[1], g[2], g[3], rgb)
+    elif k == "seg": ras.seg(g[0], g[1], g[2], g[3], g[4], rgb)
+    elif k == "robot": ras.robot(g[0], g[1], g[2], g[3], g[4], rgb)
+    elif k == "box": ras.box(g, rgb)
+    elif k == "outline": ras.outline(g)
+    else: raise ValueError(k)
+
+
+def prim_bbox(prim, scale=1.0, origin=(0.0, 0.0)):
+    """(x0, y0, x1, y1): the bounding box of a ``scene_prims`` entry in output pixels (strokes included)."""
+    ras = Raster(1, 1, scale, origin)
+    g, k = prim["g"], prim["kind"]
+    if k in ("disc", "ring"):
+        cx, cy, r = ras.X(g[0]), ras.Y(g[1]), g[2] / ras.s
+        return cx - r, cy - r, cx + r, cy + r
+    if k == "seg":
+        ax, ay, bx, by, hw = ras.X(g[0]), ras.Y(g[1]), ras.X(g[2]), ras.Y(g[3]), 0.5 * ras.stroke(g[4])
+        return min(ax, bx) - hw, min(ay, by) - hw, max(ax, bx) + hw, max(ay, by) + hw
+    if k == "robot":
+        t = math.radians(g[2])
+        ux, uy, hw, hh = abs(math.cos(t)), abs(math.sin(t)), 0.5 * g[3] / ras.s, 0.5 * g[4] / ras.s
+        cx, cy, ex, ey = ras.X(g[0]), ras.Y(g[1]), ux * hw + uy * hh, uy * hw + ux * hh
+        return cx - ex, cy - ey, cx + ex, cy + ey
+    if k in ("box", "outline"):
+        return ras.X(g[0]), ras.Y(g[1]), ras.X(g[0] + g[2]), ras.Y(g[1] + g[3])
+    raise ValueError(k)
+
+
+def render_prims(prims, width, height, scale=1.0, origin=(0.0, 0.0), ties=False):
+    """(image, band) of a primitive list painted in order; with ``ties`` also the mask of pixel centres exactly on a boundary."""
+    ras = Raster(width, height, scale, origin)
+    for p in prims:
+        paint_prim(ras, p)
+    return (ras.img, ras.band, ras.tie) if ties else (ras.img, ras.band)
+
+
+def render_scene(cfg, sc, width, height, scale=1.0, origin=(0.0, 0.0), layers=abi.RENDER_ALL, lasers=True):
+    """(image uint8 [H, W, 3], band bool [H, W]) of one env's scene (``env_scene``) under the spec of include/ftl.h."""
+    return render_prims(scene_prims(cfg, sc, layers, lasers), width, height, scale, origin)
 
 
 def compare(got, want, band, max_frac=5e-4):
