@@ -166,6 +166,10 @@ def load():
     lib.ftl_gae.restype = C.c_int
     lib.ftl_mlp_forward.argtypes = [vp, C.POINTER(abi.Mlp), i32, i32, vp, C.c_int64, vp, C.c_int64, vp]
     lib.ftl_mlp_forward.restype = C.c_int
+    lib.ftl_mlp_backward.argtypes = [vp, C.POINTER(abi.Mlp), i32, i32, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp]
+    lib.ftl_mlp_backward.restype = C.c_int
+    lib.ftl_sizeof_mlp_backward_workspace.argtypes = [C.POINTER(abi.Mlp), i32, i32]
+    lib.ftl_sizeof_mlp_backward_workspace.restype = C.c_int64
     lib.ftl_sizeof_rnn.restype = C.c_size_t
     lib.ftl_sizeof_rnn_collect_buffers.restype = C.c_size_t
     lib.ftl_rnn_param_count.argtypes = [C.POINTER(i32), i32, i32, u32]
@@ -225,7 +229,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_search_select", "ftl_search",
            "ftl_sizeof_guided_buffers", "ftl_baseline_act_guided", "ftl_rollout_guided", "ftl_guided_fanout", "ftl_search_guided",
            "ftl_sizeof_mlp", "ftl_mlp_param_count", "ftl_mlp_act", "ftl_rollout_mlp",
-           "ftl_sizeof_collect_buffers", "ftl_mlp_sample", "ftl_collect_mlp", "ftl_gae", "ftl_mlp_forward",
+           "ftl_sizeof_collect_buffers", "ftl_mlp_sample", "ftl_collect_mlp", "ftl_gae", "ftl_mlp_forward", "ftl_mlp_backward", "ftl_sizeof_mlp_backward_workspace",
            "ftl_sizeof_rnn", "ftl_sizeof_rnn_collect_buffers", "ftl_rnn_param_count", "ftl_rnn_act", "ftl_rollout_rnn", "ftl_collect_rnn",
            "ftl_sizeof_rnn_sequence", "ftl_rnn_forward",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",

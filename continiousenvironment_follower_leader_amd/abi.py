@@ -245,6 +245,7 @@ class GuidedBuffers(C.Structure):
 FTL_MLP_MAX_LAYERS, FTL_MLP_MAX_WIDTH, FTL_MLP_MAX_IN = 4, 256, 4096
 FTL_MLP_ENV_TILE, FTL_MLP_K_CHUNK, FTL_MLP_W_STAGE, FTL_MLP_ENVS_PER_WAVE, FTL_MLP_NEURON_BLOCK, FTL_MLP_THREADS = 32, 64, 4096, 16, 16, 256
 FTL_MLP_ACT_RELU, FTL_MLP_ACT_TANH = 0, 1          # ftl_mlp.activation: the hidden layers' function
+FTL_MLP_BWD_SPAN, FTL_MLP_BWD_MAX_IN = 64, FTL_MLP_MAX_IN          # ftl_mlp_backward: tiles of a span, the input-width limit
 
 
 def mlp_param_count(widths):

@@ -266,6 +266,292 @@ __global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_forward_kernel(const 
 
 __global__ __launch_bounds__(FTL_MLP_THREADS, 4) void ftl_mlp_forward_tanh_kernel(const Args a, const Forward fw) { mlp_body<false, FTL_MLP_ACT_TANH, true>(a, Sample{}, fw); }
 
+// ---- the backward pass of the net on recorded rows (include/ftl.h: ftl_mlp_backward) ---------------------------------------------------
+// ftl_mlp_backward_kernel / ftl_mlp_backward_tanh_kernel: one workgroup per SPAN of FTL_MLP_BWD_SPAN tiles of one set (the forward tile
+// map, the set's tiles enumerated block-major), the tiles one after the other.  Per tile: the hidden layers are recomputed with the loop of
+// mlp_body (same chunks, same MFMA order: the same bits), every hidden activation of the tile kept in LDS -- buffer l - 1 holds h_l
+// [TILE][act_stride] with a 1.0 in column width[l], the bias's input --, dy is staged into a buffer of its own, and for l = L .. 1 the weight
+// gradient takes h_{l-1}^T delta_l through the MFMA with K = the tile's 32 row slots and the span's running partial as the C operand, then
+// delta_{l-1} = (delta_l W_l^T) * act' through the MFMA with K = width[l] overwrites h_{l-1} in place (its only later reader is the element's
+// own derivative).  The running partial lives in the span's slice of the workspace, in the layout of a weight set: every lane loads the
+// four words of its accumulator tile, advances them by the tile's rows and stores them -- the same lane the same words on every tile, so
+// program order is all the ordering it needs and no workgroup ever reads another's.  The first tile of a span starts from +0 instead of a
+// load: the workspace needs no clearing.  Row slots past a cut tile's end feed +0 to both MFMA operands (a select on the row, not the
+// buffers' contents).  ftl_mlp_backward_reduce_kernel then sums a set's span partials in float64, ascending, one thread a word.
+struct Backward {
+    int64_t x_block_bytes;
+    const float* dy; int64_t dy_block_bytes;       // block b of the head gradients, [n][width[L]], at (char*)dy + b * dy_block_bytes
+    float* ws; int64_t count;                      // the span partials, [spans][count] floats; count = ftl_mlp_param_count
+    int32_t n_blocks, spans0, spans_mid;           // spans of the first touched set and of a whole set (the divisor of the span -> set map)
+};
+
+struct Reduce {
+    const float* ws; float* grad; int64_t count, set_stride;
+    int32_t set0, n_touched, spans0, spans_mid, spans_last;     // spans_last: of the last touched set when it is not the first
+};
+
+constexpr int BSPAN = FTL_MLP_BWD_SPAN, DWB = 4;   // accumulator tiles of the weight gradient a wave advances together
+
+// Row strides of the backward kernels' weight stage, chosen for the LDS banks (the values staged are the forward's): the forward product
+// reads B[k = lane >> 4][j = lane & 15], 16 consecutive floats of 4 rows -- a stride of 16 mod 32 puts the 64 lanes two to a bank --; the
+// delta product reads the transpose, B[j = lane >> 4][k = lane & 15] = W[k][j], 4 consecutive floats of 16 rows -- a stride of 4 mod 32.
+__host__ __device__ inline int fwd_stride(int w_out) { return ((w_out + 15) & ~31) + 16; }
+__host__ __device__ inline int bwd_stride(int w_out) { return ((w_out + 27) & ~31) + 4; }
+__host__ __device__ inline int dy_stride(int wl) { return ((wl + 31) & ~31) + 2; }      // act_stride's rule for the head alone
+
+// ws[kk * stride + j] = W[kk * w_out + j] for kk < kn, j < w_out, by all threads, without a division per element
+__device__ __forceinline__ void stage_rows(float* ws, int stride, const float* W, int kn, int w_out, int t) {
+    const int dk = FTL_MLP_THREADS / w_out, dj = FTL_MLP_THREADS - dk * w_out, n = kn * w_out;
+    int kk = t / w_out, j = t - kk * w_out;
+    for (int idx = t; idx < n; idx += FTL_MLP_THREADS) {
+        ws[kk * stride + j] = W[idx];
+        kk += dk; j += dj;
+        if (j >= w_out) { j -= w_out; kk++; }
+    }
+}
+
+// C += src^T delta over the tile's row slots, for the kn input columns [k0, k0 + kn) of a layer whose gradient matrix [w_in + 1][w_out]
+// starts at G: src holds the columns at [row][0 .. kn) with stride sstride, delta [row][w_out] with stride dstride
+__device__ __forceinline__ void dw_blocks(const float* src, int sstride, int k0, int kn, const float* delta, int dstride, int w_out,
+                                          float* G, bool first, int tile_n, int wave, int li, int lk) {
+    const int nkb = (kn + NB - 1) / NB, njb = (w_out + NB - 1) / NB, total = nkb * njb;
+    for (int q0 = wave * DWB; q0 < total; q0 += WAVES * DWB) {
+        f32x4 c[DWB];
+        int kb[DWB], jb[DWB];
+#pragma unroll
+        for (int u = 0; u < DWB; u++) {
+            const int q = q0 + u < total ? q0 + u : total - 1;
+            kb[u] = q / njb; jb[u] = q - kb[u] * njb;
+            const int j = jb[u] * NB + li;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int k = kb[u] * NB + 4 * lk + r;
+                c[u][r] = (!first && q0 + u < total && k < kn && j < w_out) ? G[(size_t)(k0 + k) * w_out + j] : 0.0f;
+            }
+        }
+        for (int rr = 0; rr < TILE; rr += 4) {
+            const int row = rr + lk;
+            const bool live = row < tile_n;
+#pragma unroll
+            for (int u = 0; u < DWB; u++) {
+                if (q0 + u >= total) continue;                  // (wave-uniform)
+                const int k = kb[u] * NB + li, j = jb[u] * NB + li;
+                const float av = (live && k < kn) ? src[row * sstride + k] : 0.0f;
+                const float bv = (live && j < w_out) ? delta[row * dstride + j] : 0.0f;
+                c[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, c[u], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DWB; u++) {
+            if (q0 + u >= total) continue;
+            const int j = jb[u] * NB + li;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int k = kb[u] * NB + 4 * lk + r;
+                if (k < kn && j < w_out) G[(size_t)(k0 + k) * w_out + j] = c[u][r];
+            }
+        }
+    }
+}
+
+template <int ACT>
+__device__ __forceinline__ void mlp_bwd_body(const Args& a, const Backward& bw) {
+    extern __shared__ float4 mlp_lds[];
+    const int L = a.n_layers, AS = a.act_stride;
+    const int DS = dy_stride(a.width[L]);
+    float* hb = reinterpret_cast<float*>(mlp_lds);             // [L - 1][TILE][AS]: buffer l - 1 is h_l, then delta_l
+    float* dyb = hb + (L - 1) * TILE * AS;                      // [TILE][DS]: dy
+    float* xs = dyb + TILE * DS;                                // [TILE][XS]
+    float* ws = xs + TILE * XS;                                 // the weight stage: bwd_stage_floats of the host
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, lk = lane >> 4;
+    const int g = wave % GROUPS, par = wave / GROUPS;
+    const int row_a = g * EPW + li, row_d = g * EPW + 4 * lk;
+    // the span's set, its rows of a block and its tiles
+    int m, sp;
+    if ((int)blockIdx.x < bw.spans0) { m = 0; sp = (int)blockIdx.x; }
+    else { const int q = (int)blockIdx.x - bw.spans0; m = 1 + q / bw.spans_mid; sp = q % bw.spans_mid; }
+    const int set = a.env_first / a.envs_per_set + m;
+    int seg, seg_end;
+    if (m == 0) { seg = 0; seg_end = a.len0; }
+    else {
+        const int64_t s0 = (int64_t)a.len0 + (int64_t)(m - 1) * a.envs_per_set, s1 = s0 + a.envs_per_set;
+        seg = (int)s0; seg_end = s1 < (int64_t)a.n_envs ? (int)s1 : a.n_envs;
+    }
+    const int set_tiles = (seg_end - seg + TILE - 1) / TILE;
+    const int64_t all_tiles = (int64_t)set_tiles * bw.n_blocks, tile0 = (int64_t)sp * BSPAN;
+    const int n_tiles = all_tiles - tile0 < BSPAN ? (int)(all_tiles - tile0) : BSPAN;
+    const float* P = a.params + (int64_t)set * a.set_stride;
+    float* G = bw.ws + (int64_t)blockIdx.x * bw.count;
+    const int w0 = a.width[0], wl = a.width[L];
+    int off[FTL_MLP_MAX_LAYERS + 1];
+    off[0] = 0;
+#pragma unroll
+    for (int l = 0; l < FTL_MLP_MAX_LAYERS; l++) off[l + 1] = off[l] + (l < L ? (a.width[l] + 1) * a.width[l + 1] : 0);
+    for (int ti = 0; ti < n_tiles; ti++) {
+        const int64_t gt = tile0 + ti;
+        const int blk = (int)(gt / set_tiles), start = seg + (int)(gt - (int64_t)blk * set_tiles) * TILE;
+        const int tile_n = seg_end - start < TILE ? seg_end - start : TILE;
+        const bool busy = g * EPW < tile_n, first = ti == 0;
+        const float* obs = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.obs) + (int64_t)blk * bw.x_block_bytes);
+        const float* dy = reinterpret_cast<const float*>(reinterpret_cast<const char*>(bw.dy) + (int64_t)blk * bw.dy_block_bytes) + (size_t)start * wl;
+        __syncthreads();                                        // the tile before this one has been read
+        for (int idx = t; idx < TILE * wl; idx += FTL_MLP_THREADS) {
+            const int r = idx / wl;
+            dyb[r * DS + (idx - r * wl)] = r < tile_n ? dy[idx] : 0.0f;
+        }
+        // the hidden layers, as mlp_body computes them
+        for (int l = 0; l + 1 < L; l++) {
+            const int w_in = a.width[l], w_out = a.width[l + 1], nblk = (w_out + NB - 1) / NB;
+            const float* W = P + off[l];
+            const float* bias = W + (size_t)w_in * w_out;
+            float* out = hb + l * TILE * AS;
+            f32x4 acc[BPW];
+#pragma unroll
+            for (int mm = 0; mm < BPW; mm++) {
+                const int j = (par + PARITIES * mm) * NB + li;
+                const float b = j < w_out ? bias[j] : 0.0f;
+                acc[mm] = f32x4{b, b, b, b};
+            }
+            const int kc = chunk_rows(w_out), wsf = fwd_stride(w_out);
+            const int xstride = l == 0 ? XS : AS;
+            for (int k0 = 0; k0 < w_in; k0 += kc) {
+                const int kn = w_in - k0 < kc ? w_in - k0 : kc;
+                __syncthreads();
+                stage_rows(ws, wsf, W + (size_t)k0 * w_out, kn, w_out, t);
+                if (l == 0) {
+                    const int e = t >> 3;
+                    if (e < tile_n) {
+                        const size_t row = (size_t)(start + e) * w0 + k0;
+                        for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = obs[row + kk];
+                    }
+                }
+                __syncthreads();
+                if (!busy) continue;
+                const float* x = l == 0 ? xs : hb + (l - 1) * TILE * AS + k0;
+                const float* xa = x + row_a * xstride + lk;
+                const float* xd = x + row_d * xstride;
+                int kk = 0;
+                for (; kk + 4 <= kn; kk += 4) {
+                    const float av = xa[kk];
+                    const float* wrow = ws + (kk + lk) * wsf + li;
+#pragma unroll
+                    for (int mm = 0; mm < BPW; mm++) {
+                        const int jb = par + PARITIES * mm;
+                        if (jb < nblk) acc[mm] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wrow[jb * NB], acc[mm], 0, 0, 0);
+                    }
+                }
+                for (; kk < kn; kk++) {
+#pragma unroll
+                    for (int mm = 0; mm < BPW; mm++) {
+                        const int jb = par + PARITIES * mm;
+                        if (jb >= nblk) continue;
+                        const float w = ws[kk * wsf + jb * NB + li];
+#pragma unroll
+                        for (int r = 0; r < 4; r++) acc[mm][r] = __builtin_fmaf(xd[r * xstride + kk], w, acc[mm][r]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int mm = 0; mm < BPW; mm++) {
+                const int j = (par + PARITIES * mm) * NB + li;
+                if (j >= w_out) continue;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const float v = acc[mm][r];
+                    out[(row_d + r) * AS + j] = ACT == FTL_MLP_ACT_TANH ? ftlrnnmath::tanh32(v) : (v > 0.0f ? v : 0.0f);
+                }
+            }
+            if (t < TILE) out[t * AS + w_out] = 1.0f;            // the bias's input
+        }
+        // the gradients, from the head down
+        for (int l = L; l >= 1; l--) {
+            const int w_in = a.width[l - 1], w_out = a.width[l];
+            const float* delta = hb + (l - 1) * TILE * AS;      // dy for l == L
+            const int dst = l == L ? DS : AS;
+            float* Gl = G + off[l - 1];
+            if (l == 1) {
+                for (int k0 = 0; k0 < w0 + 1; k0 += KC) {
+                    const int kn = w0 + 1 - k0 < KC ? w0 + 1 - k0 : KC;
+                    __syncthreads();
+                    const int e = t >> 3;
+                    if (e < tile_n) {
+                        const size_t row = (size_t)(start + e) * w0;
+                        for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = k0 + kk < w0 ? obs[row + k0 + kk] : 1.0f;
+                    }
+                    __syncthreads();
+                    dw_blocks(xs, XS, k0, kn, delta, dst, w_out, Gl, first, tile_n, wave, li, lk);
+                }
+                break;
+            }
+            float* hprev = hb + (l - 2) * TILE * AS;            // h_{l-1}, with its 1.0 in column w_in
+            __syncthreads();
+            dw_blocks(hprev, AS, 0, w_in + 1, delta, dst, w_out, Gl, first, tile_n, wave, li, lk);
+            // delta_{l-1}[r][k] = (the chain over j of W_l[k][j] * delta_l[r][j]) * act'(h_{l-1}[r][k]), in place of h_{l-1}
+            const float* W = P + off[l - 1];
+            const int kc = chunk_rows(w_out), wst = bwd_stride(w_out);
+            for (int k0 = 0; k0 < w_in; k0 += kc) {
+                const int kn = w_in - k0 < kc ? w_in - k0 : kc, nkb = (kn + NB - 1) / NB;
+                __syncthreads();
+                stage_rows(ws, wst, W + (size_t)k0 * w_out, kn, w_out, t);
+                __syncthreads();
+                if (!busy) continue;
+                f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+                const float* wr[2];
+#pragma unroll
+                for (int mm = 0; mm < 2; mm++) {
+                    const int k = (par + PARITIES * mm) * NB + li;
+                    wr[mm] = ws + (k < kn ? k : kn - 1) * wst;
+                }
+                int j = 0;
+                for (; j + 4 <= w_out; j += 4) {
+                    const float av = delta[row_a * dst + j + lk];
+#pragma unroll
+                    for (int mm = 0; mm < 2; mm++)
+                        if (par + PARITIES * mm < nkb) acc[mm] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wr[mm][j + lk], acc[mm], 0, 0, 0);
+                }
+                for (; j < w_out; j++) {
+#pragma unroll
+                    for (int mm = 0; mm < 2; mm++) {
+                        if (par + PARITIES * mm >= nkb) continue;
+                        const float w = wr[mm][j];
+#pragma unroll
+                        for (int r = 0; r < 4; r++) acc[mm][r] = __builtin_fmaf(w, delta[(row_d + r) * dst + j], acc[mm][r]);
+                    }
+                }
+#pragma unroll
+                for (int mm = 0; mm < 2; mm++) {
+                    const int k = (par + PARITIES * mm) * NB + li;
+                    if (k >= kn) continue;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        float* p = hprev + (row_d + r) * AS + k0 + k;
+                        const float h = *p, v = acc[mm][r];
+                        if (ACT == FTL_MLP_ACT_TANH) *p = v * __builtin_fmaf(-h, h, 1.0f);
+                        else *p = h > 0.0f ? v : 0.0f;
+                    }
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(FTL_MLP_THREADS, 3) void ftl_mlp_backward_kernel(const Args a, const Backward bw) { mlp_bwd_body<FTL_MLP_ACT_RELU>(a, bw); }
+
+__global__ __launch_bounds__(FTL_MLP_THREADS, 3) void ftl_mlp_backward_tanh_kernel(const Args a, const Backward bw) { mlp_bwd_body<FTL_MLP_ACT_TANH>(a, bw); }
+
+// grad[set][w] = the float64 sum of the set's span partials in ascending span order, rounded once; blockIdx.x the touched set
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_mlp_backward_reduce_kernel(const Reduce rd) {
+    const int64_t w = (int64_t)blockIdx.y * FTL_MLP_THREADS + threadIdx.x;
+    if (w >= rd.count) return;
+    const int m = (int)blockIdx.x;
+    const int n = m == 0 ? rd.spans0 : m == rd.n_touched - 1 ? rd.spans_last : rd.spans_mid;
+    const int64_t base = m == 0 ? 0 : (int64_t)rd.spans0 + (int64_t)(m - 1) * rd.spans_mid;
+    const float* p = rd.ws + base * rd.count + w;
+    double s = 0.0;
+    for (int j = 0; j < n; j++) s += (double)p[(int64_t)j * rd.count];
+    rd.grad[(int64_t)(rd.set0 + m) * rd.set_stride + w] = (float)s;
+}
+
 }  // namespace ftlmlp
 
 // floats of one weight set; -1 outside the limits of include/ftl.h
@@ -356,6 +642,22 @@ static int mlp_sample_check(const char* name, int32_t head, const float* noise, 
     return FTL_OK;
 }
 
+// the spans of ftl_mlp_backward for a checked net and its rows: those of the first touched set, of a whole set and of the last touched
+// set (0 when the first is the only one), the touched sets and the sum; false when the sum leaves the grid
+struct MlpBwdPlan { int64_t spans0, spans_mid, spans_last, n_touched, spans; };
+static MlpBwdPlan mlp_bwd_plan(const ftl_mlp* net, int64_t n_blocks, int64_t n) {
+    const int64_t eps = net->envs_per_set, first = net->env_first, tile = FTL_MLP_ENV_TILE, span = FTL_MLP_BWD_SPAN;
+    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0, full = rem / eps, last = rem % eps;
+    auto spans_of = [&](int64_t rows) { return (n_blocks * ((rows + tile - 1) / tile) + span - 1) / span; };
+    MlpBwdPlan p;
+    p.spans0 = spans_of(len0);
+    p.spans_mid = rem ? spans_of(eps) : 1;
+    p.spans_last = !rem ? 0 : last ? spans_of(last) : p.spans_mid;
+    p.n_touched = 1 + full + (last ? 1 : 0);
+    p.spans = p.spans0 + full * p.spans_mid + (last ? p.spans_last : 0);
+    return p;
+}
+
 extern "C" {
 
 size_t ftl_sizeof_mlp(void) { return sizeof(ftl_mlp); }
@@ -440,6 +742,69 @@ int ftl_mlp_forward(const ftl_handle* h, const ftl_mlp* net, int32_t n_blocks, i
     const ftlmlp::Forward fw{x_block_bytes, y, y_block_bytes};
     hipLaunchKernelGGL(net->activation == FTL_MLP_ACT_TANH ? ftlmlp::ftl_mlp_forward_tanh_kernel : ftlmlp::ftl_mlp_forward_kernel,
                        dim3(grid, (unsigned)n_blocks), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, fw);
+    return launched();
+}
+
+int64_t ftl_sizeof_mlp_backward_workspace(const ftl_mlp* net, int32_t n_blocks, int32_t n) {
+    if (!net || n_blocks < 1 || n < 1 || net->envs_per_set < 1 || net->env_first < 0) return -1;
+    const int64_t count = mlp_param_count(net->width, net->n_layers);
+    if (count < 0) return -1;
+    return mlp_bwd_plan(net, n_blocks, n).spans * count * 4;
+}
+
+int ftl_mlp_backward(const ftl_handle* h, const ftl_mlp* net, int32_t n_blocks, int32_t n, const float* x, int64_t x_block_bytes,
+                     const float* dy, int64_t dy_block_bytes, float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!h) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: h");
+    if (!net) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: net");
+    if (!net->params) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: net->params");
+    if (!x) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: x");
+    if (!dy) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: dy");
+    if (!grad) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: grad");
+    if (!workspace) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: workspace");
+    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_mlp_backward: n_blocks and n must be at least 1");
+    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: n_blocks beyond 65,535 (the limit of ftl_mlp_forward)");
+    if (int rc = mlp_net_check(net, n, true, "the last row")) return rc;
+    if (net->width[0] > FTL_MLP_BWD_MAX_IN) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: input width beyond FTL_MLP_BWD_MAX_IN");
+    const int64_t w0 = net->width[0], wl = net->width[net->n_layers];
+    if (x_block_bytes < (int64_t)n * w0 * 4 || (x_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_mlp_backward: x_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
+    if (dy_block_bytes < (int64_t)n * wl * 4 || (dy_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_mlp_backward: dy_block_bytes must be a multiple of 4 of at least one block, n * width[L] * 4");
+    ftlmlp::Args a; unsigned grid; size_t lds;
+    mlp_fill(net, n, a, grid, lds);
+    const MlpBwdPlan p = mlp_bwd_plan(net, n_blocks, n);
+    if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull || (uint64_t)p.spans * FTL_MLP_THREADS > 0xFFFFFFFFull)
+        return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: n beyond the 2^24 - 1 tiles of a block, or beyond 2^24 - 1 spans in all; split the rows");
+    const int64_t count = mlp_param_count(net->width, net->n_layers);
+    if (workspace_bytes < p.spans * count * 4)
+        return fail(FTL_E_INVALID, "ftl_mlp_backward: workspace_bytes below ftl_sizeof_mlp_backward_workspace");
+    if (((uintptr_t)x) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: x must be 4-byte aligned");
+    if (((uintptr_t)dy) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: dy must be 4-byte aligned");
+    if (((uintptr_t)grad) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: grad must be 4-byte aligned");
+    if (((uintptr_t)workspace) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: workspace must be 4-byte aligned");
+    if (int rc = set_device(h)) return rc;
+    a.obs = x; a.head = 0; a.lo0 = a.hi0 = a.lo1 = a.hi1 = 0.0; a.action = nullptr;
+    // LDS: a buffer per hidden layer and one for dy, the input chunk and the weight stage (a chunk's rows at the wider of the two strides)
+    size_t stage = 0;
+    for (int l = 1; l <= net->n_layers; l++) {
+        const int w = net->width[l];
+        stage = std::max(stage, (size_t)ftlmlp::chunk_rows(w) * std::max(ftlmlp::fwd_stride(w), ftlmlp::bwd_stride(w)));
+    }
+    lds = ((size_t)(net->n_layers - 1) * FTL_MLP_ENV_TILE * a.act_stride + (size_t)FTL_MLP_ENV_TILE * (ftlmlp::dy_stride((int)wl) + ftlmlp::XS) + stage) * sizeof(float);
+    if (lds > 163840) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: the net needs more than the 160 KB of LDS of a workgroup");
+    const bool th = net->activation == FTL_MLP_ACT_TANH;
+    if (lds > 65536) {                                          // (beyond the default limit of dynamic LDS)
+        hipError_t e = hipFuncSetAttribute(th ? (const void*)ftlmlp::ftl_mlp_backward_tanh_kernel : (const void*)ftlmlp::ftl_mlp_backward_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipFuncSetAttribute(ftl_mlp_backward_kernel): ") + hipGetErrorString(e));
+    }
+    const ftlmlp::Backward bw{x_block_bytes, dy, dy_block_bytes, static_cast<float*>(workspace), count, n_blocks, (int32_t)p.spans0, (int32_t)p.spans_mid};
+    hipLaunchKernelGGL(th ? ftlmlp::ftl_mlp_backward_tanh_kernel : ftlmlp::ftl_mlp_backward_kernel,
+                       dim3((unsigned)p.spans), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, bw);
+    const ftlmlp::Reduce rd{static_cast<const float*>(workspace), grad, count, net->set_stride, (int32_t)(net->env_first / net->envs_per_set),
+                            (int32_t)p.n_touched, (int32_t)p.spans0, (int32_t)p.spans_mid, (int32_t)p.spans_last};
+    hipLaunchKernelGGL(ftlmlp::ftl_mlp_backward_reduce_kernel, dim3((unsigned)p.n_touched, (unsigned)((count + FTL_MLP_THREADS - 1) / FTL_MLP_THREADS)),
+                       dim3(FTL_MLP_THREADS), 0, (hipStream_t)stream, rd);
     return launched();
 }
 

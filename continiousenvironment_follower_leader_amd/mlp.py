@@ -10,7 +10,10 @@ For a gradient method (the reference trains with PPO) ``sample()`` adds the call
 ``batch.collect_mlp`` play T such decisions through episode boundaries with one call and leave a ``Trajectory`` on the device
 (``ftl_collect_mlp``), and ``gae()`` turns its rewards and kinds and a critic's values into advantages (``ftl_gae``).  ``forward()`` evaluates a net on
 recorded rows with the same arithmetic (``ftl_mlp_forward``): ``Critic`` is a head-1 net whose ``values(traj.obs)`` feed ``gae()``, and
-``policy.forward(traj.obs[:-1])`` replays ``traj.head`` bit for bit.  The backward pass is torch autograd on the recorded tensors."""
+``policy.forward(traj.obs[:-1])`` replays ``traj.head`` bit for bit.  ``backward()`` is its derivative with respect to the weights
+(``ftl_mlp_backward``), per set and in a fixed summation order, and ``Net`` ties the two together under torch autograd: an ``nn.Module``
+whose one parameter can share storage with ``policy.params`` or ``critic.params``, so one optimizer trains what the device plays.  The
+recurrent net (``rnn.py``) has no such backward pass: its loss lines stay with torch autograd on a torch module."""
 import ctypes as C
 import functools
 
@@ -324,6 +327,143 @@ class Critic:
         if not 0 <= int(s) < self.n_sets:
             raise IndexError("set %d of %d" % (int(s), self.n_sets))
         return torch_module(self.widths, self.activation, self.params[int(s)])
+
+
+_BWD_WORKSPACE = {}
+
+
+def _net_struct(widths, params, n_sets, N, activation):
+    net = abi.Mlp()
+    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), abi.mlp_param_count(widths), n_sets, len(widths) - 1
+    for l, w in enumerate(widths):
+        net.width[l] = w
+    net.env_first, net.envs_per_set, net.activation = 0, N // n_sets, ACTIVATIONS[activation]
+    return net
+
+
+def backward(widths, params, x, dy, activation="relu", out=None):
+    """``d loss / d params`` of ``n_sets`` nets of shape ``widths`` on the rows ``forward`` evaluates, in one call on the current stream
+    (``ftl_mlp_backward``: a kernel that recomputes the hidden layers per tile and a small reduction): ``params`` and ``x`` are
+    ``forward``'s; ``dy`` is the gradient of a scalar loss with respect to the raw head of every row, a contiguous float32
+    ``[..., N, widths[-1]]`` tensor of ``x``'s leading shape on its device, zeros on the rows to leave out (``~traj.valid``).  Returns
+    float32 ``[n_sets, param_count]`` in the layout of ``params`` -- overwritten, not accumulated; ``out=`` reuses such a buffer.
+
+    The arithmetic is fixed operation by operation (include/ftl.h; tests/mlp_backward_numpy.py is the twin): the forward values are
+    ``forward``'s bits, the sums over rows run in a fixed order -- spans of ``abi.FTL_MLP_BWD_SPAN`` tiles, float32 chains inside, float64
+    across -- so the result does not depend on the machine or the launch, and no hidden activation reaches global memory.  The span
+    partials go through a workspace tensor cached per device and stream.  There is no gradient with respect to ``x``.
+    ``ValueError`` / ``NotImplementedError`` as ``forward``, before any library call."""
+    widths = check_net_widths(widths)
+    check_activation(activation)
+    count = abi.mlp_param_count(widths)
+    if widths[0] > abi.FTL_MLP_BWD_MAX_IN:
+        raise NotImplementedError("at most %d inputs in backward()" % abi.FTL_MLP_BWD_MAX_IN)
+    if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == count
+            and params.shape[0] >= 1 and params.is_contiguous()):
+        raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor" % count)
+    n_sets = int(params.shape[0])
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-1] == widths[0] and x.is_contiguous()):
+        raise ValueError("x must be a contiguous float32 [..., N, %d] tensor" % widths[0])
+    if x.requires_grad:
+        raise ValueError("backward() has no gradient with respect to x: pass a detached tensor")
+    lead, N = tuple(x.shape[:-2]), int(x.shape[-2])
+    blocks = 1
+    for d in lead:
+        blocks *= int(d)
+    if N < 1 or blocks < 1:
+        raise ValueError("x must hold at least one block of at least one row, not %s" % (list(x.shape),))
+    if N % n_sets:
+        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
+    if blocks > FORWARD_MAX_BLOCKS:
+        raise NotImplementedError("at most %d blocks in one call, not %d" % (FORWARD_MAX_BLOCKS, blocks))
+    shape = lead + (N, widths[-1])
+    if not (torch.is_tensor(dy) and dy.dtype == torch.float32 and tuple(dy.shape) == shape and dy.is_contiguous() and dy.device == x.device
+            and not dy.requires_grad):
+        raise ValueError("dy must be a detached contiguous float32 %s tensor on x's device" % (list(shape),))
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (n_sets, count)
+                                and out.is_contiguous() and out.device == x.device and not out.requires_grad):
+        raise ValueError("out must be a contiguous float32 [%d, %d] tensor on x's device" % (n_sets, count))
+    if not x.is_cuda or params.device != x.device:
+        raise ValueError("x and params must lie on the same GPU device")
+    if out is None:
+        out = torch.empty(n_sets, count, dtype=torch.float32, device=x.device)
+    net = _net_struct(widths, params.detach(), n_sets, N, activation)
+    lib = _lib.load()
+    h = _device_handle(x.device)
+    need = lib.ftl_sizeof_mlp_backward_workspace(C.byref(net), blocks, N)
+    if need < 0:
+        raise _lib.FtlError("ftl_sizeof_mlp_backward_workspace refused a net that the package's checks passed")
+    raw = torch.cuda.current_stream(x.device).cuda_stream
+    key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), raw)
+    ws = _BWD_WORKSPACE.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = _BWD_WORKSPACE[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+    _lib.check(lib.ftl_mlp_backward(h, C.byref(net), blocks, N, x.data_ptr(), N * widths[0] * 4, dy.data_ptr(), N * widths[-1] * 4,
+                                    out.data_ptr(), ws.data_ptr(), ws.numel() * 4, C.c_void_p(raw)), lib)
+    return out
+
+
+class _NetFunction(torch.autograd.Function):
+    """``forward`` with ``backward`` as its derivative with respect to ``params``."""
+
+    @staticmethod
+    def forward(ctx, params, x, widths, activation):
+        ctx.save_for_backward(params, x)
+        ctx.widths, ctx.activation = widths, activation
+        return forward(widths, params.detach(), x, activation)
+
+    @staticmethod
+    def backward(ctx, dy):
+        params, x = ctx.saved_tensors
+        return backward(ctx.widths, params.detach(), x, dy.detach().contiguous(), ctx.activation), None, None, None
+
+
+class Net(torch.nn.Module):
+    """A trainable net on the device, or a population of ``n_sets`` of them: ``Net(widths, n_sets=1, activation="relu", params=None,
+    device=None)`` is an ``nn.Module`` whose one ``nn.Parameter`` ``params`` is the float32 ``[n_sets, param_count]`` tensor of all weights
+    in the layout of ``ftl_mlp`` (zeros on ``device``, the current GPU by default, unless given).  ``params=policy.params`` or
+    ``params=critic.params`` shares storage: an optimizer step on ``net.params`` is what the policy plays next, with no copy.
+
+    ``net(x)`` is ``forward`` on ``x`` float32 ``[..., N, widths[0]]`` (``n_sets`` must divide N; ``x`` must not require grad) under
+    autograd: its derivative is ``backward``, so ``loss.backward()`` leaves ``d loss / d params`` in ``net.params.grad`` with the pinned
+    arithmetic of include/ftl.h, for one net as for 1,024, without a hidden activation in global memory.  ``load`` / ``module`` move
+    weights to and from a ``torch.nn.Sequential`` as on ``Critic``."""
+
+    def __init__(self, widths, n_sets=1, activation="relu", params=None, device=None):
+        super().__init__()
+        self.widths = check_net_widths(widths)
+        self.activation = check_activation(activation)
+        self.n_sets, self.param_count = int(n_sets), abi.mlp_param_count(self.widths)
+        if self.n_sets < 1:
+            raise ValueError("n_sets must be at least 1")
+        if params is None:
+            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
+        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
+                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
+            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the net's device" % self.param_count)
+        self.params = torch.nn.Parameter(params.detach())       # (the parameter shares the tensor's storage)
+
+    def forward(self, x):
+        if torch.is_tensor(x) and x.requires_grad:
+            raise ValueError("x must not require grad: there is no gradient with respect to the rows")
+        return _NetFunction.apply(self.params, x, self.widths, self.activation)
+
+    def load(self, module, s=None):
+        """Copy the weights of a torch module (``params_from_torch``) into set ``s``, or into every set (``s=None``).  Returns ``self``."""
+        widths, activation, row = params_from_torch(module)
+        if widths != self.widths or (len(widths) > 2 and activation != self.activation):
+            raise ValueError("the module is a %s %s net, this one a %s %s one" % (activation, widths, self.activation, self.widths))
+        if s is not None and not 0 <= int(s) < self.n_sets:
+            raise IndexError("set %d of %d" % (int(s), self.n_sets))
+        with torch.no_grad():
+            (self.params if s is None else self.params[int(s)]).copy_(row)
+        return self
+
+    def module(self, s=0):
+        """A new ``torch.nn.Sequential`` on the CPU with the weights of set ``s`` (``torch_module``)."""
+        if not 0 <= int(s) < self.n_sets:
+            raise IndexError("set %d of %d" % (int(s), self.n_sets))
+        return torch_module(self.widths, self.activation, self.params.detach()[int(s)])
 
 
 class MlpPolicy:

@@ -1020,6 +1020,57 @@ int ftl_mlp_forward(const ftl_handle* h /* device only, as ftl_gae */, const ftl
                     float* y, int64_t y_block_bytes,         /* block b: [n][width[L]] f32 at y + b * y_block_bytes */
                     void* stream);
 
+/* ---- the backward pass of the net on recorded rows: d loss / d params of an ftl_mlp, per weight set, with pinned arithmetic -----------
+ * ftl_mlp_backward (ftl_mlp_backward_kernel / ftl_mlp_backward_tanh_kernel and ftl_mlp_backward_reduce_kernel, csrc/ftl_mlp.hpp: two
+ * launches on `stream`, asynchronous; the handle only names the device) is ftl_mlp_forward's counterpart: h, net, n_blocks, n, x and
+ * x_block_bytes mean what they mean there, the weight-set rule (env_first + r) / envs_per_set included.  dy is the caller's gradient of a
+ * scalar loss with respect to the raw head of every row, float32 [n][width[L]] per block at (char*)dy + b * dy_block_bytes; rows to leave
+ * out (FTL_TR_VOID steps) carry zeros there.  grad receives d loss / d params, float32 [net->n_sets][set_stride] in the layout of params
+ * (W_l as [in][out], then b_l): every parameter word of every set that the rows touch is OVERWRITTEN, not accumulated; the words of
+ * untouched sets and the padding between ftl_mlp_param_count and set_stride are not written.  There is no dx: observations are data.
+ *   Contract    the result is a pure function of the arguments: no atomics, no dependence on the machine, the grid or timing.  tests/
+ *               mlp_backward_numpy.py is the twin, and the device is pinned to it bit for bit.  Per row r (fmaf: one rounding):
+ *                 forward   h_0 = x; the hidden layers h_l, l < L, exactly as ftl_mlp_forward computes them (the head is not needed).
+ *                 delta_L   = dy.
+ *                 delta_l   for l = L-1 .. 1: c[k] = the fmaf chain over j = 0 .. width[l+1]-1 ascending, from +0, of
+ *                           W_{l+1}[k][j] * delta_{l+1}[r][j]; then FTL_MLP_ACT_RELU: delta_l[r][k] = h_l[r][k] > 0 ? c[k] : +0 (the forward
+ *                           select kept the value: acc > 0); FTL_MLP_ACT_TANH: delta_l[r][k] = c[k] * d in float32 with
+ *                           d = fmaf(-a, a, 1.0f), a = h_l[r][k] = tanh32(acc).
+ *               and per set, for every layer l = 1 .. L, dW_l[k][j] = sum_r h_{l-1}[r][k] * delta_l[r][j] and db_l[j] = sum_r 1.0f *
+ *               delta_l[r][j] -- the bias is row width[l-1] of the layer's [width[l-1] + 1][width[l]] matrix, its input a constant 1.0f --
+ *               summed in this order:
+ *                 tiles     the set's tiles are those of ftl_mlp_forward (runs of up to FTL_MLP_ENV_TILE = 32 rows of a block that end at
+ *                           the set's last row of the block), enumerated block-major: all tiles of block 0 ascending, then block 1, ...
+ *                 spans     consecutive runs of FTL_MLP_BWD_SPAN tiles of that enumeration (the last span of a set may be shorter).
+ *                 partial   a span's partial of a word is the fmaf chain from +0 over its tiles ascending and, inside a tile, over 32 row
+ *                           slots ascending: acc = fmaf(h_{l-1}[r][k], delta_l[r][j], acc).
+ *                 cut tiles a tile of fewer than 32 rows still has 32 slots: in the slots past its end both factors are +0 (the 1.0f of
+ *                           the bias too), so each contributes fmaf(+0, +0, acc) -- which turns an acc of -0 into +0 and changes nothing
+ *                           else.  A short last span has no slots for the tiles it lacks.
+ *                 reduce    grad word = (float)(the float64 sum, from +0.0, of the partials as float64 in ascending span order): float64
+ *                           additions, one rounding to float32 at the end.
+ *               FTL_MLP_BWD_SPAN, the slot rule and the reduction are constants of this header, not properties of a device or a launch.
+ *   Workspace   ftl_sizeof_mlp_backward_workspace(net, n_blocks, n) bytes of device memory, 4-byte aligned, contents irrelevant before
+ *               and undefined after: spans * ftl_mlp_param_count * 4, spans = the sum over the touched sets of
+ *               ceil(n_blocks * ceil(rows of the set in a block / 32) / FTL_MLP_BWD_SPAN).  Pure host arithmetic; -1 for a NULL net,
+ *               counts below 1, envs_per_set < 1, env_first < 0 or widths outside the limits.
+ *   Limits      those of ftl_mlp_forward (layers, widths, n_blocks, tiles of a block), width[0] at most FTL_MLP_BWD_MAX_IN, and at most
+ *               2^24 - 1 spans in all: beyond any, FTL_E_UNSUPPORTED before any device work.
+ *   Aliasing    grad and workspace must not overlap x, dy, params or each other (not checked).
+ *   FTL_E_INVALID before any device work, each with a message that names the argument: NULL h, net, net->params, x, dy, grad or workspace;
+ *   n_blocks < 1 or n < 1; what ftl_mlp_forward refuses of the net itself, with its messages; x_block_bytes below n * width[0] * 4 or
+ *   dy_block_bytes below n * width[L] * 4, or either not a multiple of 4; workspace_bytes below the query's answer; x, dy, grad or
+ *   workspace not 4-byte aligned. */
+#define FTL_MLP_BWD_SPAN 64            /* tiles of a span: 2,048 row slots in one float32 chain */
+#define FTL_MLP_BWD_MAX_IN FTL_MLP_MAX_IN
+int64_t ftl_sizeof_mlp_backward_workspace(const ftl_mlp* net, int32_t n_blocks, int32_t n);
+int ftl_mlp_backward(const ftl_handle* h /* device only */, const ftl_mlp* net,
+                     int32_t n_blocks, int32_t n,
+                     const float* x, int64_t x_block_bytes,    /* block b: [n][width[0]] f32 at x + b * x_block_bytes */
+                     const float* dy, int64_t dy_block_bytes,  /* block b: [n][width[L]] f32 at dy + b * dy_block_bytes */
+                     float* grad,                              /* [n_sets][set_stride] f32, the layout of params */
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- recurrent policy: a trunk of dense ReLU layers, one LSTM cell and a linear head, as a decision, a rollout and a trajectory -------
  * The memoryless stack above (ftl_mlp_act, ftl_rollout_mlp, ftl_mlp_sample, ftl_collect_mlp) with a state per env that the caller owns
  * and the library zeroes at episode boundaries.  ftl_rnn_act (ftl_rnn_kernel, csrc/ftl_rnn.hpp, one launch per decision, asynchronous on
