@@ -312,6 +312,33 @@ class RnnSequence(C.Structure):
                 ("state_out", C.c_void_p), ("state_at", C.c_int32)]
 
 
+FTL_RNN_BWD_SPAN = 64                 # ftl_rnn_backward: (tile, block) pairs of a span
+
+
+def rnn_backward_lds_bytes(widths, cell, flags):
+    """LDS bytes of a workgroup of ftl_rnn_backward_kernel (the Limits line of the ``ftl_rnn_backward`` block of include/ftl.h): the
+    trunk's hidden buffers, u, dh, the weight stage, and the region that is xs | h' | dy before the gate passes and dz from then on."""
+    Lt, A, cell = len(widths) - 2, int(widths[-1]), int(cell)
+    U = rnn_widths(widths, cell, flags)[2]
+    r32 = lambda w: ((int(w) + 31) & ~31) + 2
+    act, us, hs = r32(max([A] + [int(w) for w in widths[1:Lt]])), r32(U), r32(cell)
+    cn = min(cell, FTL_RNN_PASS_CELLS)
+    products = [int(w) for w in widths[1:Lt + 1]] + [4 * cn] + ([4 * (cell - cn)] if cell > cn and cell % cn else [])
+    stage = max([FTL_MLP_W_STAGE + 64] + [mlp_chunk_rows(w) * (((w + 27) & ~31) + 4) for w in products])
+    region = max(4 * cn + 2, FTL_MLP_K_CHUNK + 2 + hs + r32(A))
+    return 4 * (FTL_MLP_ENV_TILE * ((Lt - 1) * act + us + hs + region) + stage)
+
+
+FTL_RNN_BWD_MAX_LDS = 160 * 1024      # ftl_rnn_backward: a net whose workgroup needs more is FTL_E_UNSUPPORTED
+
+
+class RnnGradient(C.Structure):
+    """ftl_rnn_gradient: what ``ftl_rnn_backward`` takes beside the sequence -- the head gradients of every block, where the parameter
+    gradient goes, the workspace, and the optional gradients of the state after the last block (in) and before the first (out)."""
+    _fields_ = [("dhead", C.c_void_p), ("dhead_block_bytes", C.c_int64), ("grad", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("dstate_in", C.c_void_p), ("dstate_out", C.c_void_p)]
+
+
 class RnnCollectBuffers(C.Structure):
     """ftl_rnn_collect_buffers: ``CollectBuffers`` plus where the state rows every decision read are recorded."""
     _fields_ = [("b", CollectBuffers), ("state", C.c_void_p), ("state_step_bytes", C.c_int64), ("state_steps", C.c_int32), ("_pad", C.c_int32)]

@@ -476,6 +476,430 @@ __global__ __launch_bounds__(FTL_MLP_THREADS, 2) void ftl_rnn_forward_kernel(con
     }
 }
 
+// ---- ftl_rnn_backward: d loss / d params of the net on a recorded sequence (include/ftl.h: ftl_rnn_backward) ----
+// ONE workgroup per GROUP of G = max(1, 64 / B) consecutive tiles of a set (the tile map of ftl_rnn_forward), the tiles one after the
+// other, so the carry of back-propagation through time never leaves the workgroup.  Per tile: a forward sweep over the B blocks with the
+// layers of ftl_rnn_forward_kernel (dense, layer_acc, gate_col: the same chains, the same bits) leaves h' and c' of every block in the
+// record part of the workspace; then the blocks run DESCENDING.  A block of the reverse sweep recomputes the trunk (every hidden
+// activation kept in LDS with a 1.0 in the bias's column) and u, takes dW_y and dh from dy, recomputes the gates pass by pass -- z in the
+// registers of the lane that owns the cell, as in the forward, and dc_next with it --, writes the pass's dz to LDS, advances dW_g by
+// u^T dz and du by dz W_g^T (both on the MFMA), and finishes with the trunk as ftl_mlp_backward does.  du of a cell with two passes
+// travels between them through the group's carry rows in the workspace, every lane its own words.  The running partial of a span lives in
+// the span's slice of the workspace as in ftl_mlp_backward_kernel; ftl_mlp_backward_reduce_kernel sums the spans.
+// LDS: the hidden buffers, u, dh, the weight stage, and one region that is xs | h' | dy before the gate passes and dz from then on.
+struct Bwd {
+    ftlmlp::Args m;            // the trunk and the tile map over the n rows of a block; m.obs is block 0 of obs
+    int32_t cell, P, R, A;
+    int32_t u_stride, h_stride, dz_stride, stage;               // floats; stage: of the weight stage
+    int32_t n_blocks, G, spg;                                   // tiles of a group, spans of a whole group
+    int32_t groups0, groups_mid, spans0, spans_mid;             // of the first touched set and of a whole set
+    const float* state; int64_t state_stride;
+    int64_t obs_bb, action_bb, reward_bb, kind_bb, dy_bb;
+    const void* action; const double* reward; const uint8_t* kind; const double* reward0;
+    const float* dy; const float* dstate_in; float* dstate_out;
+    float* part; int64_t count;                                 // the span partials, [spans][count]
+    float* rec;                                                 // [B][n][2C]: h' | c' of every block, before any wipe
+    float* carry;                                               // [groups][TILE][U]
+};
+
+// column j of a product -> word (j / cn) * C + j0 + j % cn of a matrix row: the pass's columns of W_g; cn = w_out, j0 = 0: the identity
+struct ColMap { int cn, C, j0; };
+__device__ __forceinline__ int map_col(const ColMap& cm, int j) { const int q = j / cm.cn; return q * cm.C + cm.j0 + (j - q * cm.cn); }
+
+// ftlmlp::dw_blocks with the column map: G[(k0 + k) * ldg + map_col(j)] += the chain over the tile's 32 row slots of src[row][k] * delta[row][j]
+__device__ __forceinline__ void dw_map(const float* src, int sstride, int k0, int kn, const float* delta, int dstride, int w_out,
+                                       float* G, int ldg, const ColMap cm, bool first, int tile_n, int wave, int li, int lk) {
+    constexpr int DWB = ftlmlp::DWB, WAVES = ftlmlp::WAVES;
+    const int nkb = (kn + NB - 1) / NB, njb = (w_out + NB - 1) / NB, total = nkb * njb;
+    for (int q0 = wave * DWB; q0 < total; q0 += WAVES * DWB) {
+        f32x4 c[DWB];
+        int kb[DWB], jb[DWB], gc[DWB];
+#pragma unroll
+        for (int v = 0; v < DWB; v++) {
+            const int q = q0 + v < total ? q0 + v : total - 1;
+            kb[v] = q / njb; jb[v] = q - kb[v] * njb;
+            const int j = jb[v] * NB + li;
+            gc[v] = map_col(cm, j < w_out ? j : w_out - 1);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int k = kb[v] * NB + 4 * lk + r;
+                c[v][r] = (!first && q0 + v < total && k < kn && j < w_out) ? G[(size_t)(k0 + k) * ldg + gc[v]] : 0.0f;
+            }
+        }
+        for (int rr = 0; rr < TILE; rr += 4) {
+            const int row = rr + lk;
+            const bool live = row < tile_n;
+#pragma unroll
+            for (int v = 0; v < DWB; v++) {
+                if (q0 + v >= total) continue;                  // (wave-uniform)
+                const int k = kb[v] * NB + li, j = jb[v] * NB + li;
+                const float av = (live && k < kn) ? src[row * sstride + k] : 0.0f;
+                const float bv = (live && j < w_out) ? delta[row * dstride + j] : 0.0f;
+                c[v] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, c[v], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < DWB; v++) {
+            if (q0 + v >= total) continue;
+            const int j = jb[v] * NB + li;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int k = kb[v] * NB + 4 * lk + r;
+                if (k < kn && j < w_out) G[(size_t)(k0 + k) * ldg + gc[v]] = c[v][r];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(FTL_MLP_THREADS) void ftl_rnn_backward_kernel(const Bwd a) {
+    extern __shared__ float4 rnn_bwd_lds[];
+    const ftlmlp::Args& m = a.m;
+    const int Lt = m.n_layers, C = a.cell, AS = m.act_stride, wx = m.width[Lt], tail = a.P + a.R + C, U = wx + tail, A = a.A, B = a.n_blocks;
+    const int US = a.u_stride, HS = a.h_stride, ZS = a.dz_stride, DS = ftlmlp::dy_stride(A), w0 = m.width[0];
+    float* hb = reinterpret_cast<float*>(rnn_bwd_lds);          // [Lt - 1][TILE][AS]: h_l of the trunk, then delta_l
+    float* u = hb + (Lt - 1) * TILE * AS;                       // [TILE][US]: u and its 1.0; the x columns become delta_Lt
+    float* dhb = u + TILE * US;                                 // [TILE][HS]: dh_next, then dh
+    float* ws = dhb + TILE * HS;                                // the weight stage
+    float* dzp = ws + a.stage;                                  // [TILE][ZS]: dz of a gate pass; before the passes:
+    float* xs = dzp;                                            //   [TILE][XS]
+    float* hn = xs + TILE * XS;                                 //   [TILE][HS]: h' of the block and its 1.0
+    float* dyb = hn + TILE * HS;                                //   [TILE][DS]
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, lk = lane >> 4;
+    const int g = wave % GROUPS, par = wave / GROUPS, row_a = g * EPW + li, row_d = g * EPW + 4 * lk;
+    // the group's set, its rows of a block and its tiles
+    int ms, gi;
+    if ((int)blockIdx.x < a.groups0) { ms = 0; gi = (int)blockIdx.x; }
+    else { const int q = (int)blockIdx.x - a.groups0; ms = 1 + q / a.groups_mid; gi = q % a.groups_mid; }
+    const int set = m.env_first / m.envs_per_set + ms;
+    int seg, seg_end;
+    if (ms == 0) { seg = 0; seg_end = m.len0; }
+    else {
+        const int64_t s0 = (int64_t)m.len0 + (int64_t)(ms - 1) * m.envs_per_set, s1 = s0 + m.envs_per_set;
+        seg = (int)s0; seg_end = s1 < (int64_t)m.n_envs ? (int)s1 : m.n_envs;
+    }
+    const int set_tiles = (seg_end - seg + TILE - 1) / TILE, tile_lo = gi * a.G;
+    const int n_tiles = set_tiles - tile_lo < a.G ? set_tiles - tile_lo : a.G;
+    const int64_t span_base = (ms == 0 ? 0 : (int64_t)a.spans0 + (int64_t)(ms - 1) * a.spans_mid) + (int64_t)gi * a.spg;
+    float* carry = a.carry + (size_t)blockIdx.x * TILE * U;
+    const float* P0 = m.params + (int64_t)set * m.set_stride;
+    int off[FTL_MLP_MAX_LAYERS + 1];
+    off[0] = 0;
+#pragma unroll
+    for (int l = 0; l < FTL_MLP_MAX_LAYERS; l++) off[l + 1] = off[l] + (l < Lt ? (m.width[l] + 1) * m.width[l + 1] : 0);
+    const int o_g = off[Lt], o_y = o_g + (U + 1) * 4 * C;
+    const float* Wg = P0 + o_g;
+    const float* bg = Wg + (size_t)U * 4 * C;
+    const float* Wy = P0 + o_y;
+    const size_t rec_bb = (size_t)m.n_envs * 2 * C;             // floats between two blocks of the record
+    constexpr int PASSES = FTL_RNN_MAX_CELL / FTL_RNN_PASS_CELLS;
+    static_assert(PASSES == 2, "dc_next of a pass is selected between two register sets");
+
+    for (int ti = 0; ti < n_tiles; ti++) {
+        const int start = seg + (tile_lo + ti) * TILE;
+        const int tile_n = seg_end - start < TILE ? seg_end - start : TILE;
+        const bool busy = g * EPW < tile_n;
+        // the trunk of block b: h_l into hb (with the bias's 1.0), x into u
+        auto trunk = [&](int b) {
+            const float* obs = reinterpret_cast<const float*>(reinterpret_cast<const char*>(m.obs) + (int64_t)b * a.obs_bb);
+            const float* P = P0;
+            for (int l = 0; l < Lt; l++) {
+                const int w_in = m.width[l], w_out = m.width[l + 1];
+                const bool last = l + 1 == Lt;
+                dense(P, P + (size_t)w_in * w_out, w_in, w_out, l == 0 ? obs : nullptr, nullptr, start, tile_n,
+                      l == 0 ? nullptr : hb + (l - 1) * TILE * AS, AS, last ? u : hb + l * TILE * AS, last ? US : AS, true, xs, ws);
+                if (!last && t < TILE) hb[l * TILE * AS + t * AS + w_out] = 1.0f;
+                P += ((size_t)w_in + 1) * w_out;
+            }
+        };
+        // the rest of u for block b: a_prev | r_prev | h of the row it reads (the zero rule of ftl_rnn_forward), and the bias's 1.0
+        auto fill_tail = [&](int b) {
+            const uint8_t* kind = b ? a.kind + (int64_t)(b - 1) * a.kind_bb : nullptr;
+            for (int idx = t; idx < tile_n * tail; idx += FTL_MLP_THREADS) {
+                const int e = idx / tail, k = idx - e * tail;
+                const size_t row_i = (size_t)start + e;
+                float v = 0.0f;
+                if (b == 0) {
+                    const float* row = a.state + row_i * a.state_stride;
+                    if (k < a.P) v = row[2 * C + k];
+                    else if (k < a.P + a.R) v = row[2 * C + a.P] != 0.0f ? (float)(a.reward0 ? a.reward0[row_i] : 0.0) : 0.0f;
+                    else v = row[k - a.P - a.R];
+                } else if (kind[row_i] != FTL_TR_VOID) {
+                    if (k < a.P) {
+                        const char* ab = static_cast<const char*>(a.action) + (int64_t)(b - 1) * a.action_bb;
+                        if (m.head == FTL_ACTION_DISCRETE) v = reinterpret_cast<const int32_t*>(ab)[row_i] == k ? 1.0f : 0.0f;
+                        else v = (float)reinterpret_cast<const double*>(ab)[row_i * a.P + k];
+                    } else if (k < a.P + a.R)
+                        v = (float)reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.reward) + (int64_t)(b - 1) * a.reward_bb)[row_i];
+                    else v = a.rec[(size_t)(b - 1) * rec_bb + row_i * 2 * C + (k - a.P - a.R)];
+                }
+                u[e * US + wx + k] = v;
+            }
+            if (t < TILE) u[t * US + U] = 1.0f;
+        };
+        // c of the row block b reads
+        auto c_prev = [&](int b, size_t row_i, int j) -> float {
+            if (b == 0) return a.state[row_i * a.state_stride + C + j];
+            if (a.kind[(int64_t)(b - 1) * a.kind_bb + row_i] == FTL_TR_VOID) return 0.0f;
+            return a.rec[(size_t)(b - 1) * rec_bb + row_i * 2 * C + C + j];
+        };
+
+        // ---- forward sweep: h' and c' of every block into the record
+        for (int b = 0; b < B; b++) {
+            trunk(b);
+            fill_tail(b);
+#pragma unroll 1
+            for (int ps = 0; ps < PASSES; ps++) {
+                const int j0 = ps * FTL_RNN_PASS_CELLS;
+                if (j0 >= C) break;
+                const int cn = C - j0 < FTL_RNN_PASS_CELLS ? C - j0 : FTL_RNN_PASS_CELLS;
+                f32x4 z[BPW];
+                layer_acc<true>(z, Wg, 4 * C, bg, Gates{cn, C, j0}, U, cn <= 2 * NB ? 128 : 256, nullptr, nullptr, start, tile_n, u, US, xs, ws);
+#pragma unroll
+                for (int gs = 0; gs < 2; gs++) {
+                    const int jj = gate_group(par, 4 * gs) * NB + li, j = j0 + jj;
+                    if (jj >= cn) continue;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int e = row_d + r;
+                        if (e >= tile_n) continue;
+                        const size_t row_i = (size_t)start + e;
+                        const float gi_ = ftlrnnmath::sig32(z[4 * gs][r]);
+                        const float gf = ftlrnnmath::sig32(z[4 * gs + 1][r]);
+                        const float gg = ftlrnnmath::tanh32(z[4 * gs + 2][r]);
+                        const float go = ftlrnnmath::sig32(z[4 * gs + 3][r]);
+                        const float tt = gi_ * gg;
+                        const float cn1 = __builtin_fmaf(gf, c_prev(b, row_i, j), tt);
+                        const float th = ftlrnnmath::tanh32(cn1);
+                        float* rc = a.rec + (size_t)b * rec_bb + row_i * 2 * C;
+                        rc[j] = go * th;
+                        rc[C + j] = cn1;
+                    }
+                }
+            }
+        }
+
+        // ---- reverse sweep
+        float dcn[PASSES][2][4];
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ps++)
+#pragma unroll
+            for (int gs = 0; gs < 2; gs++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int j = ps * FTL_RNN_PASS_CELLS + gate_group(par, 4 * gs) * NB + li, e = row_d + r;
+                    dcn[ps][gs][r] = (a.dstate_in && j < C && e < tile_n) ? a.dstate_in[((size_t)start + e) * 2 * C + C + j] : 0.0f;
+                }
+        for (int b = B - 1; b >= 0; b--) {
+            const int pair = ti * B + (B - 1 - b);
+            const bool first = pair % FTL_RNN_BWD_SPAN == 0;
+            float* Gs = a.part + (span_base + pair / FTL_RNN_BWD_SPAN) * a.count;
+            const uint8_t* kind = b + 1 < B ? a.kind + (int64_t)b * a.kind_bb : nullptr;        // the row block b + 1 read was zeros where VOID
+            trunk(b);
+            fill_tail(b);
+            {
+                const float* dy = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.dy) + (int64_t)b * a.dy_bb) + (size_t)start * A;
+                for (int idx = t; idx < TILE * A; idx += FTL_MLP_THREADS) {
+                    const int r = idx / A;
+                    dyb[r * DS + (idx - r * A)] = r < tile_n ? dy[idx] : 0.0f;
+                }
+                const float* hr = a.rec + (size_t)b * rec_bb + (size_t)start * 2 * C;
+                for (int idx = t; idx < tile_n * C; idx += FTL_MLP_THREADS) {
+                    const int r = idx / C, k = idx - r * C;
+                    hn[r * HS + k] = hr[(size_t)r * 2 * C + k];
+                }
+                if (t < TILE) hn[t * HS + C] = 1.0f;
+            }
+            __syncthreads();
+            dw_map(hn, HS, 0, C + 1, dyb, DS, A, Gs + o_y, A, ColMap{A, A, 0}, first, tile_n, wave, li, lk);
+            // dh = the chain of W_y over dy, plus dh_next
+            for (int idx = t; idx < tile_n * C; idx += FTL_MLP_THREADS) {
+                const int e = idx / C, k = idx - e * C;
+                const size_t row_i = (size_t)start + e;
+                float acc = 0.0f;
+                for (int j = 0; j < A; j++) acc = __builtin_fmaf(Wy[k * A + j], dyb[e * DS + j], acc);
+                float nx;
+                if (b + 1 == B) nx = a.dstate_in ? a.dstate_in[row_i * 2 * C + k] : 0.0f;
+                else nx = kind[row_i] == FTL_TR_VOID ? 0.0f : dhb[e * HS + k];
+                dhb[e * HS + k] = acc + nx;
+            }
+            bool wipe[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) wipe[r] = kind && row_d + r < tile_n && kind[(size_t)start + row_d + r] == FTL_TR_VOID;
+#pragma unroll 1
+            for (int ps = 0; ps < PASSES; ps++) {
+                const int j0 = ps * FTL_RNN_PASS_CELLS;
+                if (j0 >= C) break;
+                const int cn = C - j0 < FTL_RNN_PASS_CELLS ? C - j0 : FTL_RNN_PASS_CELLS, w = 4 * cn;
+                const bool firstp = ps == 0, lastp = j0 + cn >= C;
+                {
+                    f32x4 z[BPW];
+                    // (layer_acc() begins with a barrier: u, dh are complete, and nobody reads h', dy or the last pass's dz any more)
+                    layer_acc<true>(z, Wg, 4 * C, bg, Gates{cn, C, j0}, U, cn <= 2 * NB ? 128 : 256, nullptr, nullptr, start, tile_n, u, US, xs, ws);
+#pragma unroll
+                    for (int gs = 0; gs < 2; gs++) {
+                        const int jj = gate_group(par, 4 * gs) * NB + li, j = j0 + jj;
+                        if (jj >= cn) continue;
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const int e = row_d + r;
+                            if (e >= tile_n) continue;
+                            const size_t row_i = (size_t)start + e;
+                            const float gi_ = ftlrnnmath::sig32(z[4 * gs][r]);
+                            const float gf = ftlrnnmath::sig32(z[4 * gs + 1][r]);
+                            const float gg = ftlrnnmath::tanh32(z[4 * gs + 2][r]);
+                            const float go = ftlrnnmath::sig32(z[4 * gs + 3][r]);
+                            const float cp = c_prev(b, row_i, j);
+                            const float tt = gi_ * gg;
+                            const float cn1 = __builtin_fmaf(gf, cp, tt);
+                            const float tc = ftlrnnmath::tanh32(cn1);
+                            const float dh = dhb[e * HS + j];
+                            const float dcx = wipe[r] ? 0.0f : (ps == 0 ? dcn[0][gs][r] : dcn[1][gs][r]);
+                            const float q = dh * go;
+                            const float d = __builtin_fmaf(-tc, tc, 1.0f);
+                            const float dc = __builtin_fmaf(q, d, dcx);
+                            const float d_o = dh * tc;
+                            const float di = dc * gg, dg = dc * gi_, df = dc * cp, dnx = dc * gf;
+                            if (ps == 0) dcn[0][gs][r] = dnx; else dcn[1][gs][r] = dnx;
+                            float* zr = dzp + e * ZS + jj;
+                            zr[0] = di * __builtin_fmaf(-gi_, gi_, gi_);
+                            zr[cn] = df * __builtin_fmaf(-gf, gf, gf);
+                            zr[2 * cn] = dg * __builtin_fmaf(-gg, gg, 1.0f);
+                            zr[3 * cn] = d_o * __builtin_fmaf(-go, go, go);
+                        }
+                    }
+                }
+                __syncthreads();
+                dw_map(u, US, 0, U + 1, dzp, ZS, w, Gs + o_g, 4 * C, ColMap{cn, C, j0}, first, tile_n, wave, li, lk);
+                // du[r][k] = the chain over the pass's columns of W_g[k][col] * dz[r][col], from +0 or the pass before
+                const int kc = ftlmlp::chunk_rows(w), wst = ftlmlp::bwd_stride(w);
+                for (int k0 = 0; k0 < U; k0 += kc) {
+                    const int kn = U - k0 < kc ? U - k0 : kc, nkb = (kn + NB - 1) / NB;
+                    __syncthreads();
+                    for (int idx = t; idx < kn * w; idx += FTL_MLP_THREADS) {
+                        const int kk = idx / w, dd = idx - kk * w;
+                        ws[kk * wst + dd] = Wg[(size_t)(k0 + kk) * 4 * C + map_col(ColMap{cn, C, j0}, dd)];
+                    }
+                    __syncthreads();
+                    if (!busy) continue;
+                    f32x4 acc[2];
+                    const float* wr[2];
+#pragma unroll
+                    for (int mm = 0; mm < 2; mm++) {
+                        const int k = (par + PARITIES * mm) * NB + li;
+                        wr[mm] = ws + (k < kn ? k : kn - 1) * wst;
+#pragma unroll
+                        for (int r = 0; r < 4; r++) acc[mm][r] = (firstp || k >= kn) ? 0.0f : carry[(row_d + r) * U + k0 + k];
+                    }
+                    for (int j = 0; j < w; j += 4) {
+                        const float av = dzp[row_a * ZS + j + lk];
+#pragma unroll
+                        for (int mm = 0; mm < 2; mm++)
+                            if (par + PARITIES * mm < nkb) acc[mm] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wr[mm][j + lk], acc[mm], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int mm = 0; mm < 2; mm++) {
+                        const int k = (par + PARITIES * mm) * NB + li, kk = k0 + k;
+                        if (k >= kn) continue;
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            const int e = row_d + r;
+                            const float v = acc[mm][r];
+                            if (!lastp) carry[e * U + kk] = v;
+                            else if (kk < wx) { float* p = u + e * US + kk; *p = *p > 0.0f ? v : 0.0f; }
+                            else if (kk >= wx + a.P + a.R) dhb[e * HS + (kk - wx - a.P - a.R)] = v;
+                        }
+                    }
+                }
+            }
+            // the trunk, as ftl_mlp_backward_kernel: delta_Lt lies in the x columns of u
+            for (int l = Lt; l >= 1; l--) {
+                const int w_in = m.width[l - 1], w_out = m.width[l];
+                const float* delta = l == Lt ? u : hb + (l - 1) * TILE * AS;
+                const int dst = l == Lt ? US : AS;
+                float* Gl = Gs + off[l - 1];
+                if (l == 1) {
+                    const float* obs = reinterpret_cast<const float*>(reinterpret_cast<const char*>(m.obs) + (int64_t)b * a.obs_bb);
+                    for (int k0 = 0; k0 < w0 + 1; k0 += KC) {
+                        const int kn = w0 + 1 - k0 < KC ? w0 + 1 - k0 : KC;
+                        __syncthreads();
+                        const int e = t >> 3;
+                        if (e < tile_n) {
+                            const size_t row = (size_t)(start + e) * w0;
+                            for (int kk = t & 7; kk < kn; kk += 8) xs[e * XS + kk] = k0 + kk < w0 ? obs[row + k0 + kk] : 1.0f;
+                        }
+                        __syncthreads();
+                        dw_map(xs, XS, k0, kn, delta, dst, w_out, Gl, w_out, ColMap{w_out, w_out, 0}, first, tile_n, wave, li, lk);
+                    }
+                    break;
+                }
+                float* hprev = hb + (l - 2) * TILE * AS;
+                __syncthreads();
+                dw_map(hprev, AS, 0, w_in + 1, delta, dst, w_out, Gl, w_out, ColMap{w_out, w_out, 0}, first, tile_n, wave, li, lk);
+                const float* W = P0 + off[l - 1];
+                const int kc = ftlmlp::chunk_rows(w_out), wst = ftlmlp::bwd_stride(w_out);
+                for (int k0 = 0; k0 < w_in; k0 += kc) {
+                    const int kn = w_in - k0 < kc ? w_in - k0 : kc, nkb = (kn + NB - 1) / NB;
+                    __syncthreads();
+                    ftlmlp::stage_rows(ws, wst, W + (size_t)k0 * w_out, kn, w_out, t);
+                    __syncthreads();
+                    if (!busy) continue;
+                    f32x4 acc[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+                    const float* wr[2];
+#pragma unroll
+                    for (int mm = 0; mm < 2; mm++) {
+                        const int k = (par + PARITIES * mm) * NB + li;
+                        wr[mm] = ws + (k < kn ? k : kn - 1) * wst;
+                    }
+                    int j = 0;
+                    for (; j + 4 <= w_out; j += 4) {
+                        const float av = delta[row_a * dst + j + lk];
+#pragma unroll
+                        for (int mm = 0; mm < 2; mm++)
+                            if (par + PARITIES * mm < nkb) acc[mm] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wr[mm][j + lk], acc[mm], 0, 0, 0);
+                    }
+                    for (; j < w_out; j++) {
+#pragma unroll
+                        for (int mm = 0; mm < 2; mm++) {
+                            if (par + PARITIES * mm >= nkb) continue;
+                            const float wv = wr[mm][j];
+#pragma unroll
+                            for (int r = 0; r < 4; r++) acc[mm][r] = __builtin_fmaf(wv, delta[(row_d + r) * dst + j], acc[mm][r]);
+                        }
+                    }
+#pragma unroll
+                    for (int mm = 0; mm < 2; mm++) {
+                        const int k = (par + PARITIES * mm) * NB + li;
+                        if (k >= kn) continue;
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            float* p = hprev + (row_d + r) * AS + k0 + k;
+                            *p = *p > 0.0f ? acc[mm][r] : 0.0f;
+                        }
+                    }
+                }
+            }
+        }
+        // d loss / d (h, c) of the rows block 0 read
+        __syncthreads();
+        if (a.dstate_out) {
+            for (int idx = t; idx < tile_n * C; idx += FTL_MLP_THREADS) {
+                const int e = idx / C, k = idx - e * C;
+                a.dstate_out[((size_t)start + e) * 2 * C + k] = dhb[e * HS + k];
+            }
+#pragma unroll
+            for (int ps = 0; ps < PASSES; ps++)
+#pragma unroll
+                for (int gs = 0; gs < 2; gs++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int j = ps * FTL_RNN_PASS_CELLS + gate_group(par, 4 * gs) * NB + li, e = row_d + r;
+                        if (j < C && e < tile_n) a.dstate_out[((size_t)start + e) * 2 * C + C + j] = dcn[ps][gs][r];
+                    }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace ftlrnn
 
 static int32_t rnn_prev_width(int32_t head_width, uint32_t flags) { return (flags & FTL_RNN_PREV_ACTION) ? head_width : 0; }
@@ -580,6 +1004,36 @@ static int rnn_kernel_ready(size_t lds, const void* kernel = (const void*)ftlrnn
     if (lds > 160 * 1024) return fail(FTL_E_UNSUPPORTED, "rnn: the net needs more than 160 KiB of LDS per workgroup");
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     return FTL_OK;
+}
+
+// the groups and spans of ftl_rnn_backward for a checked net and its rows (include/ftl.h): per touched set -- the first, a whole one, the
+// last (0 when the first is the only one) -- and in all
+struct RnnBwdPlan { int64_t G, spg, groups0, groups_mid, groups, spans0, spans_mid, spans_last, n_touched, spans; };
+static RnnBwdPlan rnn_bwd_plan(const ftl_rnn* net, int64_t B, int64_t n) {
+    const int64_t eps = net->envs_per_set, first = net->env_first, tile = FTL_MLP_ENV_TILE, span = FTL_RNN_BWD_SPAN;
+    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0, full = rem / eps, last = rem % eps;
+    RnnBwdPlan p;
+    p.G = std::max<int64_t>(1, span / B);
+    p.spg = (p.G * B + span - 1) / span;
+    auto groups_of = [&](int64_t rows) { return ((rows + tile - 1) / tile + p.G - 1) / p.G; };
+    auto spans_of = [&](int64_t rows) {
+        const int64_t tiles = (rows + tile - 1) / tile, cut = tiles % p.G;
+        return (tiles / p.G) * p.spg + (cut ? (cut * B + span - 1) / span : 0);
+    };
+    p.groups0 = groups_of(len0); p.groups_mid = rem ? groups_of(eps) : 1;
+    p.groups = p.groups0 + full * p.groups_mid + (last ? groups_of(last) : 0);
+    p.spans0 = spans_of(len0); p.spans_mid = rem ? spans_of(eps) : 1;
+    p.spans_last = !rem ? 0 : last ? spans_of(last) : p.spans_mid;
+    p.n_touched = 1 + full + (last ? 1 : 0);
+    p.spans = p.spans0 + full * p.spans_mid + (last ? p.spans_last : 0);
+    return p;
+}
+
+// the workspace of ftl_rnn_backward in floats: the span partials, the record h' | c' of every block, the groups' carry rows
+static int64_t rnn_bwd_workspace_floats(const ftl_rnn* net, const RnnBwdPlan& p, int64_t B, int64_t n, int64_t count) {
+    const int32_t Lt = net->n_layers, A = net->width[Lt + 1], C = net->cell;
+    const int64_t U = (int64_t)net->width[Lt] + rnn_prev_width(A, net->flags) + ((net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0) + C;
+    return p.spans * count + B * n * 2 * C + p.groups * FTL_MLP_ENV_TILE * U;
 }
 
 extern "C" {
@@ -761,6 +1215,105 @@ int ftl_rnn_forward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, i
     a.action = P ? seq->action : nullptr; a.reward = R ? seq->reward : nullptr; a.kind = seq->kind; a.reward0 = R ? seq->reward0 : nullptr;
     a.head = seq->head; a.h = seq->h; a.state_out = seq->state_out;
     hipLaunchKernelGGL(ftlrnn::ftl_rnn_forward_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+    return launched();
+}
+
+size_t ftl_sizeof_rnn_gradient(void) { return sizeof(ftl_rnn_gradient); }
+
+int64_t ftl_sizeof_rnn_backward_workspace(const ftl_rnn* net, int32_t n_blocks, int32_t n) {
+    if (!net || n_blocks < 1 || n < 1 || net->envs_per_set < 1 || net->env_first < 0) return -1;
+    const int64_t count = rnn_param_count(net->width, net->n_layers, net->cell, net->flags);
+    if (count < 0) return -1;
+    return rnn_bwd_workspace_floats(net, rnn_bwd_plan(net, n_blocks, n), n_blocks, n, count) * 4;
+}
+
+int ftl_rnn_backward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, int32_t n, const ftl_rnn_sequence* seq, const ftl_rnn_gradient* g,
+                     void* stream) {
+    if (!h) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: h");
+    if (!net) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: net");
+    if (!net->params) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: net->params");
+    if (!seq) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq");
+    if (!g) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g");
+    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_rnn_backward: n_blocks and n must be at least 1");
+    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_rnn_backward: n_blocks beyond 65,535 (the limit of ftl_rnn_forward)");
+    if (int rc = rnn_net_check(net, n, "the last row")) return rc;
+    if (int rc = rnn_state_check(net)) return rc;
+    const int32_t Lt = net->n_layers, A = net->width[Lt + 1], C = net->cell;
+    const int32_t P = rnn_prev_width(A, net->flags), R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0;
+    const bool more = n_blocks > 1;
+    if (!seq->obs) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->obs");
+    if (!g->dhead) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g->dhead");
+    if (!g->grad) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g->grad");
+    if (!g->workspace) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g->workspace");
+    if (more && !seq->kind) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->kind (read for every block but the last)");
+    if (more && P && !seq->action) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->action (the net has FTL_RNN_PREV_ACTION)");
+    if (more && R && !seq->reward) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->reward (the net has FTL_RNN_PREV_REWARD)");
+    const int64_t arow = A == 2 ? 16 : A == 1 ? 8 : 4, ael = A == 5 ? 4 : 8;
+    if (seq->obs_block_bytes < (int64_t)n * net->width[0] * 4 || (seq->obs_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_rnn_backward: obs_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
+    if (more && P && (seq->action_block_bytes < (int64_t)n * arow || (seq->action_block_bytes & (ael - 1))))
+        return fail(FTL_E_INVALID, "ftl_rnn_backward: action_block_bytes must be a multiple of the action element of at least one block of encoded actions");
+    if (more && R && (seq->reward_block_bytes < (int64_t)n * 8 || (seq->reward_block_bytes & 7)))
+        return fail(FTL_E_INVALID, "ftl_rnn_backward: reward_block_bytes must be a multiple of 8 of at least one block, n * 8");
+    if (more && seq->kind_block_bytes < (int64_t)n)
+        return fail(FTL_E_INVALID, "ftl_rnn_backward: kind_block_bytes below one block, n");
+    if (g->dhead_block_bytes < (int64_t)n * A * 4 || (g->dhead_block_bytes & 3))
+        return fail(FTL_E_INVALID, "ftl_rnn_backward: dhead_block_bytes must be a multiple of 4 of at least one block, n * A * 4");
+    ftlrnn::Bwd a; unsigned grid;
+    rnn_fill(net, n, a.m, a.u_stride, a.h_stride, grid);
+    // LDS (include/ftl.h): the hidden buffers, u, dh, the weight stage, and the region that is xs | h' | dy, then dz of a gate pass
+    const int32_t cnmax = std::min<int32_t>(C, FTL_RNN_PASS_CELLS);
+    a.dz_stride = 4 * cnmax + 2;
+    size_t stage = FTL_MLP_W_STAGE + 64;
+    for (int l = 1; l <= Lt + 1; l++) {
+        const int w = l <= Lt ? net->width[l] : 4 * cnmax;
+        stage = std::max(stage, (size_t)ftlmlp::chunk_rows(w) * ftlmlp::bwd_stride(w));
+    }
+    if (C > FTL_RNN_PASS_CELLS && C % FTL_RNN_PASS_CELLS) {      // (the second pass of a cell that is no multiple of the pass)
+        const int w = 4 * (C - FTL_RNN_PASS_CELLS);
+        stage = std::max(stage, (size_t)ftlmlp::chunk_rows(w) * ftlmlp::bwd_stride(w));
+    }
+    a.stage = (int32_t)stage;
+    const size_t region = std::max<size_t>(a.dz_stride, ftlmlp::XS + a.h_stride + ftlmlp::dy_stride(A));
+    const size_t lds = ((size_t)FTL_MLP_ENV_TILE * ((size_t)(Lt - 1) * a.m.act_stride + a.u_stride + a.h_stride + region) + stage) * sizeof(float);
+    if (lds > 160 * 1024) return fail(FTL_E_UNSUPPORTED, "ftl_rnn_backward: the net needs more than the 160 KiB of LDS of a workgroup (FTL_RNN_BWD limits)");
+    const RnnBwdPlan p = rnn_bwd_plan(net, n_blocks, n);
+    if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull || (uint64_t)p.spans * FTL_MLP_THREADS > 0xFFFFFFFFull)
+        return fail(FTL_E_UNSUPPORTED, "ftl_rnn_backward: n beyond the 2^24 - 1 tiles of a block, or beyond 2^24 - 1 spans in all; split the rows");
+    const int64_t count = rnn_param_count(net->width, Lt, C, net->flags);
+    if (g->workspace_bytes < rnn_bwd_workspace_floats(net, p, n_blocks, n, count) * 4)
+        return fail(FTL_E_INVALID, "ftl_rnn_backward: workspace_bytes below ftl_sizeof_rnn_backward_workspace");
+    if (((uintptr_t)seq->obs) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: obs must be 4-byte aligned");
+    if (more && P && (((uintptr_t)seq->action) & (uintptr_t)(ael - 1))) return fail(FTL_E_INVALID, "ftl_rnn_backward: action not aligned to its element");
+    if (more && R && (((uintptr_t)seq->reward) & 7)) return fail(FTL_E_INVALID, "ftl_rnn_backward: reward must be 8-byte aligned");
+    if (((uintptr_t)seq->reward0) & 7) return fail(FTL_E_INVALID, "ftl_rnn_backward: reward0 must be 8-byte aligned");
+    if (((uintptr_t)g->dhead) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: dhead must be 4-byte aligned");
+    if (((uintptr_t)g->dstate_in) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: dstate_in must be 4-byte aligned");
+    if (((uintptr_t)g->dstate_out) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: dstate_out must be 4-byte aligned");
+    if (((uintptr_t)g->workspace) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: workspace must be 4-byte aligned");
+    if (((uintptr_t)g->grad) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: grad must be 4-byte aligned");
+    if (int rc = set_device(h)) return rc;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)ftlrnn::ftl_rnn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipFuncSetAttribute(ftl_rnn_backward_kernel): ") + hipGetErrorString(e));
+    }
+    a.m.obs = seq->obs; a.m.lo0 = a.m.hi0 = a.m.lo1 = a.m.hi1 = 0.0;
+    a.cell = C; a.P = P; a.R = R; a.A = A;
+    a.n_blocks = n_blocks; a.G = (int32_t)p.G; a.spg = (int32_t)p.spg;
+    a.groups0 = (int32_t)p.groups0; a.groups_mid = (int32_t)p.groups_mid; a.spans0 = (int32_t)p.spans0; a.spans_mid = (int32_t)p.spans_mid;
+    a.state = net->state; a.state_stride = net->state_stride;
+    a.obs_bb = seq->obs_block_bytes; a.action_bb = seq->action_block_bytes; a.reward_bb = seq->reward_block_bytes;
+    a.kind_bb = seq->kind_block_bytes; a.dy_bb = g->dhead_block_bytes;
+    a.action = P ? seq->action : nullptr; a.reward = R ? seq->reward : nullptr; a.kind = seq->kind; a.reward0 = R ? seq->reward0 : nullptr;
+    a.dy = g->dhead; a.dstate_in = g->dstate_in; a.dstate_out = g->dstate_out;
+    a.part = static_cast<float*>(g->workspace); a.count = count;
+    a.rec = a.part + p.spans * count;
+    a.carry = a.rec + (int64_t)n_blocks * n * 2 * C;
+    hipLaunchKernelGGL(ftlrnn::ftl_rnn_backward_kernel, dim3((unsigned)p.groups), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
+    const ftlmlp::Reduce rd{a.part, g->grad, count, net->set_stride, (int32_t)(net->env_first / net->envs_per_set),
+                            (int32_t)p.n_touched, (int32_t)p.spans0, (int32_t)p.spans_mid, (int32_t)p.spans_last};
+    hipLaunchKernelGGL(ftlmlp::ftl_mlp_backward_reduce_kernel, dim3((unsigned)p.n_touched, (unsigned)((count + FTL_MLP_THREADS - 1) / FTL_MLP_THREADS)),
+                       dim3(FTL_MLP_THREADS), 0, (hipStream_t)stream, rd);
     return launched();
 }
 

@@ -13,7 +13,7 @@ recorded rows with the same arithmetic (``ftl_mlp_forward``): ``Critic`` is a he
 ``policy.forward(traj.obs[:-1])`` replays ``traj.head`` bit for bit.  ``backward()`` is its derivative with respect to the weights
 (``ftl_mlp_backward``), per set and in a fixed summation order, and ``Net`` ties the two together under torch autograd: an ``nn.Module``
 whose one parameter can share storage with ``policy.params`` or ``critic.params``, so one optimizer trains what the device plays.  The
-recurrent net (``rnn.py``) has no such backward pass: its loss lines stay with torch autograd on a torch module."""
+recurrent net has the same pair in ``rnn.py`` (``rnn.backward``, ``rnn.Net``)."""
 import ctypes as C
 import functools
 

@@ -10,7 +10,9 @@ before the first decision on the new episode's observation ("same_step", "queue"
 
 A recorded sequence goes back through a recurrent net in one launch (``ftl_rnn_forward``): ``forward`` evaluates any net on recorded blocks
 with the state carried from block to block and zeroed after VOID rows as ``collect_rnn`` did, ``RecurrentPolicy.forward(traj)`` is the
-actor's replay -- ``traj.head`` bit for bit --, and ``RecurrentCritic`` is a head-1 net with memory whose ``values(traj)`` feed ``gae()``."""
+actor's replay -- ``traj.head`` bit for bit --, and ``RecurrentCritic`` is a head-1 net with memory whose ``values(traj)`` feed ``gae()``.
+``backward`` is back-propagation through time on the same record (``ftl_rnn_backward``), and ``Net`` is the ``nn.Module`` over the two whose
+parameter can be ``RecurrentPolicy.params`` or ``RecurrentCritic.params`` itself."""
 import ctypes as C
 
 import torch
@@ -249,26 +251,8 @@ def _is(t, dtype, shape, device):
     return torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device == device and t.is_contiguous()
 
 
-def forward(widths, cell, params, obs, action=None, reward=None, kind=None, state=None, reward0=None, prev_action=True, prev_reward=True,
-            out=None, h_out=None, state_out=None, state_at=0):
-    """The raw heads of ``n_sets`` recurrent nets (``widths`` = input width, trunk layers, head width; ``cell`` LSTM units) on a recorded
-    sequence, in ONE launch (``ftl_rnn_forward``): block b is evaluated operation for operation as ``ftl_rnn_act`` evaluates a decision,
-    the state is carried from block to block inside the kernel, and the row block b + 1 reads is all zeros where ``kind[b]`` is
-    ``FTL_TR_VOID`` -- what ``collect_rnn`` did when it recorded the sequence.
-
-    ``params`` float32 ``[n_sets, param_count]`` (``RecurrentPolicy.params``); ``obs`` float32 ``[B, N, widths[0]]``; ``n_sets`` must
-    divide N and row r uses set ``r // (N // n_sets)``.  ``action`` (float64 ``[>= B-1, N, 2]`` for head 2, float64 ``[>= B-1, N]`` for head
-    1, int32 ``[>= B-1, N]`` for head 5), ``reward`` float64 ``[>= B-1, N]`` and ``kind`` uint8 ``[>= B-1, N]`` are the records between
-    the blocks: a ``Trajectory``'s T-block tensors are accepted as they are for B = T (``obs[:-1]``) or B = T + 1 (``obs``).  ``action``
-    is needed only with ``prev_action``, ``reward`` only with ``prev_reward``, and none of the three for B = 1.  ``state`` float32
-    ``[N, S]`` is the state before block 0 (None: zeros, every row at the start of an episode; it is never written), ``reward0`` float64
-    ``[N]`` the reward the first decision saw (None: zeros).
-
-    Returns float32 ``[B, N, A]`` (``out=`` reuses such a buffer).  ``h_out`` float32 ``[B, N, cell]`` receives the cell's output of every
-    block, ``state_out`` float32 ``[N, S]`` the rows block ``state_at`` read (``0 <= state_at < B``): the ``state`` of a call that continues
-    there.  Outputs must not overlap inputs.  The launch goes to the current stream of ``obs``'s device.  ``ValueError`` for every shape,
-    dtype, device or contiguity mismatch, ``NotImplementedError`` beyond the limits of ``ftl_rnn`` or beyond 65,535 blocks, both before any
-    library call.  There is no backward pass."""
+def _check_sequence(widths, cell, params, obs, action, reward, kind, state, reward0, prev_action, prev_reward, grad_msg):
+    """The checks ``forward`` and ``backward`` share, in ``forward``'s order; returns ``(widths, cell, flags, count, n_sets, B, N, dev)``."""
     widths, cell = check_rnn_widths(widths, cell)
     A, W0 = widths[-1], widths[0]
     flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
@@ -281,7 +265,7 @@ def forward(widths, cell, params, obs, action=None, reward=None, kind=None, stat
     if not (torch.is_tensor(obs) and obs.dtype == torch.float32 and obs.dim() == 3 and obs.shape[2] == W0 and obs.is_contiguous()):
         raise ValueError("obs must be a contiguous float32 [B, N, %d] tensor" % W0)
     if obs.requires_grad or params.requires_grad:
-        raise ValueError("forward() has no backward pass: pass detached tensors")
+        raise ValueError(grad_msg)
     B, N, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
     if B < 1 or N < 1:
         raise ValueError("obs must hold at least one block of at least one row, not %s" % (list(obs.shape),))
@@ -301,21 +285,14 @@ def forward(widths, cell, params, obs, action=None, reward=None, kind=None, stat
         raise ValueError("state must be a contiguous float32 [N, S] = [%d, %d] tensor on obs's device" % (N, S))
     if reward0 is not None and not _is(reward0, torch.float64, (N,), dev):
         raise ValueError("reward0 must be a contiguous float64 [N] = [%d] tensor on obs's device" % N)
-    if out is not None and not _is(out, torch.float32, (B, N, A), dev):
-        raise ValueError("out must be a contiguous float32 %s tensor on obs's device" % ([B, N, A],))
-    if h_out is not None and not _is(h_out, torch.float32, (B, N, cell), dev):
-        raise ValueError("h_out must be a contiguous float32 %s tensor on obs's device" % ([B, N, cell],))
-    if state_out is not None:
-        if not _is(state_out, torch.float32, (N, S), dev):
-            raise ValueError("state_out must be a contiguous float32 [N, S] = [%d, %d] tensor on obs's device" % (N, S))
-        if not 0 <= int(state_at) < B:
-            raise ValueError("state_at must name a block, 0 <= state_at < %d, not %r" % (B, state_at))
-    if not obs.is_cuda or params.device != dev:
-        raise ValueError("obs and params must lie on the same GPU device")
-    if out is None:
-        out = torch.empty(B, N, A, dtype=torch.float32, device=dev)
-    if state is None:
-        state = torch.zeros(N, S, dtype=torch.float32, device=dev)
+    return widths, cell, flags, count, n_sets, B, N, dev
+
+
+def _structs(widths, cell, flags, count, n_sets, params, obs, action, reward, kind, state, reward0):
+    """``(abi.Rnn, abi.RnnSequence)`` of checked arguments; the outputs of ``ftl_rnn_forward`` are left NULL."""
+    A, W0 = widths[-1], widths[0]
+    P, R, U, S = abi.rnn_widths(widths, cell, flags)
+    B, N = int(obs.shape[0]), int(obs.shape[1])
     net = abi.Rnn()
     net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), count, n_sets, len(widths) - 2
     for l, w in enumerate(widths):
@@ -331,6 +308,49 @@ def forward(widths, cell, params, obs, action=None, reward=None, kind=None, stat
             seq.reward, seq.reward_block_bytes = reward.data_ptr(), N * 8
         seq.kind, seq.kind_block_bytes = kind.data_ptr(), N
     seq.reward0 = reward0.data_ptr() if reward0 is not None else None
+    return net, seq
+
+
+def forward(widths, cell, params, obs, action=None, reward=None, kind=None, state=None, reward0=None, prev_action=True, prev_reward=True,
+            out=None, h_out=None, state_out=None, state_at=0):
+    """The raw heads of ``n_sets`` recurrent nets (``widths`` = input width, trunk layers, head width; ``cell`` LSTM units) on a recorded
+    sequence, in ONE launch (``ftl_rnn_forward``): block b is evaluated operation for operation as ``ftl_rnn_act`` evaluates a decision,
+    the state is carried from block to block inside the kernel, and the row block b + 1 reads is all zeros where ``kind[b]`` is
+    ``FTL_TR_VOID`` -- what ``collect_rnn`` did when it recorded the sequence.
+
+    ``params`` float32 ``[n_sets, param_count]`` (``RecurrentPolicy.params``); ``obs`` float32 ``[B, N, widths[0]]``; ``n_sets`` must
+    divide N and row r uses set ``r // (N // n_sets)``.  ``action`` (float64 ``[>= B-1, N, 2]`` for head 2, float64 ``[>= B-1, N]`` for head
+    1, int32 ``[>= B-1, N]`` for head 5), ``reward`` float64 ``[>= B-1, N]`` and ``kind`` uint8 ``[>= B-1, N]`` are the records between
+    the blocks: a ``Trajectory``'s T-block tensors are accepted as they are for B = T (``obs[:-1]``) or B = T + 1 (``obs``).  ``action``
+    is needed only with ``prev_action``, ``reward`` only with ``prev_reward``, and none of the three for B = 1.  ``state`` float32
+    ``[N, S]`` is the state before block 0 (None: zeros, every row at the start of an episode; it is never written), ``reward0`` float64
+    ``[N]`` the reward the first decision saw (None: zeros).
+
+    Returns float32 ``[B, N, A]`` (``out=`` reuses such a buffer).  ``h_out`` float32 ``[B, N, cell]`` receives the cell's output of every
+    block, ``state_out`` float32 ``[N, S]`` the rows block ``state_at`` read (``0 <= state_at < B``): the ``state`` of a call that continues
+    there.  Outputs must not overlap inputs.  The launch goes to the current stream of ``obs``'s device.  ``ValueError`` for every shape,
+    dtype, device or contiguity mismatch, ``NotImplementedError`` beyond the limits of ``ftl_rnn`` or beyond 65,535 blocks, both before any
+    library call.  ``backward`` is its derivative with respect to ``params``, and ``Net`` puts the
+    two under autograd."""
+    widths, cell, flags, count, n_sets, B, N, dev = _check_sequence(widths, cell, params, obs, action, reward, kind, state, reward0, prev_action,
+                                                                     prev_reward, "forward() has no backward pass: pass detached tensors")
+    A, S = widths[-1], abi.rnn_widths(widths, cell, flags)[3]
+    if out is not None and not _is(out, torch.float32, (B, N, A), dev):
+        raise ValueError("out must be a contiguous float32 %s tensor on obs's device" % ([B, N, A],))
+    if h_out is not None and not _is(h_out, torch.float32, (B, N, cell), dev):
+        raise ValueError("h_out must be a contiguous float32 %s tensor on obs's device" % ([B, N, cell],))
+    if state_out is not None:
+        if not _is(state_out, torch.float32, (N, S), dev):
+            raise ValueError("state_out must be a contiguous float32 [N, S] = [%d, %d] tensor on obs's device" % (N, S))
+        if not 0 <= int(state_at) < B:
+            raise ValueError("state_at must name a block, 0 <= state_at < %d, not %r" % (B, state_at))
+    if not obs.is_cuda or params.device != dev:
+        raise ValueError("obs and params must lie on the same GPU device")
+    if out is None:
+        out = torch.empty(B, N, A, dtype=torch.float32, device=dev)
+    if state is None:
+        state = torch.zeros(N, S, dtype=torch.float32, device=dev)
+    net, seq = _structs(widths, cell, flags, count, n_sets, params, obs, action, reward, kind, state, reward0)
     seq.head, seq.head_block_bytes = out.data_ptr(), N * A * 4
     if h_out is not None:
         seq.h, seq.h_block_bytes = h_out.data_ptr(), N * cell * 4
@@ -398,3 +418,128 @@ class RecurrentCritic(_RnnParams):
         v = forward(self.widths, self.cell, self.params, traj.obs, traj.action if self.prev_action else None, traj.reward, traj.kind, state,
                     reward0, self.prev_action, self.prev_reward, out=values, state_out=carry, state_at=T1 - 1)
         return v[..., 0], carry
+
+
+_BWD_WORKSPACE = {}
+
+
+def backward(widths, cell, params, obs, dhead, action=None, reward=None, kind=None, state=None, reward0=None, prev_action=True,
+             prev_reward=True, out=None, dstate_in=None, dstate_out=None):
+    """``d loss / d params`` of the nets ``forward`` evaluates, by back-propagation through time over the B blocks in one call on the
+    current stream (``ftl_rnn_backward``: a kernel that keeps the carry of a tile inside one workgroup, and a small reduction).  Every
+    argument of ``forward`` means what it means there; ``dhead`` is the gradient of a scalar loss with respect to the raw head of every
+    row, a detached contiguous float32 ``[B, N, A]`` tensor on ``obs``'s device, zeros on the rows to leave out (``~traj.valid``).
+    Returns float32 ``[n_sets, param_count]`` in the layout of ``params`` -- overwritten, not accumulated; ``out=`` reuses such a buffer.
+
+    ``dstate_in`` float32 ``[N, 2 * cell]`` is ``d loss / d (h', c')`` of the last block, from a later piece of the sequence (None:
+    zeros); ``dstate_out`` float32 ``[N, 2 * cell]`` receives ``d loss / d (h, c)`` of the rows block 0 read: the ``dstate_in`` of the
+    piece before, once the caller has zeroed the rows whose ``kind`` at the seam is VOID.
+
+    The arithmetic is fixed operation by operation (include/ftl.h; tests/rnn_backward_numpy.py is the twin): the forward values are
+    ``forward``'s bits, the zero rule cuts the carry where ``forward`` cut the state, and the sums over rows run in a fixed order --
+    float32 chains inside spans of ``abi.FTL_RNN_BWD_SPAN`` (tile, block) pairs, float64 across.  The workspace (span partials, ``h'`` and
+    ``c'`` of every block) is a tensor cached per device and stream.  There is no gradient with respect to observations, actions or
+    rewards.  ``ValueError`` / ``NotImplementedError`` as ``forward``, before any library call."""
+    widths, cell, flags, count, n_sets, B, N, dev = _check_sequence(widths, cell, params, obs, action, reward, kind, state, reward0, prev_action,
+                                                                     prev_reward, "backward() takes detached tensors: there is no gradient "
+                                                                     "with respect to obs, and params' gradient is what it returns")
+    A, S = widths[-1], abi.rnn_widths(widths, cell, flags)[3]
+    if abi.rnn_backward_lds_bytes(widths, cell, flags) > abi.FTL_RNN_BWD_MAX_LDS:
+        raise NotImplementedError("backward() keeps a tile's activations in the 160 KiB of LDS of a workgroup: this net needs %d bytes "
+                                  "(narrower trunk layers or fewer of them)" % abi.rnn_backward_lds_bytes(widths, cell, flags))
+    if not (_is(dhead, torch.float32, (B, N, A), dev) and not dhead.requires_grad):
+        raise ValueError("dhead must be a detached contiguous float32 %s tensor on obs's device" % ([B, N, A],))
+    if out is not None and not (_is(out, torch.float32, (n_sets, count), dev) and not out.requires_grad):
+        raise ValueError("out must be a contiguous float32 [%d, %d] tensor on obs's device" % (n_sets, count))
+    for name, t in (("dstate_in", dstate_in), ("dstate_out", dstate_out)):
+        if t is not None and not (_is(t, torch.float32, (N, 2 * cell), dev) and not t.requires_grad):
+            raise ValueError("%s must be a contiguous float32 [N, 2 * cell] = [%d, %d] tensor on obs's device" % (name, N, 2 * cell))
+    if not obs.is_cuda or params.device != dev:
+        raise ValueError("obs and params must lie on the same GPU device")
+    if out is None:
+        out = torch.empty(n_sets, count, dtype=torch.float32, device=dev)
+    if state is None:
+        state = torch.zeros(N, S, dtype=torch.float32, device=dev)
+    net, seq = _structs(widths, cell, flags, count, n_sets, params, obs, action, reward, kind, state, reward0)
+    lib = _lib.load()
+    h = _device_handle(dev)
+    need = lib.ftl_sizeof_rnn_backward_workspace(C.byref(net), B, N)
+    if need < 0:
+        raise _lib.FtlError("ftl_sizeof_rnn_backward_workspace refused a net that the package's checks passed")
+    raw = torch.cuda.current_stream(dev).cuda_stream
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), raw)
+    ws = _BWD_WORKSPACE.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = _BWD_WORKSPACE[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+    g = abi.RnnGradient()
+    g.dhead, g.dhead_block_bytes, g.grad = dhead.data_ptr(), N * A * 4, out.data_ptr()
+    g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    g.dstate_in = dstate_in.data_ptr() if dstate_in is not None else None
+    g.dstate_out = dstate_out.data_ptr() if dstate_out is not None else None
+    _lib.check(lib.ftl_rnn_backward(h, C.byref(net), B, N, C.byref(seq), C.byref(g), C.c_void_p(raw)), lib)
+    return out
+
+
+class _NetFunction(torch.autograd.Function):
+    """``forward`` with ``backward`` as its derivative with respect to ``params``."""
+
+    @staticmethod
+    def forward(ctx, params, net, obs, action, reward, kind, state, reward0):
+        ctx.save_for_backward(params)
+        ctx.net, ctx.seq = net, (obs, action, reward, kind, state, reward0)
+        return forward(net.widths, net.cell, params.detach(), obs, action, reward, kind, state, reward0, net.prev_action, net.prev_reward)
+
+    @staticmethod
+    def backward(ctx, dhead):
+        (params,), net = ctx.saved_tensors, ctx.net
+        obs, action, reward, kind, state, reward0 = ctx.seq
+        grad = backward(net.widths, net.cell, params.detach(), obs, dhead.detach().contiguous(), action, reward, kind, state, reward0,
+                        net.prev_action, net.prev_reward)
+        return (grad,) + (None,) * 7
+
+
+class Net(_RnnParams, torch.nn.Module):
+    """A trainable recurrent net on the device, or a population of ``n_sets`` of them: ``Net(widths, cell, n_sets=1, prev_action=True,
+    prev_reward=True, params=None, device=None)`` is an ``nn.Module`` whose one ``nn.Parameter`` ``params`` is the float32 ``[n_sets,
+    param_count]`` tensor of all weights in the layout of ``ftl_rnn`` (zeros on ``device``, the current GPU by default, unless given).
+    ``params=policy.params`` (a ``RecurrentPolicy``) or ``params=critic.params`` (a ``RecurrentCritic``) shares storage: an optimizer step on
+    ``net.params`` is what the policy plays next, with no copy.
+
+    ``net(traj, state=None, reward0=None)`` is ``forward`` under autograd on a ``Trajectory`` of ``collect_rnn`` -- ``traj.obs[:-1]`` with
+    ``traj.action`` / ``reward`` / ``kind`` from ``traj.state[0]`` unless ``state`` is given --, float32 ``[T, N, A]``; a tuple ``(obs, action,
+    reward, kind)`` of ``forward``'s tensors is taken as it is (``state`` None: zeros).  Its derivative is ``backward``: ``loss.backward()``
+    leaves ``d loss / d params`` in ``net.params.grad``, accumulated like any parameter's, with the pinned arithmetic of include/ftl.h.
+    ``layer``, ``cell_weights``, ``head_weights`` and ``load_lstm_cell`` are the views of the policy."""
+
+    def __init__(self, widths, cell, n_sets=1, prev_action=True, prev_reward=True, params=None, device=None):
+        torch.nn.Module.__init__(self)
+        self.widths, self.cell = check_rnn_widths(widths, cell)
+        self.trunk = self.widths[:-1]
+        self.prev_action, self.prev_reward = bool(prev_action), bool(prev_reward)
+        self.flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+        self.P, self.R, self.U, self.S = abi.rnn_widths(self.widths, self.cell, self.flags)
+        self.n_sets, self.param_count = int(n_sets), abi.rnn_param_count(self.widths, self.cell, self.flags)
+        if self.n_sets < 1:
+            raise ValueError("n_sets must be at least 1")
+        if params is None:
+            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
+        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
+                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
+            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the net's device" % self.param_count)
+        self.params = torch.nn.Parameter(params.detach())       # (the parameter shares the tensor's storage)
+
+    def forward(self, seq, state=None, reward0=None):
+        if isinstance(seq, Trajectory):
+            if not torch.is_tensor(getattr(seq, "state", None)) or not torch.is_tensor(seq.obs) or seq.obs.dim() != 3 or seq.obs.shape[0] < 2:
+                raise ValueError("a Trajectory must come from collect_rnn: obs [T + 1, N, H * W] and its state blocks")
+            obs, action, reward, kind = seq.obs[:-1], seq.action, seq.reward, seq.kind
+            if state is None:
+                state = seq.state[0]
+        elif isinstance(seq, (tuple, list)) and len(seq) == 4:
+            obs, action, reward, kind = seq
+        else:
+            raise ValueError("net() takes a Trajectory of collect_rnn or a tuple (obs, action, reward, kind)")
+        if any(torch.is_tensor(t) and t.requires_grad for t in (obs, action, reward, kind, state, reward0)):
+            raise ValueError("the sequence must not require grad: there is no gradient with respect to the record")
+        return _NetFunction.apply(self.params, self, obs, action if self.prev_action else None, reward if self.prev_reward else None, kind,
+                                  state, reward0)

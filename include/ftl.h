@@ -1214,6 +1214,95 @@ typedef struct ftl_rnn_sequence {
 size_t ftl_sizeof_rnn_sequence(void);
 int ftl_rnn_forward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, int32_t n, const ftl_rnn_sequence* seq, void* stream);
 
+/* ---- the backward pass of the recurrent net on a recorded sequence: d loss / d params of an ftl_rnn, per weight set, by back-propagation
+ * through time with pinned arithmetic --------------------------------------------------------------------------------------------------
+ * ftl_rnn_backward (ftl_rnn_backward_kernel, csrc/ftl_rnn.hpp, and ftl_mlp_backward_reduce_kernel: two launches on `stream`, asynchronous;
+ * the handle only names the device) is ftl_rnn_forward's counterpart as ftl_mlp_backward is ftl_mlp_forward's.  h, net, n_blocks = B, n
+ * and seq mean what they mean to ftl_rnn_forward: seq->obs, action, reward, kind and reward0 are read exactly as there, with net->state
+ * as the rows before block 0 (read, never written); seq->head, h and state_out are neither read nor written and may be NULL.
+ *   ftl_rnn_gradient
+ *     dhead      the caller's gradient of a scalar loss with respect to the raw head of every row, float32 [n][A] per block at
+ *                (char*)dhead + b * dhead_block_bytes; rows to leave out (FTL_TR_VOID steps) carry zeros.
+ *     grad       d loss / d params, float32 [net->n_sets][set_stride] in the layout of params: every parameter word of every set the rows
+ *                touch is OVERWRITTEN, not accumulated; untouched sets and the padding up to set_stride are not written.
+ *     dstate_in  optional, float32 [n][2C] dense: d loss / d (h', c') of block B - 1, from a later piece of the sequence (NULL: zeros).
+ *     dstate_out optional, float32 [n][2C] dense: d loss / d (h, c) of the rows block 0 read: the dstate_in of the piece before.  It is
+ *                what the arithmetic below leaves, with no regard to the seam: the caller zeroes the rows whose kind at the seam is
+ *                FTL_TR_VOID (the row the later piece read was zeros there).
+ *     workspace  ftl_sizeof_rnn_backward_workspace(net, B, n) bytes of device memory, 4-byte aligned, contents irrelevant before and
+ *                undefined after.
+ *   Observations, recorded actions, rewards and live are data: there is no gradient with respect to them.
+ *   Contract    the result is a pure function of the arguments: no atomics, no communication between workgroups inside a launch, no
+ *               dependence on the machine, the grid or timing.  tests/rnn_backward_numpy.py is the twin and the device is pinned to it bit
+ *               for bit.  Per row, for b = B-1 down to 0 (fmaf: one rounding; every other line one float32 operation):
+ *                 forward   the values of block b are exactly those of ftl_rnn_forward, zero rule included: u (the cell input), z, the
+ *                           gates i f g o, c (the cell state the block read), c', h', the trunk's activations h_0 = obs .. h_Lt = x, and
+ *                           tc = tanh32(c').  (The device keeps h' and c' of every block from a forward sweep and recomputes the rest: the
+ *                           pinned chains again, so the bits are the same.)
+ *                 head      dh[k] = the fmaf chain over j = 0 .. A-1 ascending, from +0, of W_y[k][j] * dy[j]; then dh = dh + dh_next.
+ *                 carry     dh_next and dc_next are dstate_in (or +0) at b = B-1; +0 where kind[b] == FTL_TR_VOID (the row block b+1 read
+ *                           was zeros); otherwise what block b+1 left (dh_next', dc_next' below).
+ *                 cell      q = dh * o;  d = fmaf(-tc, tc, 1.0f);  dc = fmaf(q, d, dc_next);  do = dh * tc;
+ *                           di = dc * g;  dg = dc * i;  df = dc * c;  dc_next' = dc * f;
+ *                           dz_i = di * fmaf(-i, i, i);  dz_f = df * fmaf(-f, f, f);  dz_o = do * fmaf(-o, o, o);
+ *                           dz_g = dg * fmaf(-g, g, 1.0f).
+ *                 gate in   du[k], k < U = the fmaf chain from +0 of W_g[k][col] * dz[col] over the columns in PASS order: for
+ *                           p = 0 .. ceil(C / FTL_RNN_PASS_CELLS) - 1, for the gates q = i, f, g, o, for the cells j of pass p ascending
+ *                           (j0 = p * FTL_RNN_PASS_CELLS <= j < min(C, j0 + FTL_RNN_PASS_CELLS)): col = q * C + j.  For C <=
+ *                           FTL_RNN_PASS_CELLS that is col = 0 .. 4C-1 ascending.  Its h columns are dh_next', its x columns feed the
+ *                           trunk, its a_prev and r_prev columns are dropped.
+ *                 trunk     delta_Lt[k] = x[k] > 0 ? du[k] : +0; then for l = Lt .. 2 the rule of ftl_mlp_backward under FTL_MLP_ACT_RELU:
+ *                           c[k] = the fmaf chain over j = 0 .. width[l]-1 ascending, from +0, of W_l[k][j] * delta_l[j];
+ *                           delta_{l-1}[k] = h_{l-1}[k] > 0 ? c[k] : +0.
+ *               and per set dW_y = sum h' (x) dy, dW_g = sum u (x) dz, dW_l = sum h_{l-1} (x) delta_l over the set's rows of all blocks,
+ *               every bias the row of its matrix whose input is a constant 1.0f, summed in this order:
+ *                 tiles     the set's tiles are those of ftl_rnn_forward (runs of up to FTL_MLP_ENV_TILE = 32 rows of a block that end at
+ *                           the set's last row of the block).
+ *                 groups    G = max(1, FTL_RNN_BWD_SPAN / B) (integer division) consecutive tiles of a set; the last group of a set may
+ *                           be shorter.  A group's (tile, block) pairs are enumerated tile-major, inside a tile the blocks DESCENDING
+ *                           (B-1 first: the order back-propagation visits them).
+ *                 spans     runs of FTL_RNN_BWD_SPAN = 64 consecutive pairs of ONE group; a group's last span may be shorter.
+ *                 partial   a span's partial of a word is the fmaf chain from +0 over its pairs and, inside a pair, the tile's 32 row
+ *                           slots ascending: acc = fmaf(input[r][k], delta[r][j], acc).
+ *                 cut tiles in the slots past a cut tile's end both factors are +0 (the bias's 1.0f too): fmaf(+0, +0, acc), which turns
+ *                           an acc of -0 into +0 and changes nothing else, as in ftl_mlp_backward.
+ *                 reduce    grad word = (float)(the float64 sum, from +0.0, of the set's partials as float64 in ascending (group, span)
+ *                           order).
+ *               Signed zeros: every other chain above has exactly the terms written -- the chains of dh (A terms), du (4 * cells of a pass
+ *               terms per pass, a multiple of 4) and c (width[l] terms; the device finishes a width that is no multiple of 4 with plain
+ *               fmaf) have no padded terms, so no -0 is turned into +0 anywhere but in the cut tiles' slots.  A chain from +0 whose
+ *               terms are all -0 or of mixed signed zeros gives +0, as fmaf does.
+ *               A float32 chain is at most 64 * 32 = 2,048 slots long.  FTL_RNN_BWD_SPAN, the group rule and the pass order are constants
+ *               of this header, not properties of a device or a launch.
+ *   Workspace   ftl_sizeof_rnn_backward_workspace(net, B, n) = 4 * (spans * ftl_rnn_param_count + B * n * 2C + groups * 32 * U) bytes: the
+ *               span partials, the record h' | c' of every block, and one tile of du per group (a cell of two passes carries du between
+ *               them).  groups = the sum over the touched sets of ceil(tiles / G), tiles = ceil(rows of the set in a block / 32); spans =
+ *               the sum over the touched sets of floor(tiles / G) * ceil(G * B / 64) + ceil((tiles % G) * B / 64).  Pure host arithmetic;
+ *               -1 for a NULL net, counts below 1, envs_per_set < 1, env_first < 0, or a net outside the limits of ftl_rnn_param_count.
+ *   Limits      those of ftl_rnn_forward (layers, widths, cell, n_blocks, tiles of a block), at most 2^24 - 1 spans, ReLU only (the
+ *               message of every ftl_rnn_* entry point otherwise), and the workgroup's LDS: 4 * (32 * ((Lt - 1) * act_stride + u_stride
+ *               + h_stride + max(4 * min(C, 64) + 2, 66 + h_stride + 34)) + stage) bytes must not exceed 160 KiB, with act_stride,
+ *               u_stride, h_stride = the widest of width[1 .. Lt-1] and A, U, C, each rounded up to a multiple of 32, plus 2, and stage =
+ *               at most 4,416 floats.  180-256-256 with C = 128 and a head of 5 needs 152,832 bytes, 128-128-128 with C = 128 fits, three trunk
+ *               layers of 256 do not.  Beyond any: FTL_E_UNSUPPORTED before any device work.
+ *   Aliasing    grad, workspace and dstate_out must not overlap any input or each other (not checked).
+ *   FTL_E_INVALID before any device work, each with a message that names the argument: NULL h, net, net->params, seq, g, seq->obs,
+ *   g->dhead, g->grad, g->workspace, or a record array the net reads; n_blocks < 1 or n < 1; what ftl_rnn_forward refuses of the net and
+ *   its state, with its messages; a *_block_bytes below one block of n rows or no multiple of the element size; workspace_bytes below
+ *   the query's answer; a pointer not aligned to its element. */
+#define FTL_RNN_BWD_SPAN 64            /* (tile, block) pairs of a span: 2,048 row slots in one float32 chain */
+typedef struct ftl_rnn_gradient {
+    const float* dhead;      int64_t dhead_block_bytes;   /* [B][n][A] */
+    float*       grad;                                    /* out [n_sets][set_stride], the layout of params */
+    void*        workspace;  int64_t workspace_bytes;
+    const float* dstate_in;                               /* [n][2C], optional */
+    float*       dstate_out;                              /* out [n][2C], optional */
+} ftl_rnn_gradient;
+size_t ftl_sizeof_rnn_gradient(void);
+int64_t ftl_sizeof_rnn_backward_workspace(const ftl_rnn* net, int32_t n_blocks, int32_t n);
+int ftl_rnn_backward(const ftl_handle* h /* device only */, const ftl_rnn* net, int32_t n_blocks, int32_t n,
+                     const ftl_rnn_sequence* seq, const ftl_rnn_gradient* g, void* stream);
+
 /* ---- episode queue: every entry of a list of scenarios played exactly once, with one record per entry (evaluation, curricula, level
  * replay) ---------------------------------------------------------------------------------------------------------------------------
  * The third reset discipline next to FTL_STEP_AUTO_RESET and FTL_STEP_NEXT_RESET, which restart a finished env at once from the reset
