@@ -29,6 +29,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ftl_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "ftl_collect.hpp"),
            os.path.join(_PKG, "csrc", "ftl_rnn.hpp"),
            os.path.join(_PKG, "csrc", "ftl_rnn_math.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_ppo.hpp"),
+           os.path.join(_PKG, "csrc", "ftl_ppo_math.hpp"),
            os.path.join(_PKG, "csrc", "ftl_search.hpp"),
            os.path.join(_PKG, "csrc", "ftl_guided.hpp"),
            os.path.join(_ROOT, "include", "ftl.h")]
@@ -189,6 +191,11 @@ def load():
     lib.ftl_sizeof_rnn_backward_workspace.restype = C.c_int64
     lib.ftl_rnn_backward.argtypes = [vp, C.POINTER(abi.Rnn), i32, i32, C.POINTER(abi.RnnSequence), C.POINTER(abi.RnnGradient), vp]
     lib.ftl_rnn_backward.restype = C.c_int
+    lib.ftl_sizeof_ppo_head_args.restype = C.c_size_t
+    lib.ftl_sizeof_ppo_head_workspace.argtypes = [i32, i32, i32]
+    lib.ftl_sizeof_ppo_head_workspace.restype = C.c_int64
+    lib.ftl_ppo_head.argtypes = [vp, C.POINTER(abi.PpoHeadArgs), vp]
+    lib.ftl_ppo_head.restype = C.c_int
     lib.ftl_sizeof_episode_record.restype = C.c_size_t
     lib.ftl_sizeof_episode_queue.restype = C.c_size_t
     lib.ftl_set_episode_queue.argtypes = [vp, C.POINTER(abi.EpisodeQueueC)]
@@ -237,6 +244,7 @@ EXPORTS = ("ftl_create", "ftl_destroy", "ftl_lasers_len", "ftl_get_config", "ftl
            "ftl_sizeof_collect_buffers", "ftl_mlp_sample", "ftl_collect_mlp", "ftl_gae", "ftl_mlp_forward", "ftl_mlp_backward", "ftl_sizeof_mlp_backward_workspace",
            "ftl_sizeof_rnn", "ftl_sizeof_rnn_collect_buffers", "ftl_rnn_param_count", "ftl_rnn_act", "ftl_rollout_rnn", "ftl_collect_rnn",
            "ftl_sizeof_rnn_sequence", "ftl_rnn_forward", "ftl_sizeof_rnn_gradient", "ftl_sizeof_rnn_backward_workspace", "ftl_rnn_backward",
+           "ftl_sizeof_ppo_head_args", "ftl_sizeof_ppo_head_workspace", "ftl_ppo_head",
            "ftl_gz_create", "ftl_gz_destroy", "ftl_gz_state_bytes", "ftl_gz_bind_state", "ftl_gz_lasers_len", "ftl_gz_reset", "ftl_gz_step",
            "ftl_gz_state_field")
 

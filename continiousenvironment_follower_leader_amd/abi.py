@@ -339,6 +339,24 @@ class RnnGradient(C.Structure):
                 ("workspace_bytes", C.c_int64), ("dstate_in", C.c_void_p), ("dstate_out", C.c_void_p)]
 
 
+# the PPO loss head (include/ftl.h, ftl_ppo_head): rows of a segment, columns of stats
+FTL_PPO_SEG, FTL_PPO_STATS = 1024, 8
+
+
+class PpoHeadArgs(C.Structure):
+    """ftl_ppo_head_args: the heads, the record, the advantages and the values of ``ftl_ppo_head``, its scalars, and where the gradients, the
+    statistics and the segment partials go (block b of an array at base + b * its ``*_block_bytes``)."""
+    _fields_ = [("n_blocks", C.c_int32), ("n", C.c_int32), ("n_sets", C.c_int32), ("width", C.c_int32),
+                ("head_new", C.c_void_p), ("head_new_block_bytes", C.c_int64), ("head_old", C.c_void_p), ("head_old_block_bytes", C.c_int64),
+                ("noise", C.c_void_p), ("noise_block_bytes", C.c_int64),
+                ("sigma_old", C.c_void_p), ("sigma_new", C.c_void_p), ("log_sigma_shift", C.c_void_p),
+                ("adv", C.c_void_p), ("adv_block_bytes", C.c_int64), ("ret", C.c_void_p), ("ret_block_bytes", C.c_int64),
+                ("value_new", C.c_void_p), ("value_new_block_bytes", C.c_int64), ("kind", C.c_void_p), ("kind_block_bytes", C.c_int64),
+                ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("vf_coef", C.c_float), ("normalize", C.c_int32),
+                ("dhead", C.c_void_p), ("dhead_block_bytes", C.c_int64), ("dvalue", C.c_void_p), ("dvalue_block_bytes", C.c_int64),
+                ("dlog_std", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class RnnCollectBuffers(C.Structure):
     """ftl_rnn_collect_buffers: ``CollectBuffers`` plus where the state rows every decision read are recorded."""
     _fields_ = [("b", CollectBuffers), ("state", C.c_void_p), ("state_step_bytes", C.c_int64), ("state_steps", C.c_int32), ("_pad", C.c_int32)]

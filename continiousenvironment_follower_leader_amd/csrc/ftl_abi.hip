@@ -826,6 +826,7 @@ int ftl_episode_metrics(ftl_handle* h, double* dev_metrics, int32_t* dev_errors,
 #include "ftl_mlp.hpp"           // a dense feed-forward policy population on policy_obs: the forward pass and closed-loop rollouts (ftl_mlp_act, ftl_rollout_mlp), same translation unit
 #include "ftl_collect.hpp"       // T recorded stochastic closed-loop steps through episode boundaries and their advantages (ftl_collect_mlp, ftl_gae), same translation unit
 #include "ftl_rnn.hpp"           // a recurrent policy population (dense trunk, LSTM cell, linear head): decisions, rollouts, trajectories (ftl_rnn_act, ftl_rollout_rnn, ftl_collect_rnn), same translation unit
+#include "ftl_ppo.hpp"           // the PPO loss head on recorded rows: dhead, dvalue, d log_std and statistics per weight set (ftl_ppo_head), same translation unit
 #include "ftl_search.hpp"        // K candidate action sequences per env on clones in a second handle (ftl_search), same translation unit
 #include "ftl_guided.hpp"        // the search over residuals on the baseline follower with a closed-loop tail (ftl_search_guided), same translation unit
 

@@ -13,7 +13,9 @@ recorded rows with the same arithmetic (``ftl_mlp_forward``): ``Critic`` is a he
 ``policy.forward(traj.obs[:-1])`` replays ``traj.head`` bit for bit.  ``backward()`` is its derivative with respect to the weights
 (``ftl_mlp_backward``), per set and in a fixed summation order, and ``Net`` ties the two together under torch autograd: an ``nn.Module``
 whose one parameter can share storage with ``policy.params`` or ``critic.params``, so one optimizer trains what the device plays.  The
-recurrent net has the same pair in ``rnn.py`` (``rnn.backward``, ``rnn.Net``)."""
+recurrent net has the same pair in ``rnn.py`` (``rnn.backward``, ``rnn.Net``).  Between the two, ``ppo_loss()`` is the PPO loss head of
+the Box policies on the device (``ftl_ppo_head``; ``ppo_head()`` is its raw form): from the new heads, the trajectory, the advantages
+and the critic's values to the head, value and ``log_std`` gradients, per weight set, for either net family."""
 import ctypes as C
 import functools
 
@@ -464,6 +466,165 @@ class Net(torch.nn.Module):
         if not 0 <= int(s) < self.n_sets:
             raise IndexError("set %d of %d" % (int(s), self.n_sets))
         return torch_module(self.widths, self.activation, self.params.detach()[int(s)])
+
+
+class PpoHead:
+    """What ``ppo_head`` returns: ``dhead`` float32 ``[..., N, A]``, ``dvalue`` float32 ``[..., N]`` (None without a value part), ``dlog_std``
+    float32 ``[n_sets, A]`` and ``stats`` float64 ``[n_sets, abi.FTL_PPO_STATS]`` -- count, advantage mean and std, policy loss, value loss,
+    approximate KL, clip fraction, total loss, per weight set."""
+
+    def __init__(self, dhead, dvalue, dlog_std, stats):
+        self.dhead, self.dvalue, self.dlog_std, self.stats = dhead, dvalue, dlog_std, stats
+
+
+_PPO_WORKSPACE = {}
+
+
+def ppo_head(head, head_old, noise, sigma_old, sigma, adv, ret, kind, value=None, log_sigma_shift=None, clip=0.2, vf_coef=0.5,
+             normalize=True, out=None):
+    """The PPO loss head of a Box policy in one call on the current stream (``ftl_ppo_head``, four launches, no host synchronisation): from
+    the new ``head`` float32 ``[..., N, A]`` (A = 2 or 1; ``Net`` or ``rnn.Net`` on the recorded rows), the record's ``head_old`` and
+    ``noise`` of that shape, ``sigma_old`` / ``sigma`` float32 ``[n_sets, A]`` (``n_sets`` must divide N; row r of a block uses set
+    ``r // (N // n_sets)``), ``adv`` / ``ret`` float32 and ``kind`` uint8 ``[..., N]`` and, optionally, the critic's ``value`` float32
+    ``[..., N]``, to a ``PpoHead``: the gradients of
+
+        sum over sets of  mean over the set's valid rows of  -min(r a, clip(r, 1 - clip, 1 + clip) a) + vf_coef * 0.5 (value - ret)^2
+
+    with respect to every head, every value and ``log_std`` (``log_sigma_shift`` is ``log_std_new - log_std_old`` ``[n_sets, A]``, zeros
+    when None), and the statistics table.  ``normalize`` standardises the advantages per set over its valid rows.  Rows whose kind is
+    ``FTL_TR_VOID`` get zero gradients and count nowhere.  The arithmetic is fixed operation by operation and the sums run in a fixed
+    order (include/ftl.h; tests/ppo_numpy.py is the twin), so ``dhead`` -- the ``dy`` of ``backward`` -- does not depend on the machine
+    or the launch.  ``out=`` reuses a ``PpoHead``.  All tensors are detached, contiguous and on one GPU: every mismatch is a ``ValueError``
+    before any library call, a head width other than 1 or 2 a ``NotImplementedError``."""
+    if not (torch.is_tensor(head) and head.dtype == torch.float32 and head.dim() >= 2 and head.is_contiguous()):
+        raise ValueError("head must be a contiguous float32 [..., N, A] tensor")
+    lead, N, A = tuple(head.shape[:-2]), int(head.shape[-2]), int(head.shape[-1])
+    if A not in (1, 2):
+        raise NotImplementedError("ppo_head() takes the Box heads, 2 or 1 wide, not %d (Discrete(5) needs a pinned logarithm)" % A)
+    blocks = 1
+    for d in lead:
+        blocks *= int(d)
+    if N < 1 or blocks < 1:
+        raise ValueError("head must hold at least one block of at least one row, not %s" % (list(head.shape),))
+    dev = head.device
+
+    def check(name, t, shape, dtype=torch.float32):
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == dev
+                and not t.requires_grad):
+            raise ValueError("%s must be a detached contiguous %s %s tensor on head's device" % (name, dtype, list(shape)))
+
+    if head.requires_grad:
+        raise ValueError("head must be detached: ppo_head() returns the gradients, ppo_loss() is the autograd form")
+    check("head_old", head_old, head.shape)
+    check("noise", noise, head.shape)
+    if not (torch.is_tensor(sigma) and sigma.dim() == 2 and sigma.shape[0] >= 1):
+        raise ValueError("sigma must be a float32 [n_sets, %d] tensor" % A)
+    n_sets = int(sigma.shape[0])
+    check("sigma", sigma, (n_sets, A))
+    check("sigma_old", sigma_old, (n_sets, A))
+    if log_sigma_shift is not None:
+        check("log_sigma_shift", log_sigma_shift, (n_sets, A))
+    if N % n_sets:
+        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
+    check("adv", adv, lead + (N,))
+    check("ret", ret, lead + (N,))
+    check("kind", kind, lead + (N,), torch.uint8)
+    if value is not None:
+        check("value", value, lead + (N,))
+    clip, vf_coef = float(clip), float(vf_coef)
+    if not 0.0 <= clip < float("inf"):
+        raise ValueError("clip must be a finite number of at least 0, not %r" % (clip,))
+    if out is not None:
+        if not isinstance(out, PpoHead):
+            raise ValueError("out must be a PpoHead")
+        check("out.dhead", out.dhead, head.shape)
+        check("out.dlog_std", out.dlog_std, (n_sets, A))
+        check("out.stats", out.stats, (n_sets, abi.FTL_PPO_STATS), torch.float64)
+        if value is not None:
+            check("out.dvalue", out.dvalue, lead + (N,))
+        elif out.dvalue is not None:
+            raise ValueError("out.dvalue must be None without value")
+    if not head.is_cuda:
+        raise ValueError("head must lie on a GPU device")
+    if out is None:
+        out = PpoHead(torch.empty_like(head), torch.empty_like(value) if value is not None else None,
+                      torch.empty(n_sets, A, dtype=torch.float32, device=dev), torch.empty(n_sets, abi.FTL_PPO_STATS, dtype=torch.float64, device=dev))
+    lib = _lib.load()
+    h = _device_handle(dev)
+    need = lib.ftl_sizeof_ppo_head_workspace(blocks, N, n_sets)
+    if need < 0:
+        raise NotImplementedError("ftl_ppo_head: more than 2^31 - 1 segments in one call; split the blocks")
+    raw = torch.cuda.current_stream(dev).cuda_stream
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), raw)
+    ws = _PPO_WORKSPACE.get(key)
+    if ws is None or ws.numel() * 8 < need:
+        ws = _PPO_WORKSPACE[key] = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+    a = abi.PpoHeadArgs()
+    a.n_blocks, a.n, a.n_sets, a.width = blocks, N, n_sets, A
+    a.head_new, a.head_old, a.noise = head.data_ptr(), head_old.data_ptr(), noise.data_ptr()
+    a.head_new_block_bytes = a.head_old_block_bytes = a.noise_block_bytes = a.dhead_block_bytes = N * A * 4
+    a.sigma_old, a.sigma_new = sigma_old.data_ptr(), sigma.data_ptr()
+    a.log_sigma_shift = log_sigma_shift.data_ptr() if log_sigma_shift is not None else None
+    a.adv, a.ret, a.kind = adv.data_ptr(), ret.data_ptr(), kind.data_ptr()
+    a.adv_block_bytes = a.ret_block_bytes = a.value_new_block_bytes = a.dvalue_block_bytes = N * 4
+    a.kind_block_bytes = N
+    a.value_new = value.data_ptr() if value is not None else None
+    a.clip_lo, a.clip_hi, a.vf_coef, a.normalize = 1.0 - clip, 1.0 + clip, vf_coef, 1 if normalize else 0
+    a.dhead, a.dvalue = out.dhead.data_ptr(), out.dvalue.data_ptr() if value is not None else None
+    a.dlog_std, a.stats = out.dlog_std.data_ptr(), out.stats.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    _lib.check(lib.ftl_ppo_head(h, C.byref(a), C.c_void_p(raw)), lib)
+    return out
+
+
+class _PpoLossFunction(torch.autograd.Function):
+    """The scalar loss of ``ppo_head`` with its ``dhead``, ``dvalue`` and ``dlog_std`` as the derivative."""
+
+    @staticmethod
+    def forward(ctx, head, value, log_std, head_old, noise, sigma_old, log_std_old, adv, ret, kind, clip, vf_coef, normalize):
+        ls = log_std.detach()
+        r = ppo_head(head.detach().contiguous(), head_old, noise, sigma_old, ls.exp(), adv, ret, kind,
+                     value.detach().contiguous() if value is not None else None, (ls - log_std_old).contiguous(), clip, vf_coef, normalize)
+        ctx.save_for_backward(r.dhead, r.dlog_std, *(() if r.dvalue is None else (r.dvalue,)))
+        ctx.mark_non_differentiable(r.stats)
+        return r.stats[:, 7].sum().to(torch.float32), r.stats
+
+    @staticmethod
+    def backward(ctx, gloss, gstats):
+        dhead, dlog_std, *dvalue = ctx.saved_tensors
+        return (dhead * gloss, dvalue[0] * gloss if dvalue else None, dlog_std * gloss) + (None,) * 10
+
+
+def ppo_loss(traj, head, log_std, adv, ret, value=None, log_std_old=None, clip=0.2, vf_coef=0.5, normalize=True):
+    """The PPO loss of a recorded trajectory under autograd, on the device (``ppo_head``): ``traj`` is the ``Trajectory`` of ``collect()``
+    or of the recurrent ``collect_rnn`` (its ``head``, ``noise``, ``sigma`` and ``kind`` are read), ``head`` the new heads ``[T, N, A]``
+    of ``Net`` or ``rnn.Net`` on its rows, ``log_std`` the float32 ``[n_sets, A]`` parameter, ``adv`` / ``ret`` those of ``gae()``,
+    ``value`` the critic's new values ``[T, N]`` or ``[T, N, 1]`` (None: no value part).  ``log_std_old`` defaults to
+    ``traj.sigma.log()``.  Returns the scalar loss -- the sum over the weight sets of each set's mean over its valid rows, a float32
+    tensor with the float64 table ``.stats`` ``[n_sets, 8]`` attached --, and ``loss.backward()`` hands ``dhead``, ``dvalue`` and
+    ``dlog_std`` to autograd: ``opt.zero_grad(); mlp.ppo_loss(...).backward(); opt.step()`` is a PPO epoch for one net as for a
+    population, with no boolean-mask indexing, no host synchronisation and a ``dy`` that is pinned bit for bit.  The entropy bonus is
+    not included: with a state-independent sigma it is ``log_std.sum()`` plus a constant; add it in torch."""
+    for name in ("head", "noise", "sigma", "kind"):
+        if not torch.is_tensor(getattr(traj, name, None)):
+            raise ValueError("traj.%s is missing: ppo_loss() reads head, noise, sigma and kind of a stochastic trajectory" % name)
+    if not (torch.is_tensor(head) and head.dim() >= 2 and tuple(head.shape) == tuple(traj.head.shape)):
+        raise ValueError("head must have the shape of traj.head, %s" % (list(traj.head.shape),))
+    if not (torch.is_tensor(log_std) and log_std.dtype == torch.float32 and tuple(log_std.shape) == tuple(traj.sigma.shape)):
+        raise ValueError("log_std must be a float32 %s tensor, the shape of traj.sigma" % (list(traj.sigma.shape),))
+    if value is not None:
+        if torch.is_tensor(value) and value.dim() == head.dim() and value.shape[-1] == 1:
+            value = value[..., 0]
+        if not (torch.is_tensor(value) and tuple(value.shape) == tuple(head.shape[:-1])):
+            raise ValueError("value must be a [..., N] or [..., N, 1] tensor of head's leading shape")
+    if log_std_old is None:
+        log_std_old = traj.sigma.log()
+    if not (torch.is_tensor(log_std_old) and tuple(log_std_old.shape) == tuple(log_std.shape) and not log_std_old.requires_grad):
+        raise ValueError("log_std_old must be a detached tensor of log_std's shape")
+    loss, stats = _PpoLossFunction.apply(head, value, log_std, traj.head, traj.noise, traj.sigma.detach(), log_std_old, adv, ret, traj.kind,
+                                         clip, vf_coef, normalize)
+    loss.stats = stats
+    return loss
 
 
 class MlpPolicy:

@@ -1071,6 +1071,96 @@ int ftl_mlp_backward(const ftl_handle* h /* device only */, const ftl_mlp* net,
                      float* grad,                              /* [n_sets][set_stride] f32, the layout of params */
                      void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the PPO loss head on recorded rows: from heads, record, advantages and values to dhead, dvalue, d log_std and statistics ----------
+ * ftl_ppo_head (ftl_ppo_moments_kernel, ftl_ppo_scalars_kernel, ftl_ppo_rows_kernel, ftl_ppo_stats_kernel, csrc/ftl_ppo.hpp: four
+ * launches on `stream`, asynchronous, nothing synchronises with the host; the handle only names the device, as for ftl_gae) is the piece
+ * between ftl_mlp_forward / ftl_rnn_forward and ftl_mlp_backward / ftl_rnn_backward: the clipped-surrogate loss of PPO with a value term
+ * for Box heads (width A = 2, or 1 under constant_follower_speed) with a state-independent Gaussian deviation per weight set, and its
+ * derivative with respect to every head, every value and log_std.  Per set s
+ *     loss_s = mean over the set's valid rows of [ -min(r * a, clip(r) * a) + vf_coef * 0.5 * (v - ret)^2 ]
+ * and the total loss is the sum over the sets, so the gradient of a set depends on its rows alone.  The entropy bonus is not here: with a
+ * state-independent sigma it is sum(log_std) plus a constant and touches no row.
+ *   Inputs      device pointers; block b of an array lies at base + b * its *_block_bytes.  n_sets must divide n; row r of every block
+ *               uses set r / (n / n_sets), the rule of ftl_mlp_forward.  head_new, head_old (the recorded head) and noise are float32
+ *               [n][A] a block; sigma_old, sigma_new and log_sigma_shift float32 [n_sets][A] -- log_sigma_shift is the caller's
+ *               c = log_std_new - log_std_old, NULL reads as +0 --; adv, ret and value_new float32 [n] a block; value_new == NULL means no
+ *               value part (dvalue must then be NULL too, and the reverse); kind uint8 [n] a block: FTL_TR_VOID rows are left out, any
+ *               other byte is a row to learn from, as in ftl_gae.  clip_lo and clip_hi are 1 -+ eps rounded once on the host; normalize
+ *               is 0 or 1.
+ *   Outputs     dhead float32 [n][A] a block, dvalue float32 [n] a block, dlog_std float32 [n_sets][A], stats float64
+ *               [n_sets][FTL_PPO_STATS].  Every word of every output is overwritten (block padding is not touched); FTL_TR_VOID rows get
+ *               +0.  The result is a pure function of the arguments: no atomics, no dependence on the machine, the grid or timing.
+ *               tests/ppo_numpy.py is the twin and the device is pinned to it bit for bit.
+ *   Row         float32, one IEEE rounding per line; div32 and exp32 are those of csrc/ftl_rnn_math.hpp; csrc/ftl_ppo_math.hpp is these
+ *               lines for host and device.  Per component j:
+ *                 e   = head_old_j - head_new_j
+ *                 t   = fmaf(sigma_old_j, noise_j, e)
+ *                 u_j = div32(t, sigma_new_j)
+ *                 p_j = u_j * u_j
+ *                 q   = noise_j * noise_j
+ *                 w   = q - p_j
+ *                 l_j = fmaf(0.5f, w, -c_j)
+ *               per row:
+ *                 d  = l_0 (A = 1), l_0 + l_1 (A = 2)
+ *                 r  = d if d is NaN; exp32(d) if d <= 0; div32(1.0f, exp32(-d)) otherwise
+ *                 a  = adv without normalisation; am = adv - mean32_s, a = am * inv32_s with it
+ *                 s1 = r * a
+ *                 rc = fminf(fmaxf(r, clip_lo), clip_hi)
+ *                 s2 = rc * a
+ *                 active = !(s2 < s1)                    (a NaN row propagates; a tie goes through s1, as torch's does inside the range)
+ *                 g  = -(s1 * invc_s) if active, else +0
+ *                 dhead_j = g * div32(u_j, sigma_new_j)
+ *                 k_j = g * (p_j - 1.0f)                 (the row's share of d loss / d log_std_new_j; the subtraction is a line)
+ *                 hv = v - ret
+ *                 dvalue = (vf_coef * hv) * invc_s
+ *   Reductions  a segment is up to FTL_PPO_SEG consecutive rows of one set's slice of one block: a slice of fewer rows is one segment,
+ *               otherwise the last segment of a slice may be short.  Within a segment lane k of 64 sums the rows at offsets = k (mod 64),
+ *               ascending, in float64 from +0.0, FTL_TR_VOID rows skipped; then x[k] += x[k + stride] for stride 32, 16, 8, 4, 2, 1 and
+ *               x[0] is the segment's partial.  A set's total is the float64 sum from +0.0 of its partials in ascending (block,
+ *               segment) order.  Summed are, each a float32 value widened to float64: 1 (the count); adv; adv * adv, formed in float64;
+ *               -(active ? s1 : s2); 0.5f * (hv * hv) (the product is a line); -d; 1 where r < clip_lo || r > clip_hi; k_0; k_1.
+ *   Set scalars float64, one rounding per operation: mean = S1 / cnt; var = ((S2 - S1 * mean) / (cnt - 1)), replaced by +0 where it is
+ *               below 0 (a NaN stays), and +0 when cnt < 2; std = sqrt(var); inv = 1 / (std + 1e-8); mean32 and inv32 are mean and inv
+ *               rounded to float32; invc = (float)(1.0 / cnt), +0 when cnt = 0.  mean is +0 when cnt = 0.
+ *   Stats       column 0 count, 1 advantage mean, 2 advantage std, 3 policy loss (total / cnt), 4 value loss, 5 approximate KL (the mean
+ *               of -d), 6 clip fraction, 7 column 3 + (double)vf_coef * column 4.  Means over an empty set are +0.0; columns 4 and 7 take
+ *               the value part as 0 when value_new is NULL.  dlog_std_j = (float) the set's total of k_j.
+ *   Workspace   ftl_sizeof_ppo_head_workspace(n_blocks, n, n_sets) bytes of device memory, 8-byte aligned, contents irrelevant before and
+ *               undefined after: segments * 72 + n_sets * 16 with segments = n_blocks * n_sets * ceil((n / n_sets) / FTL_PPO_SEG).  Pure
+ *               host arithmetic; -1 for counts that ftl_ppo_head refuses or more than 2^31 - 1 segments.
+ *   Aliasing    outputs and workspace must not overlap the inputs or each other (not checked).
+ *   FTL_E_UNSUPPORTED before any device work: a width other than 1 or 2 (Discrete(5) needs a pinned logarithm: the follow-up); more than
+ *   2^31 - 1 segments.  FTL_E_INVALID before any device work, each with a message that names ftl_ppo_head and the argument: NULL h, a, or
+ *   a required pointer; dvalue without value_new or the reverse; n_blocks < 1, n < 1, n_sets < 1 or not dividing n; a *_block_bytes below
+ *   one block or not a multiple of its element; a pointer not aligned to its element (A * 4 bytes for head_new, head_old, noise and
+ *   dhead, 8 for stats, 4 otherwise); clip_lo > clip_hi or either NaN; normalize other than 0 / 1; workspace_bytes below the query's
+ *   answer; last, a workspace that is not 8-byte aligned. */
+#define FTL_PPO_SEG 1024               /* rows of a segment: 16 a lane */
+#define FTL_PPO_STATS 8                /* columns of stats */
+typedef struct ftl_ppo_head_args {
+    int32_t n_blocks, n, n_sets, width;                            /* B; rows a block; weight sets; A */
+    const float* head_new; int64_t head_new_block_bytes;           /* [n][A] f32 a block */
+    const float* head_old; int64_t head_old_block_bytes;
+    const float* noise; int64_t noise_block_bytes;
+    const float* sigma_old;                                        /* [n_sets][A] f32 */
+    const float* sigma_new;
+    const float* log_sigma_shift;                                  /* [n_sets][A] f32, or NULL */
+    const float* adv; int64_t adv_block_bytes;                     /* [n] f32 a block */
+    const float* ret; int64_t ret_block_bytes;
+    const float* value_new; int64_t value_new_block_bytes;         /* [n] f32 a block, or NULL */
+    const uint8_t* kind; int64_t kind_block_bytes;                 /* [n] u8 a block */
+    float clip_lo, clip_hi, vf_coef;
+    int32_t normalize;
+    float* dhead; int64_t dhead_block_bytes;                       /* out: [n][A] f32 a block */
+    float* dvalue; int64_t dvalue_block_bytes;                     /* out: [n] f32 a block, or NULL */
+    float* dlog_std;                                               /* out: [n_sets][A] f32 */
+    double* stats;                                                 /* out: [n_sets][FTL_PPO_STATS] f64 */
+    void* workspace; int64_t workspace_bytes;
+} ftl_ppo_head_args;
+size_t ftl_sizeof_ppo_head_args(void);
+int64_t ftl_sizeof_ppo_head_workspace(int32_t n_blocks, int32_t n, int32_t n_sets);
+int ftl_ppo_head(const ftl_handle* h /* device only, as ftl_gae */, const ftl_ppo_head_args* a, void* stream);
+
 /* ---- recurrent policy: a trunk of dense ReLU layers, one LSTM cell and a linear head, as a decision, a rollout and a trajectory -------
  * The memoryless stack above (ftl_mlp_act, ftl_rollout_mlp, ftl_mlp_sample, ftl_collect_mlp) with a state per env that the caller owns
  * and the library zeroes at episode boundaries.  ftl_rnn_act (ftl_rnn_kernel, csrc/ftl_rnn.hpp, one launch per decision, asynchronous on
