@@ -566,34 +566,65 @@ static int64_t mlp_param_count(const int32_t* w, int32_t L) {
 
 static size_t mlp_action_bytes(int32_t head) { return head == FTL_ACTION_BOX2 ? 16 : head == FTL_ACTION_TURN ? 8 : 4; }
 
+// What mlp_net_check and rnn_net_check share; `pre` ("mlp: " / "rnn: ") heads the messages.  The widths width[0 .. last] ...
+static int net_widths_check(const char* pre, const int32_t* width, int32_t last) {
+    for (int l = 0; l <= last; l++) {
+        if (width[l] < 1) return fail(FTL_E_INVALID, std::string(pre) + "every width must be at least 1");
+        if (width[l] > (l == 0 ? FTL_MLP_MAX_IN : FTL_MLP_MAX_WIDTH))
+            return fail(FTL_E_UNSUPPORTED, std::string(pre) + (l == 0 ? "input width beyond FTL_MLP_MAX_IN" : "layer width beyond FTL_MLP_MAX_WIDTH"));
+    }
+    return FTL_OK;
+}
+
+// ... and the weight sets of an ftl_mlp or ftl_rnn for `n` rows: `count` is the net's parameter count, `counter` the name of its function
+template <typename Net>
+static int net_sets_check(const char* pre, const Net* net, int64_t count, const char* counter, int64_t n, const char* rows) {
+    if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, std::string(pre) + "params must be 4-byte aligned");
+    if (net->set_stride < count) return fail(FTL_E_INVALID, std::string(pre) + "set_stride below " + counter);
+    if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0)
+        return fail(FTL_E_INVALID, std::string(pre) + "n_sets and envs_per_set must be at least 1, env_first at least 0");
+    const int64_t eps = net->envs_per_set, first = net->env_first;
+    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, std::string(pre) + rows + " lies beyond the last weight set");
+    return FTL_OK;
+}
+
+// The tile map of `n` rows over the weight sets, which the kernels of both nets decode, forward and backward alike: the rows of the first
+// touched set (possibly cut) and of the last one (0: it is whole, or the first is the only one), the whole sets after the first, and the
+// tiles of each and of a block in all.  The one place that computes it: mlp_fill, rnn_fill, mlp_bwd_plan and rnn_bwd_plan read it.
+struct TileMap { int64_t len0, rem, full, last, tiles0, tiles_per_set, tiles_last, tiles; };
+static TileMap tile_map(int64_t env_first, int64_t envs_per_set, int64_t n) {
+    const int64_t eps = envs_per_set, tile = FTL_MLP_ENV_TILE;
+    TileMap m;
+    m.len0 = std::min<int64_t>(n, (env_first / eps + 1) * eps - env_first); m.rem = n - m.len0; m.full = m.rem / eps; m.last = m.rem % eps;
+    m.tiles0 = (m.len0 + tile - 1) / tile; m.tiles_per_set = (eps + tile - 1) / tile; m.tiles_last = (m.last + tile - 1) / tile;
+    m.tiles = m.tiles0 + m.full * m.tiles_per_set + m.tiles_last;
+    return m;
+}
+
+// ... into the kernel's arguments; returns the grid's tiles
+static unsigned tile_map_fill(const TileMap& m, ftlmlp::Args& a) {
+    a.len0 = (int32_t)m.len0; a.tiles0 = (int32_t)m.tiles0; a.tiles_per_set = (int32_t)m.tiles_per_set;
+    return (unsigned)m.tiles;
+}
+
 // the checks of the net itself, for `n` rows (the handle's envs, or the rows of a block of ftl_mlp_forward: `rows` names them in the last
 // message); `any_head` admits every head width of 1 .. FTL_MLP_MAX_WIDTH instead of those of the three action encodings
 static int mlp_net_check(const ftl_mlp* net, int64_t n, bool any_head, const char* rows) {
     const int32_t L = net->n_layers;
     if (L < 1) return fail(FTL_E_INVALID, "mlp: n_layers must be at least 1");
     if (L > FTL_MLP_MAX_LAYERS) return fail(FTL_E_UNSUPPORTED, "mlp: more than FTL_MLP_MAX_LAYERS layers");
-    for (int l = 0; l <= L; l++) {
-        if (net->width[l] < 1) return fail(FTL_E_INVALID, "mlp: every width must be at least 1");
-        if (net->width[l] > (l == 0 ? FTL_MLP_MAX_IN : FTL_MLP_MAX_WIDTH))
-            return fail(FTL_E_UNSUPPORTED, l == 0 ? "mlp: input width beyond FTL_MLP_MAX_IN" : "mlp: layer width beyond FTL_MLP_MAX_WIDTH");
-    }
+    if (int rc = net_widths_check("mlp: ", net->width, L)) return rc;
     const int32_t wl = net->width[L];
     if (!any_head && wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "mlp: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
     if (net->activation != FTL_MLP_ACT_RELU && net->activation != FTL_MLP_ACT_TANH)
         return fail(FTL_E_INVALID, "mlp: activation must be FTL_MLP_ACT_RELU (0) or FTL_MLP_ACT_TANH (1)");
-    if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "mlp: params must be 4-byte aligned");
-    if (net->set_stride < mlp_param_count(net->width, L)) return fail(FTL_E_INVALID, "mlp: set_stride below ftl_mlp_param_count");
-    if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "mlp: n_sets and envs_per_set must be at least 1, env_first at least 0");
-    const int64_t eps = net->envs_per_set, first = net->env_first;
-    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, std::string("mlp: ") + rows + " lies beyond the last weight set");
-    return FTL_OK;
+    return net_sets_check("mlp: ", net, mlp_param_count(net->width, L), "ftl_mlp_param_count", n, rows);
 }
 
 // the kernel's arguments that follow from a checked net and its `n` rows: everything but obs, head, the bounds and `action`; the grid's
 // tiles and the LDS bytes
 static void mlp_fill(const ftl_mlp* net, int64_t n, ftlmlp::Args& a, unsigned& grid, size_t& lds) {
     const int32_t L = net->n_layers;
-    const int64_t eps = net->envs_per_set, first = net->env_first;
     a.params = net->params; a.set_stride = net->set_stride;
     a.n_envs = (int32_t)n; a.n_layers = L; a.env_first = net->env_first; a.envs_per_set = net->envs_per_set;
     int wmax = 0;
@@ -602,10 +633,7 @@ static void mlp_fill(const ftl_mlp* net, int64_t n, ftlmlp::Args& a, unsigned& g
         if (l >= 1 && a.width[l] > wmax) wmax = a.width[l];
     }
     a.act_stride = ((wmax + 31) & ~31) + 2;
-    const int64_t tile = FTL_MLP_ENV_TILE;
-    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0;
-    a.len0 = (int32_t)len0; a.tiles0 = (int32_t)((len0 + tile - 1) / tile); a.tiles_per_set = (int32_t)((eps + tile - 1) / tile);
-    grid = (unsigned)(a.tiles0 + (rem / eps) * a.tiles_per_set + (rem % eps + tile - 1) / tile);
+    grid = tile_map_fill(tile_map(net->env_first, net->envs_per_set, n), a);
     lds = ((size_t)FTL_MLP_ENV_TILE * a.act_stride + (size_t)FTL_MLP_ENV_TILE * ftlmlp::XS + FTL_MLP_W_STAGE + 64) * sizeof(float);
 }
 
@@ -642,21 +670,95 @@ static int mlp_sample_check(const char* name, int32_t head, const float* noise, 
     return FTL_OK;
 }
 
+// The closed-loop rollout of a policy, for ftl_rollout_mlp and ftl_rollout_rnn; `name` heads the messages.  What comes before the checks
+// of the entry's own net ...
+static int policy_rollout_check(const char* name, const void* h, const void* out, const void* net, const ftl_rollout_outputs* ro, int32_t T,
+                                uint32_t flags) {
+    if (!h || !out || !net) return fail(FTL_E_INVALID, "null argument");
+    if (flags & FTL_STEP_NO_SENSORS)
+        return fail(FTL_E_INVALID, std::string(name) + " refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
+    return rollout_check(name, ro, T, 0, flags);
+}
+
+// ... and what comes after them: `head` is the net's action encoding, ready() whatever its kernel needs on the handle's device before
+// the first launch, decide(action) enqueues one decision that writes every env's encoded action to `action` (block t of the caller's
+// `actions`, or the handle's scratch)
+template <typename Ready, typename Decide>
+static int policy_rollout(const char* name, ftl_handle* h, int32_t head, int32_t T, double gamma, const ftl_outputs* out,
+                          const ftl_rollout_outputs* ro, void* actions, int64_t step_bytes, void* stream, Ready ready, Decide decide) {
+    const int64_t block = (int64_t)h->P.n_envs * (int64_t)mlp_action_bytes(head);
+    if (actions && step_bytes < block) return fail(FTL_E_INVALID, std::string(name) + ": step_bytes below one block of encoded actions");
+    if (actions && ((((uintptr_t)actions) | (uintptr_t)step_bytes) & (head == FTL_ACTION_DISCRETE ? 3 : 7)))
+        return fail(FTL_E_INVALID, std::string(name) + ": actions and step_bytes not aligned to the action element");
+    if (int rc = check_ready(h, out)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (int rc = ready()) return rc;
+    if (!actions && !h->bl_action) {                            // (16 bytes per env: any encoding fits the baseline's scratch)
+        hipError_t e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
+        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(policy actions): ") + hipGetErrorString(e));
+    }
+    if (int rc = rollout_scratch(h)) return rc;                 // (a recurrent decision reads h->ro_alive)
+    return rollout_loop(h, head, T, gamma, out, ro, 0, true, stream, [&](int32_t t) {
+        void* action = actions ? (void*)((char*)actions + (int64_t)t * step_bytes) : (void*)h->bl_action;
+        decide(action);
+        return action;
+    });
+}
+
 // the spans of ftl_mlp_backward for a checked net and its rows: those of the first touched set, of a whole set and of the last touched
 // set (0 when the first is the only one), the touched sets and the sum; false when the sum leaves the grid
 struct MlpBwdPlan { int64_t spans0, spans_mid, spans_last, n_touched, spans; };
 static MlpBwdPlan mlp_bwd_plan(const ftl_mlp* net, int64_t n_blocks, int64_t n) {
-    const int64_t eps = net->envs_per_set, first = net->env_first, tile = FTL_MLP_ENV_TILE, span = FTL_MLP_BWD_SPAN;
-    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0, full = rem / eps, last = rem % eps;
-    auto spans_of = [&](int64_t rows) { return (n_blocks * ((rows + tile - 1) / tile) + span - 1) / span; };
+    const TileMap m = tile_map(net->env_first, net->envs_per_set, n);
+    auto spans_of = [&](int64_t tiles) { return (n_blocks * tiles + FTL_MLP_BWD_SPAN - 1) / FTL_MLP_BWD_SPAN; };
     MlpBwdPlan p;
-    p.spans0 = spans_of(len0);
-    p.spans_mid = rem ? spans_of(eps) : 1;
-    p.spans_last = !rem ? 0 : last ? spans_of(last) : p.spans_mid;
-    p.n_touched = 1 + full + (last ? 1 : 0);
-    p.spans = p.spans0 + full * p.spans_mid + (last ? p.spans_last : 0);
+    p.spans0 = spans_of(m.tiles0);
+    p.spans_mid = m.rem ? spans_of(m.tiles_per_set) : 1;
+    p.spans_last = !m.rem ? 0 : m.last ? spans_of(m.tiles_last) : p.spans_mid;
+    p.n_touched = 1 + m.full + (m.last ? 1 : 0);
+    p.spans = p.spans0 + m.full * p.spans_mid + (m.last ? p.spans_last : 0);
     return p;
 }
+
+// What ftl_mlp_forward and ftl_mlp_backward check alike, in their common order, between the checks of their own: `name` heads the
+// messages, `limit` is the entry's text for more than 65,535 blocks, `io` ("y" / "dy") names the rows `r` beside x
+struct MlpRows {
+    const char *name, *limit, *io;
+    const ftl_handle* h; const ftl_mlp* net; int32_t n_blocks, n;
+    const float* x; int64_t x_block_bytes; const float* r; int64_t r_block_bytes;
+    int no(int code, const std::string& what) const { return fail(code, std::string(name) + ": " + what); }
+    int nulls() const {
+        if (!h) return no(FTL_E_INVALID, "null argument: h");
+        if (!net) return no(FTL_E_INVALID, "null argument: net");
+        if (!net->params) return no(FTL_E_INVALID, "null argument: net->params");
+        if (!x) return no(FTL_E_INVALID, "null argument: x");
+        if (!r) return no(FTL_E_INVALID, std::string("null argument: ") + io);
+        return FTL_OK;
+    }
+    int shape() const {
+        if (n_blocks < 1 || n < 1) return no(FTL_E_INVALID, "n_blocks and n must be at least 1");
+        if (n_blocks > 65535) return no(FTL_E_UNSUPPORTED, limit);
+        return mlp_net_check(net, n, true, "the last row");
+    }
+    int block_bytes() const {
+        const int64_t w0 = net->width[0], wl = net->width[net->n_layers];
+        if (x_block_bytes < (int64_t)n * w0 * 4 || (x_block_bytes & 3))
+            return no(FTL_E_INVALID, "x_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
+        if (r_block_bytes < (int64_t)n * wl * 4 || (r_block_bytes & 3))
+            return no(FTL_E_INVALID, std::string(io) + "_block_bytes must be a multiple of 4 of at least one block, n * width[L] * 4");
+        return FTL_OK;
+    }
+    int aligned() const {
+        if (((uintptr_t)x) & 3) return no(FTL_E_INVALID, "x must be 4-byte aligned");
+        if (((uintptr_t)r) & 3) return no(FTL_E_INVALID, std::string(io) + " must be 4-byte aligned");
+        return FTL_OK;
+    }
+    // the kernel's arguments of a block's rows: no head map, no bounds, no action
+    void fill(ftlmlp::Args& a, unsigned& grid, size_t& lds) const {
+        mlp_fill(net, n, a, grid, lds);
+        a.obs = x; a.head = 0; a.lo0 = a.hi0 = a.lo1 = a.hi1 = 0.0; a.action = nullptr;
+    }
+};
 
 extern "C" {
 
@@ -693,52 +795,26 @@ int ftl_mlp_sample(ftl_handle* h, const ftl_outputs* out, const ftl_mlp* net, co
 
 int ftl_rollout_mlp(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_mlp* net,
                     void* actions, int64_t step_bytes, uint32_t flags, void* stream) {
-    if (!h || !out || !net) return fail(FTL_E_INVALID, "null argument");
-    if (flags & FTL_STEP_NO_SENSORS)
-        return fail(FTL_E_INVALID, "ftl_rollout_mlp refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
-    if (int rc = rollout_check("ftl_rollout_mlp", ro, T, 0, flags)) return rc;
+    if (int rc = policy_rollout_check("ftl_rollout_mlp", h, out, net, ro, T, flags)) return rc;
     ftlmlp::Args a; unsigned grid; size_t lds;
     if (int rc = mlp_args(h, out, net, a, grid, lds)) return rc;
-    const int64_t block = (int64_t)h->P.n_envs * (int64_t)mlp_action_bytes(a.head);
-    if (actions && step_bytes < block) return fail(FTL_E_INVALID, "ftl_rollout_mlp: step_bytes below one block of encoded actions");
-    if (actions && ((((uintptr_t)actions) | (uintptr_t)step_bytes) & (a.head == FTL_ACTION_DISCRETE ? 3 : 7)))
-        return fail(FTL_E_INVALID, "ftl_rollout_mlp: actions and step_bytes not aligned to the action element");
-    if (int rc = check_ready(h, out)) return rc;
-    if (int rc = set_device(h)) return rc;
-    if (!actions && !h->bl_action) {                            // (16 bytes per env: any encoding fits the baseline's scratch)
-        hipError_t e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
-        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(policy actions): ") + hipGetErrorString(e));
-    }
-    return rollout_loop(h, a.head, T, gamma, out, ro, 0, true, stream, [&](int32_t t) {
-        a.action = actions ? (void*)((char*)actions + (int64_t)t * step_bytes) : (void*)h->bl_action;
-        mlp_launch(net, a, nullptr, grid, lds, stream);
-        return a.action;
-    });
+    return policy_rollout("ftl_rollout_mlp", h, a.head, T, gamma, out, ro, actions, step_bytes, stream, [] { return (int)FTL_OK; },
+                          [&](void* action) { a.action = action; mlp_launch(net, a, nullptr, grid, lds, stream); });
 }
 
 int ftl_mlp_forward(const ftl_handle* h, const ftl_mlp* net, int32_t n_blocks, int32_t n, const float* x, int64_t x_block_bytes,
                     float* y, int64_t y_block_bytes, void* stream) {
-    if (!h) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: h");
-    if (!net) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: net");
-    if (!net->params) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: net->params");
-    if (!x) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: x");
-    if (!y) return fail(FTL_E_INVALID, "ftl_mlp_forward: null argument: y");
-    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_mlp_forward: n_blocks and n must be at least 1");
-    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_forward: n_blocks beyond 65,535 (the blocks are the grid's second dimension)");
-    if (int rc = mlp_net_check(net, n, true, "the last row")) return rc;
-    const int64_t w0 = net->width[0], wl = net->width[net->n_layers];
-    if (x_block_bytes < (int64_t)n * w0 * 4 || (x_block_bytes & 3))
-        return fail(FTL_E_INVALID, "ftl_mlp_forward: x_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
-    if (y_block_bytes < (int64_t)n * wl * 4 || (y_block_bytes & 3))
-        return fail(FTL_E_INVALID, "ftl_mlp_forward: y_block_bytes must be a multiple of 4 of at least one block, n * width[L] * 4");
+    const MlpRows r{"ftl_mlp_forward", "n_blocks beyond 65,535 (the blocks are the grid's second dimension)", "y",
+                    h, net, n_blocks, n, x, x_block_bytes, y, y_block_bytes};
+    if (int rc = r.nulls()) return rc;
+    if (int rc = r.shape()) return rc;
+    if (int rc = r.block_bytes()) return rc;
     ftlmlp::Args a; unsigned grid; size_t lds;
-    mlp_fill(net, n, a, grid, lds);
+    r.fill(a, grid, lds);
     if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull)       // (a grid dimension counts threads in 32 bits: 2^24 tiles, over 5e8 rows a block)
         return fail(FTL_E_UNSUPPORTED, "ftl_mlp_forward: n beyond the 2^24 - 1 tiles of one launch; split the rows into blocks");
-    if (((uintptr_t)x) & 3) return fail(FTL_E_INVALID, "ftl_mlp_forward: x must be 4-byte aligned");
-    if (((uintptr_t)y) & 3) return fail(FTL_E_INVALID, "ftl_mlp_forward: y must be 4-byte aligned");
+    if (int rc = r.aligned()) return rc;
     if (int rc = set_device(h)) return rc;
-    a.obs = x; a.head = 0; a.lo0 = a.hi0 = a.lo1 = a.hi1 = 0.0; a.action = nullptr;
     const ftlmlp::Forward fw{x_block_bytes, y, y_block_bytes};
     hipLaunchKernelGGL(net->activation == FTL_MLP_ACT_TANH ? ftlmlp::ftl_mlp_forward_tanh_kernel : ftlmlp::ftl_mlp_forward_kernel,
                        dim3(grid, (unsigned)n_blocks), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, fw);
@@ -754,36 +830,27 @@ int64_t ftl_sizeof_mlp_backward_workspace(const ftl_mlp* net, int32_t n_blocks, 
 
 int ftl_mlp_backward(const ftl_handle* h, const ftl_mlp* net, int32_t n_blocks, int32_t n, const float* x, int64_t x_block_bytes,
                      const float* dy, int64_t dy_block_bytes, float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!h) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: h");
-    if (!net) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: net");
-    if (!net->params) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: net->params");
-    if (!x) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: x");
-    if (!dy) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: dy");
+    const MlpRows r{"ftl_mlp_backward", "n_blocks beyond 65,535 (the limit of ftl_mlp_forward)", "dy",
+                    h, net, n_blocks, n, x, x_block_bytes, dy, dy_block_bytes};
+    if (int rc = r.nulls()) return rc;
     if (!grad) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: grad");
     if (!workspace) return fail(FTL_E_INVALID, "ftl_mlp_backward: null argument: workspace");
-    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_mlp_backward: n_blocks and n must be at least 1");
-    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: n_blocks beyond 65,535 (the limit of ftl_mlp_forward)");
-    if (int rc = mlp_net_check(net, n, true, "the last row")) return rc;
+    if (int rc = r.shape()) return rc;
     if (net->width[0] > FTL_MLP_BWD_MAX_IN) return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: input width beyond FTL_MLP_BWD_MAX_IN");
-    const int64_t w0 = net->width[0], wl = net->width[net->n_layers];
-    if (x_block_bytes < (int64_t)n * w0 * 4 || (x_block_bytes & 3))
-        return fail(FTL_E_INVALID, "ftl_mlp_backward: x_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
-    if (dy_block_bytes < (int64_t)n * wl * 4 || (dy_block_bytes & 3))
-        return fail(FTL_E_INVALID, "ftl_mlp_backward: dy_block_bytes must be a multiple of 4 of at least one block, n * width[L] * 4");
+    if (int rc = r.block_bytes()) return rc;
     ftlmlp::Args a; unsigned grid; size_t lds;
-    mlp_fill(net, n, a, grid, lds);
+    r.fill(a, grid, lds);
+    const int64_t wl = net->width[net->n_layers];
     const MlpBwdPlan p = mlp_bwd_plan(net, n_blocks, n);
     if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull || (uint64_t)p.spans * FTL_MLP_THREADS > 0xFFFFFFFFull)
         return fail(FTL_E_UNSUPPORTED, "ftl_mlp_backward: n beyond the 2^24 - 1 tiles of a block, or beyond 2^24 - 1 spans in all; split the rows");
     const int64_t count = mlp_param_count(net->width, net->n_layers);
     if (workspace_bytes < p.spans * count * 4)
         return fail(FTL_E_INVALID, "ftl_mlp_backward: workspace_bytes below ftl_sizeof_mlp_backward_workspace");
-    if (((uintptr_t)x) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: x must be 4-byte aligned");
-    if (((uintptr_t)dy) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: dy must be 4-byte aligned");
+    if (int rc = r.aligned()) return rc;
     if (((uintptr_t)grad) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: grad must be 4-byte aligned");
     if (((uintptr_t)workspace) & 3) return fail(FTL_E_INVALID, "ftl_mlp_backward: workspace must be 4-byte aligned");
     if (int rc = set_device(h)) return rc;
-    a.obs = x; a.head = 0; a.lo0 = a.hi0 = a.lo1 = a.hi1 = 0.0; a.action = nullptr;
     // LDS: a buffer per hidden layer and one for dy, the input chunk and the weight stage (a chunk's rows at the wider of the two strides)
     size_t stage = 0;
     for (int l = 1; l <= net->n_layers; l++) {

@@ -3,7 +3,9 @@
 // closed-loop steps (ftl_rollout_rnn), a recorded trajectory (ftl_collect_rnn), and the net put back over a recorded sequence in one
 // launch (ftl_rnn_forward, ftl_rnn_forward_kernel: further down, with its own comment).  Included by ftl_abi.hip after ftl_collect.hpp (same
 // translation unit: it reads the handle, uses the head maps of ftl_mlp.hpp and the record kernel of ftl_collect.hpp, and hands its
-// kernel to rollout_loop, which owns the steps; there is no second loop here).
+// kernel to rollout_loop, which owns the steps; there is no second loop here).  The host side shares with ftl_mlp.hpp the tile map
+// (tile_map), the width and set checks, and the closed-loop rollout of a policy (policy_rollout), with ftl_collect.hpp the one collect
+// (collect_loop); RnnSeq holds what ftl_rnn_forward and ftl_rnn_backward check and fill alike.
 //
 // ftl_rnn_kernel keeps the plan of ftl_mlp_kernel: one workgroup of 256 threads per tile of up to FTL_MLP_ENV_TILE envs of ONE weight set,
 // everything in one launch, activations in LDS between the layers, a layer's weights staged in LDS in k-chunks, the products on
@@ -924,23 +926,14 @@ static int rnn_net_check(const ftl_rnn* net, int64_t n, const char* rows) {
     const int32_t Lt = net->n_layers;
     if (Lt < 1) return fail(FTL_E_INVALID, "rnn: n_layers must be at least 1");
     if (Lt > FTL_MLP_MAX_LAYERS - 1) return fail(FTL_E_UNSUPPORTED, "rnn: more than FTL_MLP_MAX_LAYERS - 1 trunk layers");
-    for (int l = 0; l <= Lt + 1; l++) {
-        if (net->width[l] < 1) return fail(FTL_E_INVALID, "rnn: every width must be at least 1");
-        if (net->width[l] > (l == 0 ? FTL_MLP_MAX_IN : FTL_MLP_MAX_WIDTH))
-            return fail(FTL_E_UNSUPPORTED, l == 0 ? "rnn: input width beyond FTL_MLP_MAX_IN" : "rnn: layer width beyond FTL_MLP_MAX_WIDTH");
-    }
+    if (int rc = net_widths_check("rnn: ", net->width, Lt + 1)) return rc;
     if (net->cell < 1) return fail(FTL_E_INVALID, "rnn: cell must be at least 1");
     if (net->cell > FTL_RNN_MAX_CELL) return fail(FTL_E_UNSUPPORTED, "rnn: cell beyond FTL_RNN_MAX_CELL");
     if (net->flags & ~(uint32_t)(FTL_RNN_PREV_ACTION | FTL_RNN_PREV_REWARD)) return fail(FTL_E_INVALID, "rnn: unknown bit in ftl_rnn.flags");
     if (net->activation != FTL_MLP_ACT_RELU) return fail(FTL_E_UNSUPPORTED, "rnn: the trunk is ReLU: ftl_rnn.activation must be FTL_MLP_ACT_RELU (0)");
     const int32_t wl = net->width[Lt + 1], C = net->cell;
     if (wl != 1 && wl != 2 && wl != 5) return fail(FTL_E_INVALID, "rnn: the head width must be 2 (Box(2)), 1 (Box(1) turn) or 5 (Discrete(5))");
-    if (((uintptr_t)net->params) & 3) return fail(FTL_E_INVALID, "rnn: params must be 4-byte aligned");
-    if (net->set_stride < rnn_param_count(net->width, Lt, C, net->flags)) return fail(FTL_E_INVALID, "rnn: set_stride below ftl_rnn_param_count");
-    if (net->n_sets < 1 || net->envs_per_set < 1 || net->env_first < 0) return fail(FTL_E_INVALID, "rnn: n_sets and envs_per_set must be at least 1, env_first at least 0");
-    const int64_t eps = net->envs_per_set, first = net->env_first;
-    if ((first + n - 1) / eps >= net->n_sets) return fail(FTL_E_INVALID, std::string("rnn: ") + rows + " lies beyond the last weight set");
-    return FTL_OK;
+    return net_sets_check("rnn: ", net, rnn_param_count(net->width, Lt, C, net->flags), "ftl_rnn_param_count", n, rows);
 }
 
 // ... and of its state block
@@ -956,7 +949,6 @@ static int rnn_state_check(const ftl_rnn* net) {
 // tiles, the LDS strides of u and h'
 static void rnn_fill(const ftl_rnn* net, int64_t n, ftlmlp::Args& m, int32_t& u_stride, int32_t& h_stride, unsigned& grid) {
     const int32_t Lt = net->n_layers, wl = net->width[Lt + 1], C = net->cell;
-    const int64_t eps = net->envs_per_set, first = net->env_first;
     m.params = net->params; m.set_stride = net->set_stride;
     m.n_envs = (int32_t)n; m.n_layers = Lt; m.env_first = net->env_first; m.envs_per_set = net->envs_per_set;
     int wmax = wl;                                              // act holds the trunk's inner layers and y
@@ -965,10 +957,7 @@ static void rnn_fill(const ftl_rnn* net, int64_t n, ftlmlp::Args& m, int32_t& u_
         if (l >= 1 && l < Lt && m.width[l] > wmax) wmax = m.width[l];
     }
     m.act_stride = ((wmax + 31) & ~31) + 2;
-    const int64_t tile = FTL_MLP_ENV_TILE;
-    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0;
-    m.len0 = (int32_t)len0; m.tiles0 = (int32_t)((len0 + tile - 1) / tile); m.tiles_per_set = (int32_t)((eps + tile - 1) / tile);
-    grid = (unsigned)(m.tiles0 + (rem / eps) * m.tiles_per_set + (rem % eps + tile - 1) / tile);
+    grid = tile_map_fill(tile_map(net->env_first, net->envs_per_set, n), m);
     m.head = wl == 2 ? FTL_ACTION_BOX2 : wl == 1 ? FTL_ACTION_TURN : FTL_ACTION_DISCRETE;
     m.action = nullptr;
     const int U = net->width[Lt] + rnn_prev_width(wl, net->flags) + ((net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0) + C;
@@ -1010,22 +999,22 @@ static int rnn_kernel_ready(size_t lds, const void* kernel = (const void*)ftlrnn
 // last (0 when the first is the only one) -- and in all
 struct RnnBwdPlan { int64_t G, spg, groups0, groups_mid, groups, spans0, spans_mid, spans_last, n_touched, spans; };
 static RnnBwdPlan rnn_bwd_plan(const ftl_rnn* net, int64_t B, int64_t n) {
-    const int64_t eps = net->envs_per_set, first = net->env_first, tile = FTL_MLP_ENV_TILE, span = FTL_RNN_BWD_SPAN;
-    const int64_t len0 = std::min<int64_t>(n, (first / eps + 1) * eps - first), rem = n - len0, full = rem / eps, last = rem % eps;
+    const TileMap m = tile_map(net->env_first, net->envs_per_set, n);
+    const int64_t span = FTL_RNN_BWD_SPAN;
     RnnBwdPlan p;
     p.G = std::max<int64_t>(1, span / B);
     p.spg = (p.G * B + span - 1) / span;
-    auto groups_of = [&](int64_t rows) { return ((rows + tile - 1) / tile + p.G - 1) / p.G; };
-    auto spans_of = [&](int64_t rows) {
-        const int64_t tiles = (rows + tile - 1) / tile, cut = tiles % p.G;
+    auto groups_of = [&](int64_t tiles) { return (tiles + p.G - 1) / p.G; };
+    auto spans_of = [&](int64_t tiles) {
+        const int64_t cut = tiles % p.G;
         return (tiles / p.G) * p.spg + (cut ? (cut * B + span - 1) / span : 0);
     };
-    p.groups0 = groups_of(len0); p.groups_mid = rem ? groups_of(eps) : 1;
-    p.groups = p.groups0 + full * p.groups_mid + (last ? groups_of(last) : 0);
-    p.spans0 = spans_of(len0); p.spans_mid = rem ? spans_of(eps) : 1;
-    p.spans_last = !rem ? 0 : last ? spans_of(last) : p.spans_mid;
-    p.n_touched = 1 + full + (last ? 1 : 0);
-    p.spans = p.spans0 + full * p.spans_mid + (last ? p.spans_last : 0);
+    p.groups0 = groups_of(m.tiles0); p.groups_mid = m.rem ? groups_of(m.tiles_per_set) : 1;
+    p.groups = p.groups0 + m.full * p.groups_mid + (m.last ? groups_of(m.tiles_last) : 0);
+    p.spans0 = spans_of(m.tiles0); p.spans_mid = m.rem ? spans_of(m.tiles_per_set) : 1;
+    p.spans_last = !m.rem ? 0 : m.last ? spans_of(m.tiles_last) : p.spans_mid;
+    p.n_touched = 1 + m.full + (m.last ? 1 : 0);
+    p.spans = p.spans0 + m.full * p.spans_mid + (m.last ? p.spans_last : 0);
     return p;
 }
 
@@ -1035,6 +1024,62 @@ static int64_t rnn_bwd_workspace_floats(const ftl_rnn* net, const RnnBwdPlan& p,
     const int64_t U = (int64_t)net->width[Lt] + rnn_prev_width(A, net->flags) + ((net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0) + C;
     return p.spans * count + B * n * 2 * C + p.groups * FTL_MLP_ENV_TILE * U;
 }
+
+// What ftl_rnn_forward and ftl_rnn_backward check of their net and of an ftl_rnn_sequence alike, in their common order, between the
+// checks of their own: `name` heads the messages, `limit` is the entry's text for more than 65,535 blocks
+struct RnnSeq {
+    const char *name, *limit;
+    const ftl_handle* h; const ftl_rnn* net; int32_t n_blocks, n; const ftl_rnn_sequence* seq;
+    int32_t A, C, P, R; bool more; int64_t arow, ael;           // (set by open())
+    int no(int code, const std::string& what) const { return fail(code, std::string(name) + ": " + what); }
+    // h, net, seq and `g_missing` (the entry's further struct, if it has one); n_blocks, n, the net and its state; seq->obs
+    int open(bool g_missing) {
+        if (!h) return no(FTL_E_INVALID, "null argument: h");
+        if (!net) return no(FTL_E_INVALID, "null argument: net");
+        if (!net->params) return no(FTL_E_INVALID, "null argument: net->params");
+        if (!seq) return no(FTL_E_INVALID, "null argument: seq");
+        if (g_missing) return no(FTL_E_INVALID, "null argument: g");
+        if (n_blocks < 1 || n < 1) return no(FTL_E_INVALID, "n_blocks and n must be at least 1");
+        if (n_blocks > 65535) return no(FTL_E_UNSUPPORTED, limit);
+        if (int rc = rnn_net_check(net, n, "the last row")) return rc;
+        if (int rc = rnn_state_check(net)) return rc;
+        A = net->width[net->n_layers + 1]; C = net->cell;
+        P = rnn_prev_width(A, net->flags); R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0;
+        more = n_blocks > 1; arow = A == 2 ? 16 : A == 1 ? 8 : 4; ael = A == 5 ? 4 : 8;
+        if (!seq->obs) return no(FTL_E_INVALID, "null argument: seq->obs");
+        return FTL_OK;
+    }
+    // the records between the blocks are there where the net reads them; the bytes between two blocks of obs and of the records
+    int blocks() const {
+        if (more && !seq->kind) return no(FTL_E_INVALID, "null argument: seq->kind (read for every block but the last)");
+        if (more && P && !seq->action) return no(FTL_E_INVALID, "null argument: seq->action (the net has FTL_RNN_PREV_ACTION)");
+        if (more && R && !seq->reward) return no(FTL_E_INVALID, "null argument: seq->reward (the net has FTL_RNN_PREV_REWARD)");
+        if (seq->obs_block_bytes < (int64_t)n * net->width[0] * 4 || (seq->obs_block_bytes & 3))
+            return no(FTL_E_INVALID, "obs_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
+        if (more && P && (seq->action_block_bytes < (int64_t)n * arow || (seq->action_block_bytes & (ael - 1))))
+            return no(FTL_E_INVALID, "action_block_bytes must be a multiple of the action element of at least one block of encoded actions");
+        if (more && R && (seq->reward_block_bytes < (int64_t)n * 8 || (seq->reward_block_bytes & 7)))
+            return no(FTL_E_INVALID, "reward_block_bytes must be a multiple of 8 of at least one block, n * 8");
+        if (more && seq->kind_block_bytes < (int64_t)n) return no(FTL_E_INVALID, "kind_block_bytes below one block, n");
+        return FTL_OK;
+    }
+    int aligned() const {
+        if (((uintptr_t)seq->obs) & 3) return no(FTL_E_INVALID, "obs must be 4-byte aligned");
+        if (more && P && (((uintptr_t)seq->action) & (uintptr_t)(ael - 1))) return no(FTL_E_INVALID, "action not aligned to its element");
+        if (more && R && (((uintptr_t)seq->reward) & 7)) return no(FTL_E_INVALID, "reward must be 8-byte aligned");
+        if (((uintptr_t)seq->reward0) & 7) return no(FTL_E_INVALID, "reward0 must be 8-byte aligned");
+        return FTL_OK;
+    }
+    // the fields that ftlrnn::Seq and ftlrnn::Bwd have in common, but for those rnn_fill has set
+    template <typename Args> void fill(Args& a) const {
+        a.m.obs = seq->obs; a.m.lo0 = a.m.hi0 = a.m.lo1 = a.m.hi1 = 0.0;
+        a.cell = C; a.P = P; a.R = R; a.A = A; a.n_blocks = n_blocks;
+        a.state = net->state; a.state_stride = net->state_stride;
+        a.obs_bb = seq->obs_block_bytes; a.action_bb = seq->action_block_bytes; a.reward_bb = seq->reward_block_bytes;
+        a.kind_bb = seq->kind_block_bytes;
+        a.action = P ? seq->action : nullptr; a.reward = R ? seq->reward : nullptr; a.kind = seq->kind; a.reward0 = R ? seq->reward0 : nullptr;
+    }
+};
 
 extern "C" {
 
@@ -1064,128 +1109,44 @@ int ftl_rnn_act(ftl_handle* h, const ftl_outputs* out, const ftl_rnn* net, const
 
 int ftl_rollout_rnn(ftl_handle* h, int32_t T, double gamma, const ftl_outputs* out, const ftl_rollout_outputs* ro, const ftl_rnn* net,
                     void* actions, int64_t step_bytes, uint32_t flags, void* stream) {
-    if (!h || !out || !net) return fail(FTL_E_INVALID, "null argument");
-    if (flags & FTL_STEP_NO_SENSORS)
-        return fail(FTL_E_INVALID, "ftl_rollout_rnn refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
-    if (int rc = rollout_check("ftl_rollout_rnn", ro, T, 0, flags)) return rc;
+    if (int rc = policy_rollout_check("ftl_rollout_rnn", h, out, net, ro, T, flags)) return rc;
     ftlrnn::Args a; unsigned grid; size_t lds;
     if (int rc = rnn_args(h, out, net, a, grid, lds)) return rc;
-    const int64_t block = (int64_t)h->P.n_envs * (int64_t)mlp_action_bytes(a.m.head);
-    if (actions && step_bytes < block) return fail(FTL_E_INVALID, "ftl_rollout_rnn: step_bytes below one block of encoded actions");
-    if (actions && ((((uintptr_t)actions) | (uintptr_t)step_bytes) & (a.m.head == FTL_ACTION_DISCRETE ? 3 : 7)))
-        return fail(FTL_E_INVALID, "ftl_rollout_rnn: actions and step_bytes not aligned to the action element");
-    if (int rc = check_ready(h, out)) return rc;
-    if (int rc = set_device(h)) return rc;
-    if (int rc = rnn_kernel_ready(lds)) return rc;
-    if (!actions && !h->bl_action) {                            // (16 bytes per env: any encoding fits the baseline's scratch)
-        hipError_t e = hipMalloc((void**)&h->bl_action, align_up((size_t)h->P.n_envs * 16, 256));
-        if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMalloc(policy actions): ") + hipGetErrorString(e));
-    }
-    if (int rc = rollout_scratch(h)) return rc;
-    a.alive = h->ro_alive;                                      // (the fold's first pass sets it from the state before decision 0 reads it)
     const ftlmlp::Sample sm{nullptr, nullptr, nullptr, nullptr};
-    return rollout_loop(h, a.m.head, T, gamma, out, ro, 0, true, stream, [&](int32_t t) {
-        a.m.action = actions ? (void*)((char*)actions + (int64_t)t * step_bytes) : (void*)h->bl_action;
+    return policy_rollout("ftl_rollout_rnn", h, a.m.head, T, gamma, out, ro, actions, step_bytes, stream, [&] { return rnn_kernel_ready(lds); },
+                          [&](void* action) {
+        a.m.action = action; a.alive = h->ro_alive;             // (the fold's first pass sets it from the state before decision 0 reads it)
         hipLaunchKernelGGL(ftlrnn::ftl_rnn_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
-        return a.m.action;
     });
 }
 
 int ftl_collect_rnn(ftl_handle* h, int32_t T, const ftl_outputs* out, const ftl_rnn* net, const ftl_rnn_collect_buffers* rb, uint32_t flags, void* stream) {
-    if (!h || !out || !net || !rb) return fail(FTL_E_INVALID, "null argument");
-    const ftl_collect_buffers* b = &rb->b;
-    if (flags & FTL_STEP_NO_SENSORS)
-        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_NO_SENSORS: every step scans, because the next decision reads policy_obs");
-    if (flags & FTL_STEP_AUTO_RESET)
-        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_AUTO_RESET: a same-step reset puts the next episode's first observation where "
-                                   "the terminal one belongs, so obs[t+1] would not be the successor of transition t (FTL_STEP_NEXT_RESET keeps it)");
-    if (flags & FTL_STEP_QUEUE_RESET)
-        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_QUEUE_RESET: the queue restarts a finished env inside the step that ended its "
-                                   "episode, so obs[t+1] would not be the successor of transition t (FTL_STEP_NEXT_RESET keeps it)");
-    if (flags & FTL_STEP_SAMPLE_RESET)
-        return fail(FTL_E_INVALID, "ftl_collect_rnn refuses FTL_STEP_SAMPLE_RESET: the sampler restarts a finished env inside the step that ended its "
-                                   "episode, so obs[t+1] would not be the successor of transition t (FTL_STEP_NEXT_RESET keeps it)");
-    if (flags & ~(uint32_t)FTL_STEP_NEXT_RESET) return fail(FTL_E_INVALID, "ftl_collect_rnn takes no flag but FTL_STEP_NEXT_RESET");
-    if (T <= 0) return fail(FTL_E_INVALID, "ftl_collect_rnn: T must be positive");
+    if (int rc = collect_check("ftl_collect_rnn", h, out, net, rb, flags, T)) return rc;
     ftlrnn::Args a; unsigned grid; size_t lds;
     if (int rc = rnn_args(h, out, net, a, grid, lds)) return rc;
-    if (!b->obs || !b->head || !b->action || !b->reward || !b->kind)
-        return fail(FTL_E_INVALID, "ftl_collect_buffers: obs / head / action / reward / kind missing");
-    if (!rb->state) return fail(FTL_E_INVALID, "ftl_rnn_collect_buffers: state missing (at least block 0: the rows decision 0 read)");
-    if (rb->state_steps != 1 && rb->state_steps != T) return fail(FTL_E_INVALID, "ftl_rnn_collect_buffers: state_steps must be 1 or T");
-    const int64_t n = h->P.n_envs, wl = a.A, arow = (int64_t)mlp_action_bytes(a.m.head), S = 2 * (int64_t)a.cell + a.P + 1;
-    if (b->obs_step_bytes < n * net->width[0] * 4 || b->head_step_bytes < n * wl * 4 || b->action_step_bytes < n * arow ||
-        b->reward_step_bytes < n * 8 || b->kind_step_bytes < n || (b->noise && b->noise_step_bytes < n * wl * 4) ||
-        (rb->state_steps > 1 && rb->state_step_bytes < n * S * 4))
-        return fail(FTL_E_INVALID, "ftl_collect_buffers: a *_step_bytes below one block of its array");
-    if (((((uintptr_t)b->obs) | (uintptr_t)b->obs_step_bytes | ((uintptr_t)b->head) | (uintptr_t)b->head_step_bytes) & 3) ||
-        ((((uintptr_t)b->action) | (uintptr_t)b->action_step_bytes) & (uintptr_t)(arow == 4 ? 3 : 7)) ||
-        ((((uintptr_t)b->reward) | (uintptr_t)b->reward_step_bytes) & 7) || (b->noise && (b->noise_step_bytes & 3)) ||
-        ((((uintptr_t)rb->state) | (uintptr_t)(rb->state_steps > 1 ? rb->state_step_bytes : 0)) & 3))
-        return fail(FTL_E_INVALID, "ftl_collect_buffers: a base pointer or a *_step_bytes not aligned to the element of its array");
-    if (int rc = mlp_sample_check("ftl_collect_rnn", a.m.head, b->noise, b->sigma, b->head, b->obs)) return rc;
-    if (int rc = check_ready(h, out)) return rc;
-    if (int rc = set_device(h)) return rc;
-    if (int rc = rnn_kernel_ready(lds)) return rc;
-    if (int rc = rollout_scratch(h)) return rc;
-    ftlcol::Args r;
-    r.env_int = h->P.env_int; r.rec_stride = h->P.rec_stride; r.n_envs = h->P.n_envs;
-    r.reward = out->reward; r.done = out->done; r.status = out->status;
-    r.alive = h->ro_alive; r.rec_reward = nullptr; r.rec_kind = nullptr; r.first = 1;
-    const dim3 rgrid((unsigned)((h->P.n_envs + 255) / 256));
-    hipLaunchKernelGGL(ftlcol::ftl_collect_record_kernel, rgrid, dim3(256), 0, (hipStream_t)stream, r);
-    r.first = 0;
-    a.alive = h->ro_alive;
-    ftlmlp::Sample sm{nullptr, b->sigma, nullptr, nullptr};
-    const int rc = rollout_loop(h, a.m.head, T, 1.0, out, nullptr, flags, true, stream,
-        [&](int32_t t) {
-            sm.noise = b->noise ? (const float*)((const char*)b->noise + (int64_t)t * b->noise_step_bytes) : nullptr;
-            sm.head_rec = (float*)((char*)b->head + (int64_t)t * b->head_step_bytes);
-            sm.obs_rec = (float*)((char*)b->obs + (int64_t)t * b->obs_step_bytes);
-            a.m.action = (char*)b->action + (int64_t)t * b->action_step_bytes;
+    return collect_loop("ftl_collect_rnn", h, T, out, a.m, a.A, &rb->b, flags, stream,
+        [&](bool& is_short, bool& misaligned) {                 // the state blocks beside the feed-forward record
+            if (!rb->state) return fail(FTL_E_INVALID, "ftl_rnn_collect_buffers: state missing (at least block 0: the rows decision 0 read)");
+            if (rb->state_steps != 1 && rb->state_steps != T) return fail(FTL_E_INVALID, "ftl_rnn_collect_buffers: state_steps must be 1 or T");
+            const int64_t S = 2 * (int64_t)a.cell + a.P + 1;
+            is_short = rb->state_steps > 1 && rb->state_step_bytes < h->P.n_envs * S * 4;
+            misaligned = (((uintptr_t)rb->state) | (uintptr_t)(rb->state_steps > 1 ? rb->state_step_bytes : 0)) & 3;
+            return (int)FTL_OK;
+        },
+        [&] { return rnn_kernel_ready(lds); },
+        [&](int32_t t, const ftlmlp::Sample& sm, void* action) {
+            a.m.action = action; a.alive = h->ro_alive;
             a.state_rec = t < rb->state_steps ? (float*)((char*)rb->state + (int64_t)t * rb->state_step_bytes) : nullptr;
             hipLaunchKernelGGL(ftlrnn::ftl_rnn_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a, sm);
-            return a.m.action;
-        },
-        [&](int32_t t) {
-            r.rec_reward = (double*)((char*)b->reward + (int64_t)t * b->reward_step_bytes);
-            r.rec_kind = b->kind + (int64_t)t * b->kind_step_bytes;
-            hipLaunchKernelGGL(ftlcol::ftl_collect_record_kernel, rgrid, dim3(256), 0, (hipStream_t)stream, r);
-            return (int)FTL_OK;
         });
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync((char*)b->obs + (int64_t)T * b->obs_step_bytes, out->policy_obs, (size_t)n * net->width[0] * 4,
-                                  hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipMemcpyAsync(obs[T]): ") + hipGetErrorString(e));
-    return FTL_OK;
 }
 
 int ftl_rnn_forward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, int32_t n, const ftl_rnn_sequence* seq, void* stream) {
-    if (!h) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: h");
-    if (!net) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: net");
-    if (!net->params) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: net->params");
-    if (!seq) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq");
-    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_rnn_forward: n_blocks and n must be at least 1");
-    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_rnn_forward: n_blocks beyond 65,535");
-    if (int rc = rnn_net_check(net, n, "the last row")) return rc;
-    if (int rc = rnn_state_check(net)) return rc;
-    const int32_t Lt = net->n_layers, A = net->width[Lt + 1], C = net->cell;
-    const int32_t P = rnn_prev_width(A, net->flags), R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0;
-    const bool more = n_blocks > 1;
-    if (!seq->obs) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->obs");
+    RnnSeq r{"ftl_rnn_forward", "n_blocks beyond 65,535", h, net, n_blocks, n, seq};
+    if (int rc = r.open(false)) return rc;
+    const int32_t A = r.A, C = r.C;
     if (!seq->head) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->head");
-    if (more && !seq->kind) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->kind (read for every block but the last)");
-    if (more && P && !seq->action) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->action (the net has FTL_RNN_PREV_ACTION)");
-    if (more && R && !seq->reward) return fail(FTL_E_INVALID, "ftl_rnn_forward: null argument: seq->reward (the net has FTL_RNN_PREV_REWARD)");
-    const int64_t arow = A == 2 ? 16 : A == 1 ? 8 : 4, ael = A == 5 ? 4 : 8;
-    if (seq->obs_block_bytes < (int64_t)n * net->width[0] * 4 || (seq->obs_block_bytes & 3))
-        return fail(FTL_E_INVALID, "ftl_rnn_forward: obs_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
-    if (more && P && seq->action && (seq->action_block_bytes < (int64_t)n * arow || (seq->action_block_bytes & (ael - 1))))
-        return fail(FTL_E_INVALID, "ftl_rnn_forward: action_block_bytes must be a multiple of the action element of at least one block of encoded actions");
-    if (more && R && (seq->reward_block_bytes < (int64_t)n * 8 || (seq->reward_block_bytes & 7)))
-        return fail(FTL_E_INVALID, "ftl_rnn_forward: reward_block_bytes must be a multiple of 8 of at least one block, n * 8");
-    if (more && seq->kind_block_bytes < (int64_t)n)
-        return fail(FTL_E_INVALID, "ftl_rnn_forward: kind_block_bytes below one block, n");
+    if (int rc = r.blocks()) return rc;
     if (seq->head_block_bytes < (int64_t)n * A * 4 || (seq->head_block_bytes & 3))
         return fail(FTL_E_INVALID, "ftl_rnn_forward: head_block_bytes must be a multiple of 4 of at least one block, n * A * 4");
     if (seq->h && (seq->h_block_bytes < (int64_t)n * C * 4 || (seq->h_block_bytes & 3)))
@@ -1196,23 +1157,15 @@ int ftl_rnn_forward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, i
     rnn_fill(net, n, a.m, a.u_stride, a.h_stride, grid);
     if ((uint64_t)grid * FTL_MLP_THREADS > 0xFFFFFFFFull)       // (a grid dimension counts threads in 32 bits: 2^24 tiles, over 5e8 rows a block)
         return fail(FTL_E_UNSUPPORTED, "ftl_rnn_forward: n beyond the 2^24 - 1 tiles of one launch; split the rows");
-    if (((uintptr_t)seq->obs) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: obs must be 4-byte aligned");
-    if (more && P && (((uintptr_t)seq->action) & (uintptr_t)(ael - 1))) return fail(FTL_E_INVALID, "ftl_rnn_forward: action not aligned to its element");
-    if (more && R && (((uintptr_t)seq->reward) & 7)) return fail(FTL_E_INVALID, "ftl_rnn_forward: reward must be 8-byte aligned");
-    if (((uintptr_t)seq->reward0) & 7) return fail(FTL_E_INVALID, "ftl_rnn_forward: reward0 must be 8-byte aligned");
+    if (int rc = r.aligned()) return rc;
     if (((uintptr_t)seq->h) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: h must be 4-byte aligned");
     if (((uintptr_t)seq->state_out) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: state_out must be 4-byte aligned");
     if (((uintptr_t)seq->head) & 3) return fail(FTL_E_INVALID, "ftl_rnn_forward: head must be 4-byte aligned");
     const size_t lds = rnn_lds_bytes(a.m.act_stride, a.u_stride, a.h_stride);
     if (int rc = set_device(h)) return rc;
     if (int rc = rnn_kernel_ready(lds, (const void*)ftlrnn::ftl_rnn_forward_kernel)) return rc;
-    a.m.obs = seq->obs; a.m.lo0 = a.m.hi0 = a.m.lo1 = a.m.hi1 = 0.0;
-    a.cell = C; a.P = P; a.R = R; a.A = A;
-    a.n_blocks = n_blocks; a.state_at = seq->state_out ? seq->state_at : -1;
-    a.state = net->state; a.state_stride = net->state_stride;
-    a.obs_bb = seq->obs_block_bytes; a.action_bb = seq->action_block_bytes; a.reward_bb = seq->reward_block_bytes;
-    a.kind_bb = seq->kind_block_bytes; a.head_bb = seq->head_block_bytes; a.h_bb = seq->h_block_bytes;
-    a.action = P ? seq->action : nullptr; a.reward = R ? seq->reward : nullptr; a.kind = seq->kind; a.reward0 = R ? seq->reward0 : nullptr;
+    r.fill(a);
+    a.state_at = seq->state_out ? seq->state_at : -1; a.head_bb = seq->head_block_bytes; a.h_bb = seq->h_block_bytes;
     a.head = seq->head; a.h = seq->h; a.state_out = seq->state_out;
     hipLaunchKernelGGL(ftlrnn::ftl_rnn_forward_kernel, dim3(grid), dim3(FTL_MLP_THREADS), lds, (hipStream_t)stream, a);
     return launched();
@@ -1229,34 +1182,13 @@ int64_t ftl_sizeof_rnn_backward_workspace(const ftl_rnn* net, int32_t n_blocks, 
 
 int ftl_rnn_backward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, int32_t n, const ftl_rnn_sequence* seq, const ftl_rnn_gradient* g,
                      void* stream) {
-    if (!h) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: h");
-    if (!net) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: net");
-    if (!net->params) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: net->params");
-    if (!seq) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq");
-    if (!g) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g");
-    if (n_blocks < 1 || n < 1) return fail(FTL_E_INVALID, "ftl_rnn_backward: n_blocks and n must be at least 1");
-    if (n_blocks > 65535) return fail(FTL_E_UNSUPPORTED, "ftl_rnn_backward: n_blocks beyond 65,535 (the limit of ftl_rnn_forward)");
-    if (int rc = rnn_net_check(net, n, "the last row")) return rc;
-    if (int rc = rnn_state_check(net)) return rc;
-    const int32_t Lt = net->n_layers, A = net->width[Lt + 1], C = net->cell;
-    const int32_t P = rnn_prev_width(A, net->flags), R = (net->flags & FTL_RNN_PREV_REWARD) ? 1 : 0;
-    const bool more = n_blocks > 1;
-    if (!seq->obs) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->obs");
+    RnnSeq r{"ftl_rnn_backward", "n_blocks beyond 65,535 (the limit of ftl_rnn_forward)", h, net, n_blocks, n, seq};
+    if (int rc = r.open(!g)) return rc;
+    const int32_t Lt = net->n_layers, A = r.A, C = r.C;
     if (!g->dhead) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g->dhead");
     if (!g->grad) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g->grad");
     if (!g->workspace) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: g->workspace");
-    if (more && !seq->kind) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->kind (read for every block but the last)");
-    if (more && P && !seq->action) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->action (the net has FTL_RNN_PREV_ACTION)");
-    if (more && R && !seq->reward) return fail(FTL_E_INVALID, "ftl_rnn_backward: null argument: seq->reward (the net has FTL_RNN_PREV_REWARD)");
-    const int64_t arow = A == 2 ? 16 : A == 1 ? 8 : 4, ael = A == 5 ? 4 : 8;
-    if (seq->obs_block_bytes < (int64_t)n * net->width[0] * 4 || (seq->obs_block_bytes & 3))
-        return fail(FTL_E_INVALID, "ftl_rnn_backward: obs_block_bytes must be a multiple of 4 of at least one block, n * width[0] * 4");
-    if (more && P && (seq->action_block_bytes < (int64_t)n * arow || (seq->action_block_bytes & (ael - 1))))
-        return fail(FTL_E_INVALID, "ftl_rnn_backward: action_block_bytes must be a multiple of the action element of at least one block of encoded actions");
-    if (more && R && (seq->reward_block_bytes < (int64_t)n * 8 || (seq->reward_block_bytes & 7)))
-        return fail(FTL_E_INVALID, "ftl_rnn_backward: reward_block_bytes must be a multiple of 8 of at least one block, n * 8");
-    if (more && seq->kind_block_bytes < (int64_t)n)
-        return fail(FTL_E_INVALID, "ftl_rnn_backward: kind_block_bytes below one block, n");
+    if (int rc = r.blocks()) return rc;
     if (g->dhead_block_bytes < (int64_t)n * A * 4 || (g->dhead_block_bytes & 3))
         return fail(FTL_E_INVALID, "ftl_rnn_backward: dhead_block_bytes must be a multiple of 4 of at least one block, n * A * 4");
     ftlrnn::Bwd a; unsigned grid;
@@ -1283,10 +1215,7 @@ int ftl_rnn_backward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, 
     const int64_t count = rnn_param_count(net->width, Lt, C, net->flags);
     if (g->workspace_bytes < rnn_bwd_workspace_floats(net, p, n_blocks, n, count) * 4)
         return fail(FTL_E_INVALID, "ftl_rnn_backward: workspace_bytes below ftl_sizeof_rnn_backward_workspace");
-    if (((uintptr_t)seq->obs) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: obs must be 4-byte aligned");
-    if (more && P && (((uintptr_t)seq->action) & (uintptr_t)(ael - 1))) return fail(FTL_E_INVALID, "ftl_rnn_backward: action not aligned to its element");
-    if (more && R && (((uintptr_t)seq->reward) & 7)) return fail(FTL_E_INVALID, "ftl_rnn_backward: reward must be 8-byte aligned");
-    if (((uintptr_t)seq->reward0) & 7) return fail(FTL_E_INVALID, "ftl_rnn_backward: reward0 must be 8-byte aligned");
+    if (int rc = r.aligned()) return rc;
     if (((uintptr_t)g->dhead) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: dhead must be 4-byte aligned");
     if (((uintptr_t)g->dstate_in) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: dstate_in must be 4-byte aligned");
     if (((uintptr_t)g->dstate_out) & 3) return fail(FTL_E_INVALID, "ftl_rnn_backward: dstate_out must be 4-byte aligned");
@@ -1297,14 +1226,10 @@ int ftl_rnn_backward(const ftl_handle* h, const ftl_rnn* net, int32_t n_blocks, 
         hipError_t e = hipFuncSetAttribute((const void*)ftlrnn::ftl_rnn_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(FTL_E_DEVICE, std::string("hipFuncSetAttribute(ftl_rnn_backward_kernel): ") + hipGetErrorString(e));
     }
-    a.m.obs = seq->obs; a.m.lo0 = a.m.hi0 = a.m.lo1 = a.m.hi1 = 0.0;
-    a.cell = C; a.P = P; a.R = R; a.A = A;
-    a.n_blocks = n_blocks; a.G = (int32_t)p.G; a.spg = (int32_t)p.spg;
+    r.fill(a);
+    a.G = (int32_t)p.G; a.spg = (int32_t)p.spg;
     a.groups0 = (int32_t)p.groups0; a.groups_mid = (int32_t)p.groups_mid; a.spans0 = (int32_t)p.spans0; a.spans_mid = (int32_t)p.spans_mid;
-    a.state = net->state; a.state_stride = net->state_stride;
-    a.obs_bb = seq->obs_block_bytes; a.action_bb = seq->action_block_bytes; a.reward_bb = seq->reward_block_bytes;
-    a.kind_bb = seq->kind_block_bytes; a.dy_bb = g->dhead_block_bytes;
-    a.action = P ? seq->action : nullptr; a.reward = R ? seq->reward : nullptr; a.kind = seq->kind; a.reward0 = R ? seq->reward0 : nullptr;
+    a.dy_bb = g->dhead_block_bytes;
     a.dy = g->dhead; a.dstate_in = g->dstate_in; a.dstate_out = g->dstate_out;
     a.part = static_cast<float*>(g->workspace); a.count = count;
     a.rec = a.part + p.spans * count;

@@ -17,7 +17,6 @@ recurrent net has the same pair in ``rnn.py`` (``rnn.backward``, ``rnn.Net``).  
 the Box policies on the device (``ftl_ppo_head``; ``ppo_head()`` is its raw form): from the new heads, the trajectory, the advantages
 and the critic's values to the head, value and ``log_std`` gradients, per weight set, for either net family."""
 import ctypes as C
-import functools
 
 import torch
 
@@ -116,21 +115,6 @@ def torch_module(widths, activation, params_row=None):
     return module
 
 
-def _takes_activation(init):
-    """``MlpPolicy.__init__`` with the option ``activation`` in front of it: the fifth argument, or a keyword.  The wrapped function keeps the
-    parameter list ``(batch, widths, params, n_sets)`` that the package has had since the policy arrived, which tests/test_mlp_abi.py pins
-    by introspection; the option is checked and stored here, before the body builds the parts' ``ftl_mlp`` structs from it."""
-    @functools.wraps(init)
-    def __init__(self, *args, **kw):
-        if len(args) > 4:
-            if len(args) > 5 or "activation" in kw:
-                raise TypeError("MlpPolicy(batch, widths, params=None, n_sets=1, activation=\"relu\"): too many arguments")
-            args, kw = args[:4], dict(kw, activation=args[4])
-        self.activation = check_activation(kw.pop("activation", "relu"))
-        init(self, *args, **kw)
-    return __init__
-
-
 class Trajectory:
     """What ``MlpPolicy.collect`` leaves on the device for T steps of N envs (the blocks of ``ftl_collect_buffers``):
     ``obs`` float32 ``[T+1, N, H*W]`` -- ``obs[t]`` decided step t, ``obs[t+1]`` is its true successor (the terminal observation where the
@@ -224,6 +208,84 @@ def check_net_widths(widths):
 FORWARD_MAX_BLOCKS = 65535                 # include/ftl.h, ftl_mlp_forward: n_blocks
 
 
+def _check_params(params, count, n_sets=None, on=None, where=""):
+    """The one rule for every ``params`` of the package: a contiguous float32 ``[n_sets, count]`` tensor -- of ``n_sets`` rows when given, of
+    at least one otherwise, whose device satisfies the predicate ``on`` (asked last) when given; ``where`` ends the message.  Returns
+    ``params``."""
+    ok = torch.is_tensor(params) and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == count and params.is_contiguous()
+    ok = ok and (params.shape[0] >= 1 if n_sets is None else params.shape[0] == n_sets)
+    if not (ok and (on is None or on(params.device))):
+        raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor%s" % (count, where))
+    return params
+
+
+def _held_params(params, n_sets, count, device, who):
+    """The ``params`` of a holder (``Critic``, ``Net`` and the recurrent pair; ``who`` names it in the message): checked, or zeros on
+    ``device`` -- the current GPU by default -- when None."""
+    if n_sets < 1:
+        raise ValueError("n_sets must be at least 1")
+    if params is None:
+        params = torch.zeros(n_sets, count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
+    return _check_params(params, count, n_sets, None if device is None else lambda d: d == torch.device(device), " on the %s's device" % who)
+
+
+def _lead_blocks(t, name, n_sets=None):
+    """``(lead, N, blocks)`` of a tensor ``[..., N, W]`` whose leading axes are flattened to blocks.  With ``n_sets``, the limits of a net's
+    launch as well: ``n_sets`` divides N, at most ``FORWARD_MAX_BLOCKS`` blocks."""
+    lead, N = tuple(t.shape[:-2]), int(t.shape[-2])
+    blocks = 1
+    for d in lead:
+        blocks *= int(d)
+    if N < 1 or blocks < 1:
+        raise ValueError("%s must hold at least one block of at least one row, not %s" % (name, list(t.shape)))
+    if n_sets is not None and N % n_sets:
+        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
+    if n_sets is not None and blocks > FORWARD_MAX_BLOCKS:
+        raise NotImplementedError("at most %d blocks in one call, not %d" % (FORWARD_MAX_BLOCKS, blocks))
+    return lead, N, blocks
+
+
+_WORKSPACE = {}                            # (purpose, device index, raw stream) -> the tensor
+
+
+def _workspace(purpose, device, need, dtype=torch.float32):
+    """``(tensor, raw stream)``: a ``dtype`` tensor of at least ``need`` bytes for the current stream of ``device``, kept per purpose
+    (``"mlp_backward"``, ``"rnn_backward"``, ``"ppo_head"``), device and stream, and grown when a call needs more."""
+    raw = torch.cuda.current_stream(device).cuda_stream
+    key = (purpose, device.index if device.index is not None else torch.cuda.current_device(), raw)
+    size = torch.finfo(dtype).bits // 8
+    ws = _WORKSPACE.get(key)
+    if ws is None or ws.numel() * size < need:
+        ws = _WORKSPACE[key] = torch.empty((need + size - 1) // size, dtype=dtype, device=device)
+    return ws, raw
+
+
+def _mlp_struct(widths, params, n_sets, envs_per_set, activation, env_first=0):
+    """The ``abi.Mlp`` of checked arguments: rows from ``env_first`` on, ``envs_per_set`` of them to a weight set."""
+    net = abi.Mlp()
+    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), abi.mlp_param_count(widths), n_sets, len(widths) - 1
+    for l, w in enumerate(widths):
+        net.width[l] = w
+    net.env_first, net.envs_per_set, net.activation = env_first, envs_per_set, ACTIVATIONS[activation]
+    return net
+
+
+def _check_rows(widths, params, x, activation, grad_msg, params_too, max_in=None):
+    """The checks ``forward`` and ``backward`` share, in ``forward``'s order; returns ``(widths, count, n_sets, lead, N, blocks)``.
+    ``max_in`` is ``backward``'s limit on the input width; ``grad_msg`` refuses an ``x`` (``params_too``: or ``params``) that requires grad."""
+    widths = check_net_widths(widths)
+    check_activation(activation)
+    count = abi.mlp_param_count(widths)
+    if max_in is not None and widths[0] > max_in:
+        raise NotImplementedError("at most %d inputs in backward()" % max_in)
+    n_sets = int(_check_params(params, count).shape[0])
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-1] == widths[0] and x.is_contiguous()):
+        raise ValueError("x must be a contiguous float32 [..., N, %d] tensor" % widths[0])
+    if x.requires_grad or (params_too and params.requires_grad):
+        raise ValueError(grad_msg)
+    return (widths, count, n_sets) + _lead_blocks(x, "x", n_sets)
+
+
 def forward(widths, params, x, activation="relu", out=None):
     """The raw heads of ``n_sets`` nets of shape ``widths`` on caller-supplied rows, in one launch (``ftl_mlp_forward``): the forward pass
     of ``ftl_mlp_act`` operation for operation -- the k-ordered ``fmaf`` chains, ReLU or ``tanh32`` hidden layers, a linear head -- without
@@ -241,27 +303,8 @@ def forward(widths, params, x, activation="relu", out=None):
     2.42 ms (ReLU) / 2.00 ms (tanh) against 3.84 / 3.88 ms for per-block ``baddbmm`` -- the project's timing bar holds --; with ONE set
     2.23 / 1.80 ms against 1.47 / 1.48 ms for torch's single large ``addmm`` chain -- the bar does NOT hold: there torch is faster and
     this call buys the pinned arithmetic and 1.66 GB less peak memory, not time."""
-    widths = check_net_widths(widths)
-    check_activation(activation)
-    count = abi.mlp_param_count(widths)
-    if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == count
-            and params.shape[0] >= 1 and params.is_contiguous()):
-        raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor" % count)
-    n_sets = int(params.shape[0])
-    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-1] == widths[0] and x.is_contiguous()):
-        raise ValueError("x must be a contiguous float32 [..., N, %d] tensor" % widths[0])
-    if x.requires_grad or params.requires_grad:
-        raise ValueError("forward() has no backward pass: pass detached tensors")
-    lead, N = tuple(x.shape[:-2]), int(x.shape[-2])
-    blocks = 1
-    for d in lead:
-        blocks *= int(d)
-    if N < 1 or blocks < 1:
-        raise ValueError("x must hold at least one block of at least one row, not %s" % (list(x.shape),))
-    if N % n_sets:
-        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
-    if blocks > FORWARD_MAX_BLOCKS:
-        raise NotImplementedError("at most %d blocks in one call, not %d" % (FORWARD_MAX_BLOCKS, blocks))
+    widths, count, n_sets, lead, N, blocks = _check_rows(widths, params, x, activation, "forward() has no backward pass: pass detached tensors",
+                                                         True)
     shape = lead + (N, widths[-1])
     if out is not None and not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()
                                 and out.device == x.device):
@@ -270,11 +313,7 @@ def forward(widths, params, x, activation="relu", out=None):
         raise ValueError("x and params must lie on the same GPU device")
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    net = abi.Mlp()
-    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), count, n_sets, len(widths) - 1
-    for l, w in enumerate(widths):
-        net.width[l] = w
-    net.env_first, net.envs_per_set, net.activation = 0, N // n_sets, ACTIVATIONS[activation]
+    net = _mlp_struct(widths, params, n_sets, N // n_sets, activation)
     lib = _lib.load()
     h = _device_handle(x.device)
     stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
@@ -282,43 +321,26 @@ def forward(widths, params, x, activation="relu", out=None):
     return out
 
 
-class Critic:
-    """A value net for ``gae()``, or a population of ``n_sets`` of them: an ``ftl_mlp`` of head width 1 evaluated by ``forward``.
-    ``Critic(widths, n_sets=1, activation="tanh", params=None, device=None)``: ``widths[-1]`` must be 1 (``ValueError``); ``params`` is the
-    float32 ``[n_sets, param_count]`` tensor of all weights (zeros on ``device``, the current GPU by default, unless given).  The critic
-    is trained as a torch module by autograd; ``load(module)`` copies its weights here once per iteration and ``values(traj.obs)`` then
-    gives ``gae()`` its values in one launch, with the device's pinned arithmetic and without materialising a hidden activation."""
+class _Holder:
+    """What ``Critic`` and ``Net`` share: the checked ``widths``, ``activation``, ``n_sets`` and ``param_count``, the checked or new
+    ``params`` tensor (``_hold`` returns it: the critic keeps the tensor, the net wraps it), and ``load`` / ``module``.  ``_WHO`` and
+    ``_THIS`` name the class in the messages."""
+    _WHO, _THIS = "net", "this one"
 
-    def __init__(self, widths, n_sets=1, activation="tanh", params=None, device=None):
+    def _hold(self, widths, n_sets, activation, params, device, head=None):
         self.widths = check_net_widths(widths)
-        if self.widths[-1] != 1:
-            raise ValueError("a critic's head is 1 wide, not %d" % self.widths[-1])
+        if head is not None and self.widths[-1] != head:
+            raise ValueError("a critic's head is %d wide, not %d" % (head, self.widths[-1]))
         self.activation = check_activation(activation)
         self.n_sets, self.param_count = int(n_sets), abi.mlp_param_count(self.widths)
-        if self.n_sets < 1:
-            raise ValueError("n_sets must be at least 1")
-        if params is None:
-            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
-        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
-                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
-            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the critic's device" % self.param_count)
-        self.params, self.device = params, params.device
-
-    def values(self, obs, out=None):
-        """float32 ``[..., N]``: the value of every row of ``obs`` ``[..., N, widths[0]]`` (``forward``; ``n_sets`` must divide N, row r
-        uses set ``r // (N // n_sets)``).  ``out=`` reuses a contiguous float32 ``[..., N]`` buffer."""
-        if out is not None:
-            if not (torch.is_tensor(out) and out.is_contiguous() and torch.is_tensor(obs) and tuple(out.shape) == tuple(obs.shape[:-1])):
-                raise ValueError("out must be a contiguous float32 [..., N] tensor of obs's leading shape")
-            out = out.unsqueeze(-1)
-        return forward(self.widths, self.params, obs, self.activation, out)[..., 0]
+        return _held_params(params, self.n_sets, self.param_count, device, self._WHO)
 
     def load(self, module, s=None):
-        """Copy the weights of a torch module (``params_from_torch``: an ``nn.Sequential`` of this critic's widths and activation) into set
+        """Copy the weights of a torch module (``params_from_torch``: an ``nn.Sequential`` of this net's widths and activation) into set
         ``s``, or into every set (``s=None``).  Returns ``self``."""
         widths, activation, row = params_from_torch(module)
         if widths != self.widths or (len(widths) > 2 and activation != self.activation):
-            raise ValueError("the module is a %s %s net, the critic a %s %s one" % (activation, widths, self.activation, self.widths))
+            raise ValueError("the module is a %s %s net, %s a %s %s one" % (activation, widths, self._THIS, self.activation, self.widths))
         if s is not None and not 0 <= int(s) < self.n_sets:
             raise IndexError("set %d of %d" % (int(s), self.n_sets))
         (self.params if s is None else self.params[int(s)]).copy_(row)
@@ -328,19 +350,30 @@ class Critic:
         """A new ``torch.nn.Sequential`` on the CPU with the weights of set ``s`` (``torch_module``)."""
         if not 0 <= int(s) < self.n_sets:
             raise IndexError("set %d of %d" % (int(s), self.n_sets))
-        return torch_module(self.widths, self.activation, self.params[int(s)])
+        return torch_module(self.widths, self.activation, self.params.detach()[int(s)])
 
 
-_BWD_WORKSPACE = {}
+class Critic(_Holder):
+    """A value net for ``gae()``, or a population of ``n_sets`` of them: an ``ftl_mlp`` of head width 1 evaluated by ``forward``.
+    ``Critic(widths, n_sets=1, activation="tanh", params=None, device=None)``: ``widths[-1]`` must be 1 (``ValueError``); ``params`` is the
+    float32 ``[n_sets, param_count]`` tensor of all weights (zeros on ``device``, the current GPU by default, unless given).  The critic
+    is trained as a torch module by autograd; ``load(module)`` copies its weights here once per iteration and ``values(traj.obs)`` then
+    gives ``gae()`` its values in one launch, with the device's pinned arithmetic and without materialising a hidden activation."""
 
+    _WHO, _THIS = "critic", "the critic"
 
-def _net_struct(widths, params, n_sets, N, activation):
-    net = abi.Mlp()
-    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), abi.mlp_param_count(widths), n_sets, len(widths) - 1
-    for l, w in enumerate(widths):
-        net.width[l] = w
-    net.env_first, net.envs_per_set, net.activation = 0, N // n_sets, ACTIVATIONS[activation]
-    return net
+    def __init__(self, widths, n_sets=1, activation="tanh", params=None, device=None):
+        self.params = self._hold(widths, n_sets, activation, params, device, head=1)
+        self.device = self.params.device
+
+    def values(self, obs, out=None):
+        """float32 ``[..., N]``: the value of every row of ``obs`` ``[..., N, widths[0]]`` (``forward``; ``n_sets`` must divide N, row r
+        uses set ``r // (N // n_sets)``).  ``out=`` reuses a contiguous float32 ``[..., N]`` buffer."""
+        if out is not None:
+            if not (torch.is_tensor(out) and out.is_contiguous() and torch.is_tensor(obs) and tuple(out.shape) == tuple(obs.shape[:-1])):
+                raise ValueError("out must be a contiguous float32 [..., N] tensor of obs's leading shape")
+            out = out.unsqueeze(-1)
+        return forward(self.widths, self.params, obs, self.activation, out)[..., 0]
 
 
 def backward(widths, params, x, dy, activation="relu", out=None):
@@ -355,29 +388,8 @@ def backward(widths, params, x, dy, activation="relu", out=None):
     across -- so the result does not depend on the machine or the launch, and no hidden activation reaches global memory.  The span
     partials go through a workspace tensor cached per device and stream.  There is no gradient with respect to ``x``.
     ``ValueError`` / ``NotImplementedError`` as ``forward``, before any library call."""
-    widths = check_net_widths(widths)
-    check_activation(activation)
-    count = abi.mlp_param_count(widths)
-    if widths[0] > abi.FTL_MLP_BWD_MAX_IN:
-        raise NotImplementedError("at most %d inputs in backward()" % abi.FTL_MLP_BWD_MAX_IN)
-    if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == count
-            and params.shape[0] >= 1 and params.is_contiguous()):
-        raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor" % count)
-    n_sets = int(params.shape[0])
-    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-1] == widths[0] and x.is_contiguous()):
-        raise ValueError("x must be a contiguous float32 [..., N, %d] tensor" % widths[0])
-    if x.requires_grad:
-        raise ValueError("backward() has no gradient with respect to x: pass a detached tensor")
-    lead, N = tuple(x.shape[:-2]), int(x.shape[-2])
-    blocks = 1
-    for d in lead:
-        blocks *= int(d)
-    if N < 1 or blocks < 1:
-        raise ValueError("x must hold at least one block of at least one row, not %s" % (list(x.shape),))
-    if N % n_sets:
-        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
-    if blocks > FORWARD_MAX_BLOCKS:
-        raise NotImplementedError("at most %d blocks in one call, not %d" % (FORWARD_MAX_BLOCKS, blocks))
+    widths, count, n_sets, lead, N, blocks = _check_rows(widths, params, x, activation, "backward() has no gradient with respect to x: pass a "
+                                                         "detached tensor", False, abi.FTL_MLP_BWD_MAX_IN)
     shape = lead + (N, widths[-1])
     if not (torch.is_tensor(dy) and dy.dtype == torch.float32 and tuple(dy.shape) == shape and dy.is_contiguous() and dy.device == x.device
             and not dy.requires_grad):
@@ -389,17 +401,13 @@ def backward(widths, params, x, dy, activation="relu", out=None):
         raise ValueError("x and params must lie on the same GPU device")
     if out is None:
         out = torch.empty(n_sets, count, dtype=torch.float32, device=x.device)
-    net = _net_struct(widths, params.detach(), n_sets, N, activation)
+    net = _mlp_struct(widths, params.detach(), n_sets, N // n_sets, activation)
     lib = _lib.load()
     h = _device_handle(x.device)
     need = lib.ftl_sizeof_mlp_backward_workspace(C.byref(net), blocks, N)
     if need < 0:
         raise _lib.FtlError("ftl_sizeof_mlp_backward_workspace refused a net that the package's checks passed")
-    raw = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), raw)
-    ws = _BWD_WORKSPACE.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = _BWD_WORKSPACE[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+    ws, raw = _workspace("mlp_backward", x.device, need)
     _lib.check(lib.ftl_mlp_backward(h, C.byref(net), blocks, N, x.data_ptr(), N * widths[0] * 4, dy.data_ptr(), N * widths[-1] * 4,
                                     out.data_ptr(), ws.data_ptr(), ws.numel() * 4, C.c_void_p(raw)), lib)
     return out
@@ -420,7 +428,7 @@ class _NetFunction(torch.autograd.Function):
         return backward(ctx.widths, params.detach(), x, dy.detach().contiguous(), ctx.activation), None, None, None
 
 
-class Net(torch.nn.Module):
+class Net(_Holder, torch.nn.Module):
     """A trainable net on the device, or a population of ``n_sets`` of them: ``Net(widths, n_sets=1, activation="relu", params=None,
     device=None)`` is an ``nn.Module`` whose one ``nn.Parameter`` ``params`` is the float32 ``[n_sets, param_count]`` tensor of all weights
     in the layout of ``ftl_mlp`` (zeros on ``device``, the current GPU by default, unless given).  ``params=policy.params`` or
@@ -432,18 +440,8 @@ class Net(torch.nn.Module):
     weights to and from a ``torch.nn.Sequential`` as on ``Critic``."""
 
     def __init__(self, widths, n_sets=1, activation="relu", params=None, device=None):
-        super().__init__()
-        self.widths = check_net_widths(widths)
-        self.activation = check_activation(activation)
-        self.n_sets, self.param_count = int(n_sets), abi.mlp_param_count(self.widths)
-        if self.n_sets < 1:
-            raise ValueError("n_sets must be at least 1")
-        if params is None:
-            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
-        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
-                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
-            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the net's device" % self.param_count)
-        self.params = torch.nn.Parameter(params.detach())       # (the parameter shares the tensor's storage)
+        torch.nn.Module.__init__(self)
+        self.params = torch.nn.Parameter(self._hold(widths, n_sets, activation, params, device).detach())       # (it shares the tensor's storage)
 
     def forward(self, x):
         if torch.is_tensor(x) and x.requires_grad:
@@ -451,21 +449,9 @@ class Net(torch.nn.Module):
         return _NetFunction.apply(self.params, x, self.widths, self.activation)
 
     def load(self, module, s=None):
-        """Copy the weights of a torch module (``params_from_torch``) into set ``s``, or into every set (``s=None``).  Returns ``self``."""
-        widths, activation, row = params_from_torch(module)
-        if widths != self.widths or (len(widths) > 2 and activation != self.activation):
-            raise ValueError("the module is a %s %s net, this one a %s %s one" % (activation, widths, self.activation, self.widths))
-        if s is not None and not 0 <= int(s) < self.n_sets:
-            raise IndexError("set %d of %d" % (int(s), self.n_sets))
+        """``Critic.load`` under ``no_grad``: ``params`` is a parameter here."""
         with torch.no_grad():
-            (self.params if s is None else self.params[int(s)]).copy_(row)
-        return self
-
-    def module(self, s=0):
-        """A new ``torch.nn.Sequential`` on the CPU with the weights of set ``s`` (``torch_module``)."""
-        if not 0 <= int(s) < self.n_sets:
-            raise IndexError("set %d of %d" % (int(s), self.n_sets))
-        return torch_module(self.widths, self.activation, self.params.detach()[int(s)])
+            return _Holder.load(self, module, s)
 
 
 class PpoHead:
@@ -475,9 +461,6 @@ class PpoHead:
 
     def __init__(self, dhead, dvalue, dlog_std, stats):
         self.dhead, self.dvalue, self.dlog_std, self.stats = dhead, dvalue, dlog_std, stats
-
-
-_PPO_WORKSPACE = {}
 
 
 def ppo_head(head, head_old, noise, sigma_old, sigma, adv, ret, kind, value=None, log_sigma_shift=None, clip=0.2, vf_coef=0.5,
@@ -498,14 +481,10 @@ def ppo_head(head, head_old, noise, sigma_old, sigma, adv, ret, kind, value=None
     before any library call, a head width other than 1 or 2 a ``NotImplementedError``."""
     if not (torch.is_tensor(head) and head.dtype == torch.float32 and head.dim() >= 2 and head.is_contiguous()):
         raise ValueError("head must be a contiguous float32 [..., N, A] tensor")
-    lead, N, A = tuple(head.shape[:-2]), int(head.shape[-2]), int(head.shape[-1])
+    A = int(head.shape[-1])
     if A not in (1, 2):
         raise NotImplementedError("ppo_head() takes the Box heads, 2 or 1 wide, not %d (Discrete(5) needs a pinned logarithm)" % A)
-    blocks = 1
-    for d in lead:
-        blocks *= int(d)
-    if N < 1 or blocks < 1:
-        raise ValueError("head must hold at least one block of at least one row, not %s" % (list(head.shape),))
+    lead, N, blocks = _lead_blocks(head, "head")
     dev = head.device
 
     def check(name, t, shape, dtype=torch.float32):
@@ -554,11 +533,7 @@ def ppo_head(head, head_old, noise, sigma_old, sigma, adv, ret, kind, value=None
     need = lib.ftl_sizeof_ppo_head_workspace(blocks, N, n_sets)
     if need < 0:
         raise NotImplementedError("ftl_ppo_head: more than 2^31 - 1 segments in one call; split the blocks")
-    raw = torch.cuda.current_stream(dev).cuda_stream
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), raw)
-    ws = _PPO_WORKSPACE.get(key)
-    if ws is None or ws.numel() * 8 < need:
-        ws = _PPO_WORKSPACE[key] = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+    ws, raw = _workspace("ppo_head", dev, need, torch.float64)
     a = abi.PpoHeadArgs()
     a.n_blocks, a.n, a.n_sets, a.width = blocks, N, n_sets, A
     a.head_new, a.head_old, a.noise = head.data_ptr(), head_old.data_ptr(), noise.data_ptr()
@@ -643,9 +618,19 @@ class MlpPolicy:
 
     On a pipelined batch every part works on its rows on its own stream: like ``step``, ``act()`` does not join."""
 
-    @_takes_activation
-    def __init__(self, batch, widths, params=None, n_sets=1):
-        self.widths = widths = check_widths(batch.cfg, widths)
+    _ROLLOUT, _COLLECT = "ftl_rollout_mlp", "ftl_collect_mlp"                          # the library functions of this net family
+    _COUNT_MISMATCH = "ftl_mlp_param_count disagrees with abi.mlp_param_count: library and package do not match"
+
+    def __init__(self, batch, widths, params=None, n_sets=1, activation="relu"):
+        self.activation = check_activation(activation)
+        self.widths = check_widths(batch.cfg, widths)
+        self.param_count = abi.mlp_param_count(self.widths)
+        self._bind(batch, n_sets, params)
+
+    def _bind(self, batch, n_sets, params):
+        """What a policy of either family does with its batch once ``widths`` and ``param_count`` stand: the checks against the batch, the
+        checked or new ``params``, the library, the persistent action tensor and ``_parts``, the built struct of every part."""
+        widths = self.widths
         self.encoding, _ = head_encoding(batch.cfg)
         pol = getattr(batch, "policy_obs", None)
         if pol is None:
@@ -656,30 +641,28 @@ class MlpPolicy:
         if n_sets < 1 or batch.n % n_sets:
             raise ValueError("n_sets must divide the batch's %d envs" % batch.n)
         self.batch, self.n, self.device, self.n_sets, self.envs_per_set = batch, batch.n, batch.device, n_sets, batch.n // n_sets
-        self.param_count = abi.mlp_param_count(widths)
         if params is None:
             params = torch.zeros(n_sets, self.param_count, dtype=torch.float32, device=self.device)
-        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (n_sets, self.param_count)
-                or params.device != self.device or not params.is_contiguous()):
-            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the batch's device" % self.param_count)
-        self.params = params
+        self.params = _check_params(params, self.param_count, n_sets, lambda d: d == self.device, " on the batch's device")
+        self._buffers()
         self.lib = _lib.load()
-        if self.lib.ftl_mlp_param_count((C.c_int32 * len(widths))(*widths), len(widths) - 1) != self.param_count:
-            raise _lib.FtlError("ftl_mlp_param_count disagrees with abi.mlp_param_count: library and package do not match")
+        if self._lib_param_count() != self.param_count:
+            raise _lib.FtlError(self._COUNT_MISMATCH)
         shape = (self.n, 2) if self.encoding == abi.FTL_ACTION_BOX2 else (self.n,)
         self.action = torch.zeros(*shape, dtype=torch.int32 if self.encoding == abi.FTL_ACTION_DISCRETE else torch.float64, device=self.device)
         self.row = self.action.element_size() * (2 if self.encoding == abi.FTL_ACTION_BOX2 else 1)     # bytes of one env's action
         games = getattr(batch, "games", None)
-        # (game, first env, its ftl_mlp) of every handle under the batch
+        # (game, first env, its net struct) of every handle under the batch
         self._parts = [(g, lo, self._net(lo)) for g, lo in ([(batch, 0)] if games is None else [(g, sh.lo) for g, sh in zip(games, batch.shards)])]
 
+    def _buffers(self):
+        """The persistent tensors a net family keeps beside ``params`` (``head`` and ``obs`` here arrive with the first ``sample()``)."""
+
+    def _lib_param_count(self):
+        return self.lib.ftl_mlp_param_count((C.c_int32 * len(self.widths))(*self.widths), len(self.widths) - 1)
+
     def _net(self, env_first):
-        net = abi.Mlp()
-        net.params, net.set_stride, net.n_sets, net.n_layers = self.params.data_ptr(), self.param_count, self.n_sets, len(self.widths) - 1
-        for l, w in enumerate(self.widths):
-            net.width[l] = w
-        net.env_first, net.envs_per_set, net.activation = env_first, self.envs_per_set, ACTIVATIONS[self.activation]
-        return net
+        return _mlp_struct(self.widths, self.params, self.n_sets, self.envs_per_set, self.activation, env_first)
 
     def layer(self, l):
         """Views ``(W [n_sets, in, out], b [n_sets, out])`` of layer ``l`` (0-based) in ``params``: ``W[s].copy_(linear.weight.T)``
@@ -707,7 +690,7 @@ class MlpPolicy:
         return self.act()
 
     def rollout(self, T, gamma=1.0, record=False):
-        """``batch.rollout_mlp(self, ...)``."""
+        """``batch.rollout_mlp(self, ...)`` (``batch.rollout_rnn`` for a recurrent policy)."""
         b, T = self.batch, int(T)
         b._need_pool()
         if T < 1:
@@ -715,9 +698,10 @@ class MlpPolicy:
         actions = torch.empty(T, *self.action.shape, dtype=self.action.dtype, device=self.device) if record else None
         b._prepare_rollout_outputs()
         ap = actions.data_ptr() if record else 0
+        rollout = getattr(self.lib, self._ROLLOUT)
         for (g, lo, net), s in zip(self._parts, self._streams(actions)):
-            _lib.check(self.lib.ftl_rollout_mlp(g.h, T, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), C.byref(net),
-                                                (ap + lo * self.row) if record else None, self.n * self.row if record else 0, 0, s), self.lib)
+            _lib.check(rollout(g.h, T, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), C.byref(net),
+                               (ap + lo * self.row) if record else None, self.n * self.row if record else 0, 0, s), self.lib)
         out = (b.rollout_ret, b.rollout_steps, b.rollout_status)
         return out + (actions,) if record else out
 
@@ -755,6 +739,19 @@ class MlpPolicy:
 
     def collect(self, T, noise=None, sigma=None, auto_reset="next_step", out=None):
         """``batch.collect_mlp(self, ...)``."""
+        return self._collect(T, noise, sigma, auto_reset, out)
+
+    def _state_blocks(self, T, record_state):
+        """``{name: (shape, dtype)}`` of what a trajectory of this net family holds beside the feed-forward record."""
+        return {}
+
+    def _collect_struct(self, out, lo):
+        """``(the struct the library takes, its ftl_collect_buffers)`` for the part whose first env is ``lo``, with the family's own blocks set."""
+        cb = abi.CollectBuffers()
+        return cb, cb
+
+    def _collect(self, T, noise, sigma, auto_reset, out, record_state=False):
+        """The one ``collect`` of both net families: ``_state_blocks`` and ``_collect_struct`` add a recurrent policy's state blocks."""
         b, T = self.batch, int(T)
         b._need_pool()
         if T < 1:
@@ -764,30 +761,31 @@ class MlpPolicy:
                              'the terminal one belongs (got %r)' % (auto_reset,))
         self._check_noise(noise, sigma, lead=(T,))
         A, W0, N = self.widths[-1], self.widths[0], self.n
+        extra = self._state_blocks(T, record_state)
+        want = dict(obs=((T + 1, N, W0), torch.float32), head=((T, N, A), torch.float32), action=((T,) + tuple(self.action.shape), self.action.dtype),
+                    reward=((T, N), torch.float64), kind=((T, N), torch.uint8), **extra)
         if out is None:
-            out = Trajectory(obs=torch.empty(T + 1, N, W0, dtype=torch.float32, device=self.device),
-                             head=torch.empty(T, N, A, dtype=torch.float32, device=self.device),
-                             action=torch.empty(T, *self.action.shape, dtype=self.action.dtype, device=self.device),
-                             reward=torch.empty(T, N, dtype=torch.float64, device=self.device),
-                             kind=torch.empty(T, N, dtype=torch.uint8, device=self.device))
+            new = {k: torch.empty(*shape, dtype=dtype, device=self.device) for k, (shape, dtype) in want.items()}
+            out = Trajectory(**{k: t for k, t in new.items() if k not in extra})
+            for k in extra:
+                setattr(out, k, new[k])
         else:
-            want = dict(obs=((T + 1, N, W0), torch.float32), head=((T, N, A), torch.float32),
-                        action=((T,) + tuple(self.action.shape), self.action.dtype), reward=((T, N), torch.float64), kind=((T, N), torch.uint8))
             for name, (shape, dtype) in want.items():
                 t = getattr(out, name, None)
                 if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
                     raise ValueError("out.%s must be a contiguous %s %s tensor on the batch's device" % (name, dtype, list(shape)))
         out.noise, out.sigma = noise, sigma
         flags = abi.FTL_STEP_NEXT_RESET if auto_reset == "next_step" else 0
+        collect = getattr(self.lib, self._COLLECT)
         for (g, lo, net), s in zip(self._parts, self._streams(noise)):
-            cb = abi.CollectBuffers()
+            bufs, cb = self._collect_struct(out, lo)
             cb.obs, cb.head, cb.action = out.obs.data_ptr() + lo * W0 * 4, out.head.data_ptr() + lo * A * 4, out.action.data_ptr() + lo * self.row
             cb.reward, cb.kind = out.reward.data_ptr() + lo * 8, out.kind.data_ptr() + lo
             cb.noise = (noise.data_ptr() + lo * A * 4) if noise is not None else None
             cb.sigma = sigma.data_ptr() if sigma is not None else None
             cb.obs_step_bytes, cb.head_step_bytes, cb.action_step_bytes = N * W0 * 4, N * A * 4, N * self.row
             cb.reward_step_bytes, cb.kind_step_bytes, cb.noise_step_bytes = N * 8, N, N * A * 4
-            _lib.check(self.lib.ftl_collect_mlp(g.h, T, g._out_ref, C.byref(net), C.byref(cb), flags, s), self.lib)
+            _lib.check(collect(g.h, T, g._out_ref, C.byref(net), C.byref(bufs), flags, s), self.lib)
         self._keep = out                                            # (the parts' streams write into it: it outlives the call)
         return out
 

@@ -18,13 +18,43 @@ import ctypes as C
 import torch
 
 from . import _lib, abi
-from .mlp import FORWARD_MAX_BLOCKS, MlpPolicy, Trajectory, _device_handle, check_net_widths, check_widths, head_encoding
+from .mlp import MlpPolicy, Trajectory, _check_params, _device_handle, _held_params, _lead_blocks, _workspace, check_net_widths, check_widths
 
 _BEFORE = ("same_step", "queue", "sample")
 
 
+def _flags(prev_action, prev_reward):
+    return (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+
+
+def _rnn_struct(widths, cell, flags, params, n_sets, envs_per_set, state, env_first=0):
+    """The ``abi.Rnn`` of checked arguments: rows from ``env_first`` on, ``envs_per_set`` of them to a weight set; ``state`` is the
+    ``[rows, S]`` tensor whose row 0 belongs to env 0."""
+    S = abi.rnn_widths(widths, cell, flags)[3]
+    net = abi.Rnn()
+    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), abi.rnn_param_count(widths, cell, flags), n_sets, len(widths) - 2
+    for l, w in enumerate(widths):
+        net.width[l] = w
+    net.env_first, net.envs_per_set, net.cell, net.flags = env_first, envs_per_set, cell, flags
+    net.state, net.state_stride = state.data_ptr() + env_first * S * 4, S
+    return net
+
+
 class _RnnParams:
     """Views into ``params`` of a recurrent net (``widths``, ``trunk``, ``cell``, ``U``, ``n_sets``), shared by the policy and the critic."""
+
+    def _hold(self, widths, cell, n_sets, prev_action, prev_reward, params, device, who, head=None):
+        """The constructor body of ``RecurrentCritic`` and ``Net``: the checked shape and its derived widths, and the checked or new
+        ``params`` tensor, which it returns (the critic keeps the tensor, the net wraps it); ``who`` names the class in the message."""
+        self.widths, self.cell = check_rnn_widths(widths, cell)
+        if head is not None and self.widths[-1] != head:
+            raise ValueError("a critic's head is %d wide, not %d" % (head, self.widths[-1]))
+        self.trunk = self.widths[:-1]
+        self.prev_action, self.prev_reward = bool(prev_action), bool(prev_reward)
+        self.flags = _flags(prev_action, prev_reward)
+        self.P, self.R, self.U, self.S = abi.rnn_widths(self.widths, self.cell, self.flags)
+        self.n_sets, self.param_count = int(n_sets), abi.rnn_param_count(self.widths, self.cell, self.flags)
+        return _held_params(params, self.n_sets, self.param_count, device, who)
 
     def layer(self, l):
         """Views ``(W [n_sets, in, out], b [n_sets, out])`` of trunk layer ``l`` (0-based) in ``params``."""
@@ -73,6 +103,9 @@ class RecurrentPolicy(_RnnParams, MlpPolicy):
     ``act()`` / ``sample()`` are used with: it decides where the state is zeroed.  ``act()``, ``sample()`` and the call operator return the
     persistent action tensor like ``MlpPolicy``; like ``step`` they do not join a pipelined batch."""
 
+    _ROLLOUT, _COLLECT = "ftl_rollout_rnn", "ftl_collect_rnn"                          # (``rollout`` is ``MlpPolicy``'s)
+    _COUNT_MISMATCH = "ftl_rnn_param_count disagrees with abi.rnn_param_count: library and package do not match"
+
     def __init__(self, batch, widths, cell, n_sets=1, params=None, prev_action=True, prev_reward=True, auto_reset="next_step"):
         widths = tuple(int(w) for w in widths)
         if len(widths) < 3:
@@ -86,47 +119,22 @@ class RecurrentPolicy(_RnnParams, MlpPolicy):
         if auto_reset is not False and auto_reset != "next_step" and auto_reset not in _BEFORE:
             raise ValueError('auto_reset must be False, "next_step", "same_step", "queue" or "sample" (got %r)' % (auto_reset,))
         self.cell, self.auto_reset = cell, auto_reset
-        self.flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+        self.flags = _flags(prev_action, prev_reward)
         self.P, self.R, self.U, self.S = abi.rnn_widths(widths, cell, self.flags)
         self.widths, self.trunk = widths, widths[:-1]
-        self.encoding, _ = head_encoding(batch.cfg)
-        pol = getattr(batch, "policy_obs", None)
-        if pol is None:
-            raise ValueError("the policy reads policy_obs: build the batch with policy_obs=True on a config that has a sensor for it")
-        if widths[0] != pol.shape[1] * pol.shape[2]:
-            raise ValueError("widths[0] must be H * W = %d of policy_obs, not %d" % (pol.shape[1] * pol.shape[2], widths[0]))
-        n_sets = int(n_sets)
-        if n_sets < 1 or batch.n % n_sets:
-            raise ValueError("n_sets must divide the batch's %d envs" % batch.n)
-        self.batch, self.n, self.device, self.n_sets, self.envs_per_set = batch, batch.n, batch.device, n_sets, batch.n // n_sets
         self.param_count = abi.rnn_param_count(widths, cell, self.flags)
-        if params is None:
-            params = torch.zeros(n_sets, self.param_count, dtype=torch.float32, device=self.device)
-        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (n_sets, self.param_count)
-                or params.device != self.device or not params.is_contiguous()):
-            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the batch's device" % self.param_count)
-        self.params = params
+        self._bind(batch, n_sets, params)
+
+    def _buffers(self):
         self.state = torch.zeros(self.n, self.S, dtype=torch.float32, device=self.device)
-        self.lib = _lib.load()
-        if self.lib.ftl_rnn_param_count((C.c_int32 * len(widths))(*widths), len(widths) - 2, cell, self.flags) != self.param_count:
-            raise _lib.FtlError("ftl_rnn_param_count disagrees with abi.rnn_param_count: library and package do not match")
-        shape = (self.n, 2) if self.encoding == abi.FTL_ACTION_BOX2 else (self.n,)
-        self.action = torch.zeros(*shape, dtype=torch.int32 if self.encoding == abi.FTL_ACTION_DISCRETE else torch.float64, device=self.device)
-        self.row = self.action.element_size() * (2 if self.encoding == abi.FTL_ACTION_BOX2 else 1)
-        self.head = torch.zeros(self.n, widths[-1], dtype=torch.float32, device=self.device)
-        self.obs = torch.zeros(self.n, widths[0], dtype=torch.float32, device=self.device)
-        games = getattr(batch, "games", None)
-        self._parts = [(g, lo, self._net(lo)) for g, lo in ([(batch, 0)] if games is None else [(g, sh.lo) for g, sh in zip(games, batch.shards)])]
+        self.head = torch.zeros(self.n, self.widths[-1], dtype=torch.float32, device=self.device)
+        self.obs = torch.zeros(self.n, self.widths[0], dtype=torch.float32, device=self.device)
+
+    def _lib_param_count(self):
+        return self.lib.ftl_rnn_param_count((C.c_int32 * len(self.widths))(*self.widths), len(self.widths) - 2, self.cell, self.flags)
 
     def _net(self, env_first):
-        net = abi.Rnn()
-        net.params, net.set_stride, net.n_sets, net.n_layers = self.params.data_ptr(), self.param_count, self.n_sets, len(self.widths) - 2
-        for l, w in enumerate(self.widths):
-            net.width[l] = w
-        net.env_first, net.envs_per_set = env_first, self.envs_per_set
-        net.cell, net.flags = self.cell, self.flags
-        net.state, net.state_stride = self.state.data_ptr() + env_first * self.S * 4, self.S
-        return net
+        return _rnn_struct(self.widths, self.cell, self.flags, self.params, self.n_sets, self.envs_per_set, self.state, env_first)
 
     def reset_state(self, env_ids=None):
         """Zero the state of every env, or of ``env_ids``: the rows of a fresh episode (after a ``batch.reset`` of those envs)."""
@@ -162,58 +170,17 @@ class RecurrentPolicy(_RnnParams, MlpPolicy):
         self._keep = (noise, sigma, state_rec)
         return self.action
 
-    def rollout(self, T, gamma=1.0, record=False):
-        """``batch.rollout_rnn(self, ...)``."""
-        b, T = self.batch, int(T)
-        b._need_pool()
-        if T < 1:
-            raise ValueError("a rollout needs T >= 1")
-        actions = torch.empty(T, *self.action.shape, dtype=self.action.dtype, device=self.device) if record else None
-        b._prepare_rollout_outputs()
-        ap = actions.data_ptr() if record else 0
-        for (g, lo, net), s in zip(self._parts, self._streams(actions)):
-            _lib.check(self.lib.ftl_rollout_rnn(g.h, T, float(gamma), g._out_ref, C.byref(g._rollout_outputs()), C.byref(net),
-                                                (ap + lo * self.row) if record else None, self.n * self.row if record else 0, 0, s), self.lib)
-        out = (b.rollout_ret, b.rollout_steps, b.rollout_status)
-        return out + (actions,) if record else out
-
     def collect(self, T, noise=None, sigma=None, auto_reset="next_step", out=None, record_state=False):
         """``batch.collect_rnn(self, ...)``."""
-        b, T = self.batch, int(T)
-        b._need_pool()
-        if T < 1:
-            raise ValueError("a trajectory needs T >= 1")
-        if auto_reset is not False and auto_reset != "next_step":
-            raise ValueError('collect() takes auto_reset=False or "next_step": the other modes put the next episode\'s first observation where '
-                             'the terminal one belongs (got %r)' % (auto_reset,))
-        self._check_noise(noise, sigma, lead=(T,))
-        A, W0, N, S = self.widths[-1], self.widths[0], self.n, self.S
-        TS = T if record_state else 1
-        want = dict(obs=((T + 1, N, W0), torch.float32), head=((T, N, A), torch.float32), action=((T,) + tuple(self.action.shape), self.action.dtype),
-                    reward=((T, N), torch.float64), kind=((T, N), torch.uint8), state=((TS, N, S), torch.float32))
-        if out is None:
-            out = Trajectory(**{k: torch.empty(*shape, dtype=dtype, device=self.device) for k, (shape, dtype) in want.items() if k != "state"})
-            out.state = torch.empty(TS, N, S, dtype=torch.float32, device=self.device)
-        else:
-            for name, (shape, dtype) in want.items():
-                t = getattr(out, name, None)
-                if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous()):
-                    raise ValueError("out.%s must be a contiguous %s %s tensor on the batch's device" % (name, dtype, list(shape)))
-        out.noise, out.sigma = noise, sigma
-        flags = abi.FTL_STEP_NEXT_RESET if auto_reset == "next_step" else 0
-        for (g, lo, net), s in zip(self._parts, self._streams(noise)):
-            rb = abi.RnnCollectBuffers()
-            cb = rb.b
-            cb.obs, cb.head, cb.action = out.obs.data_ptr() + lo * W0 * 4, out.head.data_ptr() + lo * A * 4, out.action.data_ptr() + lo * self.row
-            cb.reward, cb.kind = out.reward.data_ptr() + lo * 8, out.kind.data_ptr() + lo
-            cb.noise = (noise.data_ptr() + lo * A * 4) if noise is not None else None
-            cb.sigma = sigma.data_ptr() if sigma is not None else None
-            cb.obs_step_bytes, cb.head_step_bytes, cb.action_step_bytes = N * W0 * 4, N * A * 4, N * self.row
-            cb.reward_step_bytes, cb.kind_step_bytes, cb.noise_step_bytes = N * 8, N, N * A * 4
-            rb.state, rb.state_step_bytes, rb.state_steps = out.state.data_ptr() + lo * S * 4, N * S * 4, TS
-            _lib.check(self.lib.ftl_collect_rnn(g.h, T, g._out_ref, C.byref(net), C.byref(rb), flags, s), self.lib)
-        self._keep = out
-        return out
+        return self._collect(T, noise, sigma, auto_reset, out, record_state)
+
+    def _state_blocks(self, T, record_state):
+        return dict(state=((T if record_state else 1, self.n, self.S), torch.float32))
+
+    def _collect_struct(self, out, lo):
+        rb = abi.RnnCollectBuffers()
+        rb.state, rb.state_step_bytes, rb.state_steps = out.state.data_ptr() + lo * self.S * 4, self.n * self.S * 4, int(out.state.shape[0])
+        return rb, rb.b
 
     def forward(self, traj, reward0=None, **outs):
         """The policy's own net -- its sets and its flags -- replayed on a trajectory its ``collect`` recorded, in one launch (the
@@ -255,24 +222,15 @@ def _check_sequence(widths, cell, params, obs, action, reward, kind, state, rewa
     """The checks ``forward`` and ``backward`` share, in ``forward``'s order; returns ``(widths, cell, flags, count, n_sets, B, N, dev)``."""
     widths, cell = check_rnn_widths(widths, cell)
     A, W0 = widths[-1], widths[0]
-    flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
+    flags = _flags(prev_action, prev_reward)
     P, R, U, S = abi.rnn_widths(widths, cell, flags)
     count = abi.rnn_param_count(widths, cell, flags)
-    if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == count
-            and params.shape[0] >= 1 and params.is_contiguous()):
-        raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor" % count)
-    n_sets = int(params.shape[0])
+    n_sets = int(_check_params(params, count).shape[0])
     if not (torch.is_tensor(obs) and obs.dtype == torch.float32 and obs.dim() == 3 and obs.shape[2] == W0 and obs.is_contiguous()):
         raise ValueError("obs must be a contiguous float32 [B, N, %d] tensor" % W0)
     if obs.requires_grad or params.requires_grad:
         raise ValueError(grad_msg)
-    B, N, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
-    if B < 1 or N < 1:
-        raise ValueError("obs must hold at least one block of at least one row, not %s" % (list(obs.shape),))
-    if N % n_sets:
-        raise ValueError("n_sets = %d must divide the %d rows of a block" % (n_sets, N))
-    if B > FORWARD_MAX_BLOCKS:
-        raise NotImplementedError("at most %d blocks in one call, not %d" % (FORWARD_MAX_BLOCKS, B))
+    (_, N, B), dev = _lead_blocks(obs, "obs", n_sets), obs.device
     adt, atail = (torch.int32, (N,)) if A == 5 else (torch.float64, (N, 2) if A == 2 else (N,))
     need = (("action", action, adt, atail, bool(P)), ("reward", reward, torch.float64, (N,), bool(R)), ("kind", kind, torch.uint8, (N,), True))
     for name, t, dtype, tail, used in need:
@@ -293,12 +251,7 @@ def _structs(widths, cell, flags, count, n_sets, params, obs, action, reward, ki
     A, W0 = widths[-1], widths[0]
     P, R, U, S = abi.rnn_widths(widths, cell, flags)
     B, N = int(obs.shape[0]), int(obs.shape[1])
-    net = abi.Rnn()
-    net.params, net.set_stride, net.n_sets, net.n_layers = params.data_ptr(), count, n_sets, len(widths) - 2
-    for l, w in enumerate(widths):
-        net.width[l] = w
-    net.env_first, net.envs_per_set, net.cell, net.flags = 0, N // n_sets, cell, flags
-    net.state, net.state_stride = state.data_ptr(), S
+    net = _rnn_struct(widths, cell, flags, params, n_sets, N // n_sets, state)
     seq = abi.RnnSequence()
     seq.obs, seq.obs_block_bytes = obs.data_ptr(), N * W0 * 4
     if B > 1:
@@ -375,22 +328,8 @@ class RecurrentCritic(_RnnParams):
     refuses any other action record with ``ValueError``.  The default feeds the last reward only."""
 
     def __init__(self, widths, cell, n_sets=1, prev_reward=True, params=None, device=None, prev_action=False):
-        self.widths, self.cell = check_rnn_widths(widths, cell)
-        if self.widths[-1] != 1:
-            raise ValueError("a critic's head is 1 wide, not %d" % self.widths[-1])
-        self.trunk = self.widths[:-1]
-        self.prev_action, self.prev_reward = bool(prev_action), bool(prev_reward)
-        self.flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
-        self.P, self.R, self.U, self.S = abi.rnn_widths(self.widths, self.cell, self.flags)
-        self.n_sets, self.param_count = int(n_sets), abi.rnn_param_count(self.widths, self.cell, self.flags)
-        if self.n_sets < 1:
-            raise ValueError("n_sets must be at least 1")
-        if params is None:
-            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
-        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
-                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
-            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the critic's device" % self.param_count)
-        self.params, self.device = params, params.device
+        self.params = self._hold(widths, cell, n_sets, prev_action, prev_reward, params, device, "critic", head=1)
+        self.device = self.params.device
 
     def values(self, traj, state=None, reward0=None, out=None):
         """``(values, carry)``: float32 ``[T + 1, N]``, the value of every ``traj.obs[t]`` with the memory of the blocks before it -- what
@@ -418,9 +357,6 @@ class RecurrentCritic(_RnnParams):
         v = forward(self.widths, self.cell, self.params, traj.obs, traj.action if self.prev_action else None, traj.reward, traj.kind, state,
                     reward0, self.prev_action, self.prev_reward, out=values, state_out=carry, state_at=T1 - 1)
         return v[..., 0], carry
-
-
-_BWD_WORKSPACE = {}
 
 
 def backward(widths, cell, params, obs, dhead, action=None, reward=None, kind=None, state=None, reward0=None, prev_action=True,
@@ -466,11 +402,7 @@ def backward(widths, cell, params, obs, dhead, action=None, reward=None, kind=No
     need = lib.ftl_sizeof_rnn_backward_workspace(C.byref(net), B, N)
     if need < 0:
         raise _lib.FtlError("ftl_sizeof_rnn_backward_workspace refused a net that the package's checks passed")
-    raw = torch.cuda.current_stream(dev).cuda_stream
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), raw)
-    ws = _BWD_WORKSPACE.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = _BWD_WORKSPACE[key] = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+    ws, raw = _workspace("rnn_backward", dev, need)
     g = abi.RnnGradient()
     g.dhead, g.dhead_block_bytes, g.grad = dhead.data_ptr(), N * A * 4, out.data_ptr()
     g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
@@ -513,19 +445,7 @@ class Net(_RnnParams, torch.nn.Module):
 
     def __init__(self, widths, cell, n_sets=1, prev_action=True, prev_reward=True, params=None, device=None):
         torch.nn.Module.__init__(self)
-        self.widths, self.cell = check_rnn_widths(widths, cell)
-        self.trunk = self.widths[:-1]
-        self.prev_action, self.prev_reward = bool(prev_action), bool(prev_reward)
-        self.flags = (abi.FTL_RNN_PREV_ACTION if prev_action else 0) | (abi.FTL_RNN_PREV_REWARD if prev_reward else 0)
-        self.P, self.R, self.U, self.S = abi.rnn_widths(self.widths, self.cell, self.flags)
-        self.n_sets, self.param_count = int(n_sets), abi.rnn_param_count(self.widths, self.cell, self.flags)
-        if self.n_sets < 1:
-            raise ValueError("n_sets must be at least 1")
-        if params is None:
-            params = torch.zeros(self.n_sets, self.param_count, dtype=torch.float32, device=torch.device("cuda" if device is None else device))
-        if (not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (self.n_sets, self.param_count)
-                or not params.is_contiguous() or (device is not None and params.device != torch.device(device))):
-            raise ValueError("params must be a contiguous float32 [n_sets, %d] tensor on the net's device" % self.param_count)
+        params = self._hold(widths, cell, n_sets, prev_action, prev_reward, params, device, "net")
         self.params = torch.nn.Parameter(params.detach())       # (the parameter shares the tensor's storage)
 
     def forward(self, seq, state=None, reward0=None):

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from continiousenvironment_follower_leader_amd import abi, rnn  # noqa: E402
+from continiousenvironment_follower_leader_amd import abi, mlp, rnn  # noqa: E402
 from mlp_forward_times import peak_above, spread  # noqa: E402
 from mlp_policy_times import layer_views, timed  # noqa: E402
 
@@ -162,7 +162,7 @@ def main():
             diff, scale = float((ga - gb).abs().max()), float(gb.abs().max())
             del ga, gb
             mem = dict(net=peak_above(fa), torch=peak_above(fb))
-            workspace = max(t.numel() * 4 for t in rnn._BWD_WORKSPACE.values())
+            workspace = max(t.numel() * 4 for key, t in mlp._WORKSPACE.items() if key[0] == "rnn_backward")
             times = dict(net=[], torch=[])
             for _ in range(a.rounds):
                 times["net"].append(timed(lambda: [fa() for _ in range(a.reps)], a.reps))
@@ -173,7 +173,7 @@ def main():
                 peak_bytes_above_inputs=mem, cached_workspace_bytes=workspace, max_abs_difference_of_the_gradients=diff, max_abs_gradient=scale)
             print(json.dumps({k: result[k] for k in list(result)[-1:]}), flush=True)
             del net, tparams, v, mods
-            rnn._BWD_WORKSPACE.clear()
+            mlp._WORKSPACE.clear()
             torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

@@ -232,7 +232,8 @@ def test_python_surface_needs_no_device(cfg_b):
     from continiousenvironment_follower_leader_amd.mlp import MlpPolicy, check_widths, head_encoding
     from continiousenvironment_follower_leader_amd.vec_game import PipelinedVecGame, VecGame
     p = inspect.signature(MlpPolicy.__init__).parameters
-    assert list(p)[1:] == ["batch", "widths", "params", "n_sets"] and p["params"].default is None and p["n_sets"].default == 1
+    assert list(p)[1:] == ["batch", "widths", "params", "n_sets", "activation"] and p["params"].default is None and p["n_sets"].default == 1
+    assert p["activation"].default == "relu" and all(q.kind is q.POSITIONAL_OR_KEYWORD for q in p.values())    # (a plain signature)
     p = inspect.signature(MlpPolicy.rollout).parameters
     assert list(p)[1:] == ["T", "gamma", "record"] and [p[k].default for k in list(p)[2:]] == [1.0, False]
     for cls in (VecGame, PipelinedVecGame):

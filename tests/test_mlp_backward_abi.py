@@ -165,6 +165,9 @@ def test_python_surface(monkeypatch):
     assert list(p)[1:] == ["widths", "n_sets", "activation", "params", "device"]
     assert [p[k].default for k in list(p)[2:]] == [1, "relu", None, None]
     assert issubclass(mlp.Net, torch.nn.Module) and all(callable(getattr(mlp.Net, name)) for name in ("load", "module", "forward"))
+    for name in ("module", "_hold"):                                                    # one base under Net and Critic: shared, not copied
+        assert getattr(mlp.Net, name) is getattr(mlp.Critic, name) and name not in vars(mlp.Net) and name not in vars(mlp.Critic)
+    assert mlp.Critic.load is mlp._Holder.load and "load" not in vars(mlp.Critic)      # (Net.load is the same under no_grad)
 
     widths = (5, 4, 3)
     count = abi.mlp_param_count(widths)

@@ -248,6 +248,9 @@ def test_python_surface_needs_no_device(cfg_b):
         assert list(inspect.signature(cls.rollout_rnn).parameters)[1:] == ["policy", "T", "gamma", "record"]
         assert list(inspect.signature(cls.collect_rnn).parameters)[1:] == ["policy", "T", "noise", "sigma", "auto_reset", "out", "record_state"]
     assert issubclass(rnn.RecurrentPolicy, mlp.MlpPolicy)
+    assert rnn.RecurrentPolicy.rollout is mlp.MlpPolicy.rollout and "rollout" not in vars(rnn.RecurrentPolicy)     # shared, not copied
+    assert rnn.RecurrentPolicy._bind is mlp.MlpPolicy._bind and rnn.RecurrentPolicy._collect is mlp.MlpPolicy._collect
+    assert rnn.RecurrentCritic.cell_weights is rnn.Net.cell_weights and rnn.RecurrentCritic._hold is rnn.Net._hold
 
     class FakeBatch:
         n, device, policy_obs = 6, "cpu", None
